@@ -3,6 +3,8 @@
 problem (BASELINE.json configs[4], grid 512^3), one process per GPU.
 
   python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run)
+  python bench.py --gpus 1 --steps K --warmup W --full   (every figure below, not only the headline)
+  python bench.py --gpus 1 --steps K --warmup W --dump-outputs bench_outputs
 
 A "step" is one application of the V-cycle preconditioner (MultiGridPrecond::solve, reference
 src/common/bicg.cpp:51-61) to a fixed right-hand side that is already resident in HBM.  The
@@ -10,10 +12,18 @@ hierarchy is built on the device (mgs_hier_coarsen) before the timed region.  N>
 fine grid by contiguous plane ranges (strong scaling: the 512^3 problem is fixed) and exchanges
 one halo plane per neighbour per SpMV-shaped kernel through torch.distributed (RCCL).
 
-Prints ONE JSON line on rank 0 (see the contract in the task description): value = whole-job
-V-cycles/s; "roofline" = achieved algorithmic HBM GB/s of the fine-level SpMV kernel measured
-live with HIP events on the stream the kernel runs on; "cpu_baseline" = the CPU oracle's V-cycle
-(port of the same cycle) timed on this host on a bounded sample.
+Prints ONE JSON line on rank 0: value = whole-job V-cycles/s over exactly K timed steps,
+ms_per_step = milliseconds of one of them.  A plain run does only that: set-up, W warm-up
+steps, the K timed steps, the outputs (--dump-outputs) and the line.  --full adds everything
+else, as its own untimed legs: "roofline" = achieved HBM GB/s of the fine-level SpMV kernel
+measured live with HIP events on the stream the kernel runs on; "solve_check" = solves to
+1e-10 (BiCGSTAB and FGCR + K-cycle, the convection-diffusion leg); "bundled_matrices";
+"cpu_baseline" = the CPU oracle's V-cycle (port of the same cycle) timed on this host.
+
+--dump-outputs DIR writes what the last timed step computed, x = M^-1 b, as DIR/x.npy (float64)
+when it fits in 64 MB, else a fixed sample of it: DIR/x_sample.npy at the row indices in
+DIR/x_sample_index.npy (2^20 rows drawn with seed 0).  b is seeded, so the same arguments give
+the same inputs in every run.
 """
 import argparse
 import ctypes as C
@@ -396,11 +406,32 @@ def emit_json(obj):
         sys.stdout.write(line.decode()); sys.stdout.flush()
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_ROWS = 1 << 20
+
+
+def dump_outputs(d, x):
+    """the timed path's result (x = M^-1 b of the last step) as float64 .npy files under d: the whole vector when it fits in
+    DUMP_MAX_BYTES, else DUMP_SAMPLE_ROWS rows at indices drawn with a fixed seed (the same rows for the same grid in every run)"""
+    os.makedirs(d, exist_ok=True)
+    xh = np.ascontiguousarray(x, dtype=np.float64)
+    if xh.nbytes <= DUMP_MAX_BYTES:
+        np.save(os.path.join(d, "x.npy"), xh)
+        return ["x"]
+    idx = np.sort(np.random.default_rng(0).choice(xh.size, DUMP_SAMPLE_ROWS, replace=False))
+    np.save(os.path.join(d, "x_sample.npy"), xh[idx])
+    np.save(os.path.join(d, "x_sample_index.npy"), idx.astype(np.float64))
+    return ["x_sample", "x_sample_index"]
+
+
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (V-cycles); >= 1")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true", help="also run every leg beside the headline (roofline kernel timings, unfused A/B, solve checks, "
+                                                         "bundled operators, convection-diffusion, CPU baseline); off: headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's result as DIR/<name>.npy (one GPU only)")
     ap.add_argument("--grid", type=int, default=512, help="N of the N^3 7-point Poisson grid (headline: 512)")
     ap.add_argument("--omega", type=float, default=0.6)
     ap.add_argument("--nu1", type=int, default=1)
@@ -416,7 +447,12 @@ def parse_args():
     ap.add_argument("--no-convdiff", action="store_true", help="skip the 256^3 convection-diffusion leg (untimed solve comparison)")
     ap.add_argument("--convdiff-grid", type=int, default=256)
     ap.add_argument("--kernel-reps", type=int, default=20)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.gpus != 1:
+        ap.error("--dump-outputs is supported with --gpus 1 only")
+    return args
 
 
 def main():
@@ -453,12 +489,14 @@ def main():
     if args.gpus != world:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE is {world}")
     if world > 1 or os.environ.get("MGS_FORCE_SHARDED"):   # MGS_FORCE_SHARDED: rehearse the sharded code path on one rank
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs is supported on the unsharded one-GPU path only")
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1"); os.environ.setdefault("MASTER_PORT", "29755")
         os.environ.setdefault("RANK", "0"); os.environ.setdefault("WORLD_SIZE", "1")
         from multigridsolver_amd import dist as mgdist
         args.no_cpu_cross = True        # N > 1: the run's time budget (launch.py) goes to transport generations, not to a second oracle sample
         return mgdist.bench_sharded(args, rank, world, local_rank, log, spmv_bytes, emit_json,
-                                    cpu_baseline=None if args.no_cpu else (lambda: cpu_baseline(mg, args)),
+                                    cpu_baseline=None if (args.no_cpu or not args.full) else (lambda: cpu_baseline(mg, args)),
                                     pmc_traffic=pmc_traffic)
     torch.cuda.set_device(local_rank)
 
@@ -481,29 +519,33 @@ def main():
 
     b = ctx.vec(n).rand(seed=0)
     x = ctx.vec(n)
-    # ---- roofline of the dominant kernel: fine-level CSR SpMV (HIP events on the kernel's stream)
+    # ---- roofline of the dominant kernel: fine-level CSR SpMV (HIP events on the kernel's stream), --full only.  A plain run makes the
+    # same allocations and the same pattern code in the same order without the timed launches: the arena then places the cycle's operands
+    # where a --full run places them, so the headline is the same figure in both (placement moves a kernel by a few %, profiles/r03_spread.md)
     xs = ctx.vec(n).rand(seed=1)
     y = ctx.vec(n)
     dinv = A.diag_inv()
     # plain CSR kernel first (12 B per entry streamed), then the shipped path: pattern-coded column index
     # (mgs_csr_optimize: 8 B per entry + 1 B per row streamed; same products, same bits)
     ctx.set_option("rowcode", 0)
-    A.time_kernel(mg.OP_SPMV, xs, out=y, reps=3)
-    ms_spmv_csr = A.time_kernel(mg.OP_SPMV, xs, out=y, reps=args.kernel_reps)
+    if args.full:
+        A.time_kernel(mg.OP_SPMV, xs, out=y, reps=3)
+        ms_spmv_csr = A.time_kernel(mg.OP_SPMV, xs, out=y, reps=args.kernel_reps)
     ctx.set_option("rowcode", 1)
     A.optimize()
     code = A.rowcode_info()
     streamed = (8 * nnz + 17 * n + n // 16 + 4 * code["table_ints"] + 4 * (code["blocks"] + 1) * 2) if code["coded_blocks"] == code["blocks"] else None
-    A.time_kernel(mg.OP_SPMV, xs, out=y, reps=3)
-    ms_spmv = A.time_kernel(mg.OP_SPMV, xs, out=y, reps=args.kernel_reps)
-    ms_res = A.time_kernel(mg.OP_RESIDUAL, xs, b=b, out=y, reps=args.kernel_reps)
-    ms_jac = A.time_kernel(mg.OP_JACOBI, xs, b=b, dinv=dinv, out=y, reps=args.kernel_reps)
     gbps = lambda byts, ms: byts / (ms * 1e-3) / 1e9  # noqa: E731
-    spmv_gbps = gbps(spmv_bytes(n, nnz), ms_spmv)
-    log(f"fine SpMV, plain CSR kernel {ms_spmv_csr:.3f} ms = {gbps(spmv_bytes(n, nnz), ms_spmv_csr):.0f} GB/s; pattern-coded: streams "
-        f"{(streamed or 0) / 1e9:.2f} GB of the {spmv_bytes(n, nnz) / 1e9:.2f} algorithmic GB")
-    log(f"fine SpMV {ms_spmv:.3f} ms = {spmv_gbps:.0f} GB/s; residual {ms_res:.3f} ms = {gbps(residual_bytes(n, nnz), ms_res):.0f} GB/s; "
-        f"jacobi {ms_jac:.3f} ms = {gbps(jacobi_bytes(n, nnz), ms_jac):.0f} GB/s")
+    if args.full:
+        A.time_kernel(mg.OP_SPMV, xs, out=y, reps=3)
+        ms_spmv = A.time_kernel(mg.OP_SPMV, xs, out=y, reps=args.kernel_reps)
+        ms_res = A.time_kernel(mg.OP_RESIDUAL, xs, b=b, out=y, reps=args.kernel_reps)
+        ms_jac = A.time_kernel(mg.OP_JACOBI, xs, b=b, dinv=dinv, out=y, reps=args.kernel_reps)
+        spmv_gbps = gbps(spmv_bytes(n, nnz), ms_spmv)
+        log(f"fine SpMV, plain CSR kernel {ms_spmv_csr:.3f} ms = {gbps(spmv_bytes(n, nnz), ms_spmv_csr):.0f} GB/s; pattern-coded: streams "
+            f"{(streamed or 0) / 1e9:.2f} GB of the {spmv_bytes(n, nnz) / 1e9:.2f} algorithmic GB")
+        log(f"fine SpMV {ms_spmv:.3f} ms = {spmv_gbps:.0f} GB/s; residual {ms_res:.3f} ms = {gbps(residual_bytes(n, nnz), ms_res):.0f} GB/s; "
+            f"jacobi {ms_jac:.3f} ms = {gbps(jacobi_bytes(n, nnz), ms_jac):.0f} GB/s")
     del xs, y
 
     # the first cycle builds the setup-time operands of the fused passes (Â = A·diag(ωD⁻¹), A·P, pattern codes, row-block groups):
@@ -523,8 +565,26 @@ def main():
     ctx.sync(); torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     ms_step = elapsed / args.steps * 1e3
-    vbytes = h.vcycle_bytes
     log(f"V-cycle {ms_step:.3f} ms ({args.steps / elapsed:.2f} /s)")
+    if args.dump_outputs:          # before any other leg touches x
+        names = dump_outputs(args.dump_outputs, x.numpy())
+        log(f"outputs of the last timed step written to {args.dump_outputs}: " + ", ".join(names))
+    out = {
+        "metric": "V-cycles/sec + fine-level SpMV HBM GB/s, 512³ 7-pt Poisson, 1/2/4/8 GPU",
+        "value": args.steps / elapsed, "unit": "V-cycles/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_step, "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
+        "data": "synthetic", "full": args.full,
+        "config": {"workload": f"poisson3d_{N}^3_7pt (BASELINE.json configs[4]); V({args.nu1},{args.nu2}) damped-Jacobi cycle, omega={args.omega}, "
+                               f"hierarchy built on device by pairwise aggregation ktg={args.ktg} npass={args.npass} tou={args.tou}",
+                   "grid": N, "rows": n, "nnz": nnz, "levels": levels, "parallelism": "1 GPU", "setup_seconds": t_setup,
+                   "first_cycle_seconds_incl_operand_setup": t_operands, "device_arena_gb": float(os.environ.get("MGS_ARENA_GB", "0"))},
+    }
+    if not args.full:
+        del h, A, b, x, dinv
+        ctx.close()
+        emit_json(out)
+        return
+    vbytes = h.vcycle_bytes
 
     # A/B inside the same process: the unfused one-kernel-per-step form of the same cycle
     ctx.set_option("fuse", 0)
@@ -602,15 +662,7 @@ def main():
     summ = pmc_summary(N)
     cyc = (summ[0].get("vcycle") if summ else None) or {}
     cyc_bytes = cyc.get("traffic_bytes")
-    out = {
-        "metric": "V-cycles/sec + fine-level SpMV HBM GB/s, 512³ 7-pt Poisson, 1/2/4/8 GPU",
-        "value": args.steps / elapsed, "unit": "V-cycles/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms_step, "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
-        "data": "synthetic",
-        "config": {"workload": f"poisson3d_{N}^3_7pt (BASELINE.json configs[4]); V({args.nu1},{args.nu2}) damped-Jacobi cycle, omega={args.omega}, "
-                               f"hierarchy built on device by pairwise aggregation ktg={args.ktg} npass={args.npass} tou={args.tou}",
-                   "grid": N, "rows": n, "nnz": nnz, "levels": levels, "parallelism": "1 GPU", "setup_seconds": t_setup,
-                   "first_cycle_seconds_incl_operand_setup": t_operands, "device_arena_gb": float(os.environ.get("MGS_ARENA_GB", "0"))},
+    out.update({
         "spmv_hbm_gbps": gbps(phys_bytes, ms_spmv),
         "spmv_effective_csr_gbps": spmv_gbps,
         # roofline of the dominant kernel = what crosses HBM per second against the 8 TB/s peak.  The SURVEY §8d-d3 figure (CSR bytes /
@@ -649,7 +701,7 @@ def main():
                         "fgcr10_kcycle4_energy_omega08": {"runs": kruns08, "spd_only": True,
                                                           "note": "the same solve with the smoother's damping omega = 0.8 (a value the reference's own two-grid tests run; the headline "
                                                                   "cycle and every figure above use the default 0.6); tools/fgcr_knobs.py scans omega x K levels x restart length"}},
-    }
+    })
     del h, A, b, x, xsol, dinv
     ctx.close()
     if args.optin:       # a second hierarchy for a figure that only constant-coefficient operators see: not part of the default run

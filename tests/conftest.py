@@ -5,6 +5,9 @@ import sys
 
 import numpy as np
 import pytest
+# before any test loads libmgs.so (multigridsolver_amd/_lib.py): torch ships its own HIP runtime, and with libmgs loaded first one
+# test process would hold two — once a CPU test has asked torch for the device, the GPU tests' in-process contexts find none
+import torch  # noqa: F401
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if REPO not in sys.path:

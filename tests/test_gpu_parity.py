@@ -1436,13 +1436,13 @@ print("ARENA", cap, x1.tobytes().hex()[:64], np.float64(s1).sum().hex(), it1)
 
 
 def test_bench_line_contract_small_grid():
-    """bench.py as the driver runs it (one process, one GPU), at a small grid so that the whole run takes seconds: ONE JSON line on stdout with the
+    """bench.py --full (one process, one GPU), at a small grid so that the whole run takes seconds: ONE JSON line on stdout with the
     contract's fields, `roofline` and `cpu_baseline` objects, and the solve checks — every solve converged on its TRUE residual, the convection-
     diffusion leg included.  (The oracle is used by the cpu_baseline leg only.)"""
     import json, subprocess, sys
     from conftest import REPO
     p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--grid", "96", "--steps", "5", "--warmup", "2", "--kernel-reps", "5",
-                        "--convdiff-grid", "48", "--no-cpu-cross"], capture_output=True, text=True, timeout=600, cwd=REPO)
+                        "--convdiff-grid", "48", "--no-cpu-cross", "--full"], capture_output=True, text=True, timeout=600, cwd=REPO)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines
@@ -1471,6 +1471,34 @@ def test_bench_line_contract_small_grid():
     for run in cd["runs"]:
         assert run["bicgstab_vcycle"]["status"] == 0 and run["bicgstab_vcycle"]["true_residual"] <= 2e-10
         assert run["fgcr10_kcycle_gcr"]["true_residual"] <= 2e-10 or run["fgcr10_kcycle_gcr"]["status"] != 0      # status 0 only on the true residual
+
+
+def test_bench_plain_line_and_dumped_outputs(ctx, mg, tmp_path):
+    """a plain bench.py run (no --full): ONE JSON line with the headline fields and none of the --full legs; --dump-outputs writes the
+    last timed step's x = M^-1 b, bit for bit the V-cycle of the same operator and seeded right-hand side built here"""
+    import json, subprocess, sys
+    from conftest import REPO
+    N, n = 96, 96 ** 3
+    d = tmp_path / "out"
+    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--grid", str(N), "--steps", "4", "--warmup", "1", "--dump-outputs", str(d)],
+                       capture_output=True, text=True, timeout=300, cwd=REPO)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    r = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config"):
+        assert k in r, k
+    assert r["steps"] == 4 and r["warmup"] == 1 and r["unit"] == "V-cycles/s" and r["dtype"] == "f64" and r["full"] is False
+    assert abs(r["value"] - 1e3 / r["ms_per_step"]) <= 1e-6 * r["value"]
+    for k in ("roofline", "solve_check", "bundled_matrices", "cpu_baseline"):
+        assert k not in r, k
+    assert sorted(os.listdir(d)) == ["x.npy"]
+    x = np.load(d / "x.npy")
+    assert x.dtype == np.float64 and x.shape == (n,)
+    A = ctx.poisson3d(N)
+    h = mg.Hierarchy(A, 0.6, 1, 1).coarsen(10.0, 2, 8.0, 2500, 32).finalize()
+    b = ctx.vec(n).rand(seed=0)
+    assert np.array_equal(x, h.vcycle(b).numpy())
 
 
 def test_kcycle_split_launch_same_bits(ctx, mg):

@@ -1,36 +1,29 @@
 """The drop-in claim under test: the reference's OWN `main()` — the text of
-src/common/bicg.cpp from `int main` to the end of the file, read from the reference checkout at test time, never stored
-here — compiles and links as written behind `#include "mgs_host.hpp"` + `using namespace mgs;`.  Build container only
-(skipped where /root/reference is absent, i.e. on the GPU box); nothing is executed: no GPU here."""
+src/common/bicg.cpp from `int main` to the end of the file, never stored here — compiles and links as written behind
+`#include "mgs_host.hpp"` + `using namespace mgs;`.  build() compiles it by the recipe in oracle/Makefile into
+oracle/_ref/ref_main_mgs (with its translation unit beside it) wherever the reference checkout was there to build from;
+this test checks what that build made.  Only the usage path runs: no device is touched."""
 import os
-import re
 import subprocess
 
 import pytest
 
 from conftest import REPO
 
-REF = "/root/reference/src/common/bicg.cpp"
+REF = os.path.join(REPO, "oracle", "_ref")
+TU = os.path.join(REF, "ref_main_tu.cpp")
+EXE = os.path.join(REF, "ref_main_mgs")
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="reference checkout not present (GPU box)")
-def test_reference_main_compiles_and_links_against_mgs_host(tmp_path):
-    text = open(REF).read()
-    m = re.search(r"^int main\s*\(", text, flags=re.M)
-    assert m, "reference main() not found"
-    main_src = text[m.start():]
+def test_reference_main_compiles_and_links_against_mgs_host():
+    if not os.path.exists(os.path.join(REF, "ref_dump")):
+        pytest.skip("oracle/_ref not built: the reference checkout was not there when build() ran")
+    assert os.path.exists(TU) and os.path.exists(EXE), "oracle/_ref has the reference build but not ref_main_mgs (oracle/Makefile)"
+    text = open(TU).read()
+    assert '#include "mgs_host.hpp"' in text and "using namespace mgs;" in text
+    main_src = text[text.index("int main"):]
     assert "BiCGSTABiml(A, x, b, precond, max_iter, tol)" in main_src and "readMatrix(" in main_src and "VectorXd" in main_src
-    tu = tmp_path / "ref_main_tu.cpp"
-    tu.write_text('#include <cstdio>\n#include <cstdlib>\n#include <iostream>\n#include <string>\n'
-                  f'#include "{os.path.join(REPO, "multigridsolver_amd", "cpp", "mgs_host.hpp")}"\n'
-                  "using namespace std;\nusing namespace mgs;\n" + main_src)
-    lib = os.path.join(REPO, "multigridsolver_amd")
-    assert os.path.exists(os.path.join(lib, "libmgs.so")), "libmgs.so not built (run __graft_entry__.build())"
-    exe = tmp_path / "ref_main"
-    r = subprocess.run(["g++", "-std=c++14", "-O1", "-Wall", "-o", str(exe), str(tu), f"-L{lib}", "-lmgs", f"-Wl,-rpath,{lib}"],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-4000:]
-    assert exe.exists()
+    assert os.path.exists(os.path.join(REPO, "multigridsolver_amd", "libmgs.so")), "libmgs.so not built (run __graft_entry__.build())"
     # usage path (argc != 3) runs without a device: same message and exit code as the reference's main
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
+    r = subprocess.run([EXE], capture_output=True, text=True, timeout=60)
     assert r.returncode == 1 and "Incorrect number of arguments." in r.stdout

@@ -5,7 +5,7 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out/prof_bench
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp; export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py --no-cpu > $OUT/bench.json 2> $OUT/bench.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py --full --no-cpu > $OUT/bench.json 2> $OUT/bench.log
 # the full trace is large (BiCGSTAB etc.): keep the stats table and the fine-level rows of the trace only
 F=$(ls $OUT/trace/*/*_kernel_trace.csv | head -1)
 head -1 $F > $OUT/fine_level_trace.csv

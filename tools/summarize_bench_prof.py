@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""profiles/<tag>_bench_prof.md: rocprofv3 --kernel-trace --stats of `python bench.py --no-cpu` itself — the fine-level
+"""profiles/<tag>_bench_prof.md: rocprofv3 --kernel-trace --stats of `python bench.py --full --no-cpu` itself — the fine-level
 SpMV kernel's average duration in the trace next to the HIP-event figure bench.py printed in the same run."""
 import csv, json, os, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -11,7 +11,7 @@ for r in rows:
     name = r["Kernel_Name"].replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0]
     byk.setdefault(name, []).append(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]))
 with open(os.path.join(REPO, "profiles", f"{tag}_bench_prof.md"), "w") as f:
-    f.write(f"# rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu  ({tag})\n\n")
+    f.write(f"# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu  ({tag})\n\n")
     f.write(f"bench.py line of this run: value {bench['value']:.2f} V-cycles/s, ms_per_step {bench['ms_per_step']:.3f}, "
             f"roofline.achieved {bench['roofline']['achieved']:.0f} GB/s, ms_per_launch (HIP events) {bench['roofline']['ms_per_launch']:.4f}\n\n")
     f.write("Fine-level (512^3) dispatches of the row-block kernels in the trace:\n\n| kernel | launches | avg us | min us | max us |\n|---|---|---|---|---|\n")
