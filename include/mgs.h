@@ -183,6 +183,25 @@ int mgs_hier_coarsen(mgs_hier *h, double ktg, int npass, double tou, int coarse_
  * smoothed by 8 damped-Jacobi sweeps instead.                                          */
 int mgs_hier_finalize(mgs_hier *h);
 int mgs_hier_set_smoother(mgs_hier *h, double omega, int nu1, int nu2);
+/* Operand precision of the cycle (the reference's GPU path keeps its matrices in float32: SURVEY G3,
+ * src/GPU_CUDAC++/MatrixIO.cu:32-36).  Here only the STORED values of the two setup-time operands of the fused zero-guess
+ * V(1,1) passes — Â = A·diag(ωD⁻¹) and A·P — are rounded to FP32 (round to nearest, on the device, from the FP64
+ * operands); vectors, gathers, products, sums, ωD⁻¹, the coarsest solve and the Krylov methods (which always use the
+ * caller's FP64 A) stay FP64.  The cycle is then the FP64 cycle of a slightly different, fixed linear operator.
+ *   bits: 64 (default) or 32; levels: how many leading levels to switch (<0: every eligible one).
+ *   Applied to the longest eligible prefix not longer than `levels`; every other level runs 64 bits after the call
+ *   (bits = 64 switches all levels back: bit-identical to a hierarchy that was never switched).
+ * A level is eligible when its fused branch runs on those operands: aggregation P, square operator, options fuse,
+ * fuse_operands and merge_ap on, rows of A and A·P no longer than 64.  K-cycle levels use the same passes and follow.
+ * Cycles that do not take the fused branch (non-zero guess, ν ≠ 1, additive form, general P) read A itself and stay FP64
+ * whatever was set here; mgs_hier_operand_precision reports 64 for them.  Prepares the operands (first-cycle setup) itself
+ * and drops the cached graphs.  A new ω (mgs_hier_set_smoother) refreshes the FP32 copies together with Â.  The FP64
+ * operands stay allocated beside the copies (+4 B per entry of A and of A·P on a switched level).
+ * MGS_ERR_INVALID: bits not 64/32; before mgs_hier_finalize; option valcode on (coded blocks stream no values, nothing to
+ * shrink); a row-sharded hierarchy (halo columns, halo callbacks, native transport or tail).                          */
+int mgs_hier_set_operand_precision(mgs_hier *h, int bits, int levels);
+/* what level `level` runs with right now: *bits = 64 | 32 */
+int mgs_hier_operand_precision(const mgs_hier *h, int level, int *bits);
 /* K-cycle (docs/AGMG_For_Convection_Diffusion.pdf §3.1, Fortran `nlvcyc`
  * src/CPU_Matlab/dagtwolev_mex.f90:59-61,72): the coarse problems of levels 1..levels are solved
  * by two GCR steps preconditioned by the cycle below instead of one recursive cycle.  0 = V-cycle

@@ -61,6 +61,8 @@ PROTOTYPES = {
     "mgs_ctx_set_native_allreduce": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mgs_csr_optimize": (C.c_int, [C.c_void_p]),
     "mgs_hier_fused_info": (C.c_int, [C.c_void_p, C.c_int, c_i64_p]),
+    "mgs_hier_set_operand_precision": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "mgs_hier_operand_precision": (C.c_int, [C.c_void_p, C.c_int, c_int_p]),
     "mgs_csr_rowcode_info": (C.c_int, [C.c_void_p, c_i64_p]),
     "mgs_hier_graph_info": (C.c_int, [C.c_void_p, c_i64_p]),
     "mgs_hier_group_info": (C.c_int, [C.c_void_p, C.c_int, c_i64_p]),

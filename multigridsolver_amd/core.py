@@ -318,6 +318,15 @@ class Hierarchy:
     def set_smoother(self, omega, nu1, nu2):
         check(lib().mgs_hier_set_smoother(self.h, omega, nu1, nu2), self.ctx.h); return self
 
+    def set_operand_precision(self, bits, levels=-1):
+        """stored precision of the fused passes' matrix operands Â and A·P: 64, or 32 = values rounded to float on the longest eligible
+        prefix of at most `levels` levels (< 0: every eligible one); vectors and arithmetic stay FP64 (mgs.h)"""
+        check(lib().mgs_hier_set_operand_precision(self.h, int(bits), int(levels)), self.ctx.h); return self
+
+    def operand_precision(self, level):
+        """64 or 32: what `level` runs with right now"""
+        bits = C.c_int(); check(lib().mgs_hier_operand_precision(self.h, int(level), C.byref(bits)), self.ctx.h); return bits.value
+
     def set_kcycle(self, levels):
         check(lib().mgs_hier_set_kcycle(self.h, levels), self.ctx.h); return self
 

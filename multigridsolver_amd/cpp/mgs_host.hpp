@@ -168,6 +168,10 @@ class MultiGridPrecond {
   mgs_hier *handle() const { return h_.get(); }
   const DeviceMatrix &matrix() const { return A_; }
   int levels() const { return mgs_hier_nlev(h_.get()); }
+  // stored precision of the cycle's matrix operands (mgs.h: mgs_hier_set_operand_precision; the reference's GPU path keeps its matrices in
+  // float32, src/GPU_CUDAC++/MatrixIO.cu:32-36): bits = 64 | 32, on at most `levels` leading levels (< 0: every eligible one)
+  void set_operand_precision(int bits, int levels = -1) { check(mgs_hier_set_operand_precision(h_.get(), bits, levels), context()); }
+  int operand_precision(int level) const { int bits = 64; check(mgs_hier_operand_precision(h_.get(), level, &bits), context()); return bits; }
  private:
   void build(const DeviceMatrix &A, const SMatrix *P, const Options &o) {
     mgs_hier *h = nullptr;

@@ -140,8 +140,10 @@ __global__ void restrict_agg_kernel(int nc, const int *__restrict__ cptr, const 
 // columns, unfused multiply/add from 0.0: the row-block kernel's arithmetic), stores r for the post pass, and lane 0 adds the members'
 // residuals in ascending member order (restrict_agg_kernel's order): same bits as the two kernels it replaces, one dispatch less per
 // level.  Rows outside every aggregate (G0) get their residual from the tail of the grid.  hv: halo payload of a row shard (NULL: none).
+// VT = float: valhat holds the values rounded to FP32 (operand precision of the level); widened before the product, sums in FP64.
+template <class VT>
 __global__ __launch_bounds__(TB) void agg_pre_kernel(int n, int nc, const int *__restrict__ rowptr, const int *__restrict__ col,
-                                                      const double *__restrict__ valhat, const double *__restrict__ b, const double *__restrict__ hv,
+                                                      const VT *__restrict__ valhat, const double *__restrict__ b, const double *__restrict__ hv,
                                                       const int *__restrict__ cptr, const int *__restrict__ members, const int *__restrict__ agg,
                                                       double *__restrict__ r_out, double *__restrict__ rc_out) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -156,7 +158,7 @@ __global__ __launch_bounds__(TB) void agg_pre_kernel(int n, int nc, const int *_
 #pragma unroll
       for (int q = 0; q < 8; ++q) c[q] = e + q < ee ? col[e + q] : -1;
 #pragma unroll
-      for (int q = 0; q < 8; ++q) v[q] = e + q < ee ? valhat[e + q] : 0.0;
+      for (int q = 0; q < 8; ++q) v[q] = e + q < ee ? (double)valhat[e + q] : 0.0;
 #pragma unroll
       for (int q = 0; q < 8; ++q) xv[q] = c[q] < 0 ? 0.0 : (c[q] < n ? b[c[q]] : hv[c[q] - n]);
 #pragma unroll
@@ -730,11 +732,16 @@ int k_diag_pos(const mgs_csr *A, unsigned char *dpos) {
   MGS_HIP(ctx, hipGetLastError());
   return MGS_OK;
 }
-int k_agg_pre(const mgs_csr *A, const double *valhat, const double *b, const double *hv, const mgs_xfer *T, double *r_out, double *rc_out) {
+int k_agg_pre(const mgs_csr *A, const double *valhat, const double *b, const double *hv, const mgs_xfer *T, double *r_out, double *rc_out,
+              const float *valhat32) {
   mgs_ctx *ctx = A->ctx;
   const int64_t threads = 4 * (int64_t)T->n_coarse + (T->nnz < (int64_t)A->rows ? A->rows : 0);   // rows outside every aggregate only where there are any
-  if (threads) hipLaunchKernelGGL(agg_pre_kernel, dim3(mgs_grid(threads, TB)), dim3(TB), 0, ctx->stream, A->rows, T->n_coarse, A->rowptr, A->col, valhat, b, hv,
-                                  T->cptr, T->members, T->agg, r_out, rc_out);
+  if (threads && valhat32)
+    hipLaunchKernelGGL(agg_pre_kernel<float>, dim3(mgs_grid(threads, TB)), dim3(TB), 0, ctx->stream, A->rows, T->n_coarse, A->rowptr, A->col, valhat32, b, hv,
+                       T->cptr, T->members, T->agg, r_out, rc_out);
+  else if (threads)
+    hipLaunchKernelGGL(agg_pre_kernel<double>, dim3(mgs_grid(threads, TB)), dim3(TB), 0, ctx->stream, A->rows, T->n_coarse, A->rowptr, A->col, valhat, b, hv,
+                       T->cptr, T->members, T->agg, r_out, rc_out);
   MGS_HIP(ctx, hipGetLastError());
   return MGS_OK;
 }
@@ -794,6 +801,16 @@ int k_gather(mgs_ctx *ctx, const double *x, const int *idx, int64_t n, double *o
   return MGS_OK;
 }
 
+// FP32 copy of an operand's values: round to nearest (the conversion instruction's default mode)
+__global__ void round_vals_kernel(const double *__restrict__ in, float *__restrict__ out, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = (float)in[i];
+}
+int k_round_vals(mgs_ctx *ctx, const double *in, float *out, int64_t n) {
+  if (n) hipLaunchKernelGGL(round_vals_kernel, dim3(mgs_grid(n, TB)), dim3(TB), 0, ctx->stream, in, out, n);
+  MGS_HIP(ctx, hipGetLastError());
+  return MGS_OK;
+}
 int k_scale_vals(mgs_ctx *ctx, const mgs_csr *A, const double *wd, double *out) {
   if (A->rows) hipLaunchKernelGGL(scale_vals_kernel, dim3(mgs_grid(A->rows, TB)), dim3(TB), 0, ctx->stream, A->rows, A->rowptr, A->col, A->val, wd, out);
   MGS_HIP(ctx, hipGetLastError());

@@ -50,14 +50,17 @@ __device__ __forceinline__ void st_stream(double *p, double v, bool nt) {
 // keep alive or spill): piece p = 64 pairs = 1 KiB, wave w takes pieces w, w + 4, w + 8, w + 12; lane l of a piece moves pair 64p + l.
 // Covers up to 1024 pairs (2048 doubles); the caller checks that.  The caller waits for its own transfers (s_waitcnt vmcnt(0), explicit)
 // before the workgroup barrier that publishes the slice.
-__device__ __forceinline__ void stage_pairs_dma(const double *__restrict__ src, double *lds, int npairs, int tid) {
+// VT = float (FP32 operand values): the same 16-byte transfers carry four floats each; `npairs` counts 16-byte pieces either way.
+template <class VT>
+__device__ __forceinline__ void stage_pairs_dma(const VT *__restrict__ src, VT *lds, int npairs, int tid) {
+  constexpr int PER = 16 / (int)sizeof(VT);
   const int wave = tid >> 6, lane = tid & 63;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const int p = wave + 4 * k;
     if (p * 64 + lane < npairs)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + 2 * (p * 64 + lane)),
-                                       (__attribute__((address_space(3))) void *)(lds + 128 * p), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + PER * (p * 64 + lane)),
+                                       (__attribute__((address_space(3))) void *)(lds + 64 * PER * p), 16, 0, 0);
   }
 }
 
@@ -74,6 +77,15 @@ __device__ __forceinline__ void epilogue(int row, double s, const double *__rest
 typedef int int4_t __attribute__((ext_vector_type(4)));
 typedef int int2_t __attribute__((ext_vector_type(2)));
 typedef double double2_t __attribute__((ext_vector_type(2)));
+typedef float float4_t __attribute__((ext_vector_type(4)));
+// Value type of a matrix operand of the fused cycle passes (mgs_hier_set_operand_precision): double, or float for operands whose STORED
+// values were rounded to FP32 at setup.  Only storage changes: a float value is widened before its product, every sum stays FP64 in the
+// same order.  A 16-byte load carries VA values; the staged slice starts at an entry index that is a multiple of VA.
+template <class VT> struct val_traits;
+template <> struct val_traits<double> { typedef double2_t v16; typedef int2_t i16; static constexpr int VA = 2; };
+template <> struct val_traits<float> { typedef float4_t v16; typedef int4_t i16; static constexpr int VA = 4; };
+// doubles of LDS the value region of a row block takes: capv values + what the alignment of the slice's two ends adds
+template <class VT> __host__ __device__ __forceinline__ int val_region(int capv) { return sizeof(VT) == 4 ? (capv + 8) >> 1 : capv + 2; }
 
 // Workgroup → row-block map.  (1) XCD-contiguous: workgroups are dealt round-robin over the 8
 // XCDs, so XCD x = bid & 7 sweeps the x-th eighth of the row blocks.  (2) Optional strip-major
@@ -407,9 +419,9 @@ __device__ __forceinline__ void coded_row_range(const int *__restrict__ ints, in
 // VAL: the tuples carry the values as well (`vtab`, option valcode): a coded block then streams no matrix entry at all.
 // one 256-row block of the pattern-coded kernel (the two __global__ wrappers below call it once per workgroup, or once per row block
 // of a group of blocks)
-template <int OP, int U, bool HALO, bool VAL>
+template <int OP, int U, bool HALO, bool VAL, class VT = double>
 __device__ __forceinline__ void coded_block_body(
-    const int blk, int n, const int *__restrict__ rowptr, const int *__restrict__ idx, const double *__restrict__ val,
+    const int blk, int n, const int *__restrict__ rowptr, const int *__restrict__ idx, const VT *__restrict__ val,
     const unsigned char *__restrict__ pid, const int *__restrict__ tptr, const int *__restrict__ tab,
     const double *__restrict__ x /*gather source: x, or e_c for the post pass*/, const double *__restrict__ b /*b, or r for the post pass*/,
     const double *__restrict__ dinv /*dinv, or wd for the post pass*/, double omega, const double *__restrict__ xin /*post pass: b*/,
@@ -420,19 +432,25 @@ __device__ __forceinline__ void coded_block_body(
     int dot_nb, int flags /*kernel-uniform; bit 0: no row is longer than U → the gather step runs once, without a loop; bit 1: loop-free staging (option stage_unroll); bit 2: option rowptr_scan*/) {
   extern __shared__ double lds_raw[];
   constexpr bool POST = OP == FUSE_POST_MAPPED;
+  constexpr bool F32 = sizeof(VT) == 4;      // FP32 operand values: no value tuples, no fused dots, ωD⁻¹ from wd; the code may be absent (tptr = NULL)
+  constexpr int VA = val_traits<VT>::VA;
+  typedef typename val_traits<VT>::v16 v16_t;
+  typedef typename val_traits<VT>::i16 i16_t;
+  static_assert(!F32 || (!VAL && !HALO && (OP == MGS_OP_RESIDUAL || POST)), "float values: pre and post pass of an unsharded level only");
   const int r0 = blk * RB;
   const int r1 = min(r0 + RB, n);
   const int tid = threadIdx.x;
   const int lo = blkptr[blk], hi = blkptr[blk + 1];
-  const int t0 = tptr[blk], tlen = tptr[blk + 1] - t0;
+  int t0 = 0, tlen = 0;
+  if (!F32 || tptr) { t0 = tptr[blk]; tlen = tptr[blk + 1] - t0; }
   const int capi_abs = capi < 0 ? -capi : capi;
-  double *__restrict__ vals = lds_raw;                                    // capv + 2 doubles
-  int *__restrict__ ints = reinterpret_cast<int *>(lds_raw + capv + 2);   // capi ints: the block's table, or its index slice
+  VT *__restrict__ vals = reinterpret_cast<VT *>(lds_raw);                                // capv + 2 doubles (capv + 8 floats)
+  int *__restrict__ ints = reinterpret_cast<int *>(lds_raw + val_region<VT>(capv));       // capi ints: the block's table, or its index slice
   const int row = r0 + tid;
-  const int start = lo & ~1;
+  const int start = lo & ~(VA - 1);
   const int nent = hi - start;
   const bool coded = tlen > 0 && tlen <= capi_abs && (!VAL || tlen <= capv);
-  const bool staged = hi - lo <= capv && (coded || nent + 1 <= capi_abs);     // block-uniform
+  const bool staged = hi - lo <= capv && (coded || nent + VA - 1 <= capi_abs);     // block-uniform
   int ga = 0, ge = 0, base = row;
   double bi = 0.0, di = 0.0, xi = 0.0, pei = 0.0;
   const bool dmode = POST && dpos != nullptr && xin == nullptr;    // ωD⁻¹ from the streamed diagonal entry (same bits as wd = ω·(1/a_ii))
@@ -465,7 +483,7 @@ __device__ __forceinline__ void coded_block_body(
   };
   double s = 0.0;
   if (staged) {
-    const int nch = (nent + 1) >> 1;
+    const int nch = (nent + VA - 1) >> (VA == 4 ? 2 : 1);      // 16-byte pieces of the value slice
     if (coded) {
       if (VAL) { for (int c = tid; c < tlen; c += RB) vals[c] = vtab[t0 + c]; }     // value tuples instead of the value slice (tlen <= capv)
       else if (nch <= 4 * RB && (flags & 2)) {
@@ -473,27 +491,27 @@ __device__ __forceinline__ void coded_block_body(
         // loads.  A loop here makes the compiler drain every outstanding load at its header (s_waitcnt vmcnt(0) in the ISA: wait counts
         // across a back edge are not tracked), i.e. a workgroup paid one full memory latency for rowptr/b/agg/… and a second one for
         // its value slice.
-        double2_t rr[4];
+        v16_t rr[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) { const int c = tid + k * RB; if (c < nch) rr[k] = *reinterpret_cast<const double2_t *>(val + start + 2 * c); }
+        for (int k = 0; k < 4; ++k) { const int c = tid + k * RB; if (c < nch) rr[k] = *reinterpret_cast<const v16_t *>(val + start + VA * c); }
         int tw = 0;
         if (tid < tlen) tw = tab[t0 + tid];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) { const int c = tid + k * RB; if (c < nch) *reinterpret_cast<double2_t *>(vals + 2 * c) = rr[k]; }
+        for (int k = 0; k < 4; ++k) { const int c = tid + k * RB; if (c < nch) *reinterpret_cast<v16_t *>(vals + VA * c) = rr[k]; }
         if (tid < tlen) ints[tid] = tw;
         for (int c = tid + RB; c < tlen; c += RB) ints[c] = tab[t0 + c];
       } else {
 #pragma unroll 4
-        for (int c = tid; c < nch; c += RB) *reinterpret_cast<double2_t *>(vals + 2 * c) = *reinterpret_cast<const double2_t *>(val + start + 2 * c);
+        for (int c = tid; c < nch; c += RB) *reinterpret_cast<v16_t *>(vals + VA * c) = *reinterpret_cast<const v16_t *>(val + start + VA * c);
         for (int c = tid; c < tlen; c += RB) ints[c] = tab[t0 + c];
       }
       if (VAL) for (int c = tid; c < tlen; c += RB) ints[c] = tab[t0 + c];
     } else {
 #pragma unroll 4
       for (int c = tid; c < nch; c += RB) {
-        const int k = start + 2 * c;
-        *reinterpret_cast<int2_t *>(ints + 2 * c) = *reinterpret_cast<const int2_t *>(idx + k);
-        *reinterpret_cast<double2_t *>(vals + 2 * c) = *reinterpret_cast<const double2_t *>(val + k);
+        const int k = start + VA * c;
+        *reinterpret_cast<i16_t *>(ints + VA * c) = *reinterpret_cast<const i16_t *>(idx + k);
+        *reinterpret_cast<v16_t *>(vals + VA * c) = *reinterpret_cast<const v16_t *>(val + k);
       }
     }
     __syncthreads();
@@ -551,7 +569,7 @@ __device__ __forceinline__ void coded_block_body(
     late_loads();
     for (int k = ga; k < ge; ++k) {
       const int c = idx[k];
-      s += val[k] * ((HALO && c >= split) ? hv[c - split] : ((POST && c < 0) ? 0.0 : x[c]));
+      s += (double)val[k] * ((HALO && c >= split) ? hv[c - split] : ((POST && c < 0) ? 0.0 : x[c]));
     }
     if (POST && dmode && dp != 255) di = omega * (1.0 / val[ga + (int)dp]);
   }
@@ -568,18 +586,18 @@ __device__ __forceinline__ void coded_block_body(
     double p1 = row < r1 ? bi : 0.0, p2 = row < r1 ? di : 0.0;
     for (int off = 32; off > 0; off >>= 1) { p1 += __shfl_down(p1, off); p2 += __shfl_down(p2, off); }
     __syncthreads();                                   // the staged values are done with: their LDS holds the 4 wave sums
-    if ((tid & 63) == 0) { vals[2 * (tid >> 6)] = p1; vals[2 * (tid >> 6) + 1] = p2; }
+    if ((tid & 63) == 0) { lds_raw[2 * (tid >> 6)] = p1; lds_raw[2 * (tid >> 6) + 1] = p2; }
     __syncthreads();
     if (tid == 0) {
       double t1 = 0.0, t2 = 0.0;
-      for (int q = 0; q < RB / 64; ++q) { t1 += vals[2 * q]; t2 += vals[2 * q + 1]; }
+      for (int q = 0; q < RB / 64; ++q) { t1 += lds_raw[2 * q]; t2 += lds_raw[2 * q + 1]; }
       dot_part[blk] = t1; dot_part[dot_nb + blk] = t2;
     }
   }
 }
 
 #define CODED_PARAMS                                                                                                                    \
-    int n, const int *__restrict__ rowptr, const int *__restrict__ idx, const double *__restrict__ val,                                  \
+    int n, const int *__restrict__ rowptr, const int *__restrict__ idx, const VT *__restrict__ val,                                      \
     const unsigned char *__restrict__ pid, const int *__restrict__ tptr, const int *__restrict__ tab, const double *__restrict__ x,      \
     const double *__restrict__ b, const double *__restrict__ dinv, double omega, const double *__restrict__ xin,                         \
     const int *__restrict__ agg, double *__restrict__ out, int capv, int capi, BlockMap bm, const int *__restrict__ blkptr,               \
@@ -589,15 +607,15 @@ __device__ __forceinline__ void coded_block_body(
 
 // (round 1: the post pass took 68 VGPRs unbounded = 7 waves per SIMD, bounded to 8 waves it measured 2 % faster, the other ops 0.5–0.8 % slower;
 // since its prologue was rewritten it needs 52–56, the other ops 58–64, and the bound no longer binds)
-template <int OP, int U, bool HALO, bool VAL>
+template <int OP, int U, bool HALO, bool VAL, class VT = double>
 __global__ __launch_bounds__(RB, OP == FUSE_POST_MAPPED ? 8 : 1) void csr_rowblock_coded_kernel(CODED_PARAMS) {
   const int vb = map_block(bm, blockIdx.x);
   if (vb < 0) return;
-  coded_block_body<OP, U, HALO, VAL>(block_of(bm, vb), CODED_ARGS);
+  coded_block_body<OP, U, HALO, VAL, VT>(block_of(bm, vb), CODED_ARGS);
 }
 // the same row blocks swept group by group (descriptors of the grouped pre pass: up to GRP_BLOCKS blocks per workgroup, one after the
 // other) — experiment: does the post pass gain what the grouped pre pass gains from fewer, fatter workgroups?
-template <int OP, int U, bool HALO, bool VAL>
+template <int OP, int U, bool HALO, bool VAL, class VT = double>
 __global__ __launch_bounds__(RB, OP == FUSE_POST_MAPPED ? 8 : 1) void csr_rowblock_coded_group_kernel(CODED_PARAMS, const int *__restrict__ gdesc) {
   const int g = map_block(bm, blockIdx.x);
   if (g < 0) return;
@@ -910,15 +928,19 @@ __global__ void restrict_stray_kernel(int ns, const int *__restrict__ stray, con
 // unstaged walk — block-uniform choices), then the in-LDS restriction of the group's aggregates
 // (six waves per SIMD: the halo variants of U = 7 / 8 came out at 82 / 89 registers — one wave less than the 80 of the others — and ran 6 % behind
 // their share on a row shard)
-template <int U, bool HALO>
+template <int U, bool HALO, class VT = double>
 __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(6))) void csr_group_pre_kernel(
-    int n, const int *__restrict__ rowptr, const int *__restrict__ idx, const double *__restrict__ val,
+    int n, const int *__restrict__ rowptr, const int *__restrict__ idx, const VT *__restrict__ val,
     const unsigned char *__restrict__ pid, const int *__restrict__ tptr, const int *__restrict__ tab,
     const double *__restrict__ x, const double *__restrict__ b, double *__restrict__ t_out, double *__restrict__ r_out,
     double *__restrict__ rc_out, const int *__restrict__ gdesc, const unsigned long long *__restrict__ acode,
     const unsigned *__restrict__ wmask, int capv, int capi, BlockMap bm, const double *__restrict__ hv, int split, int nts /*bit 0: streaming store of t; bit 1: slice staged by LDS-DMA, no loop; bit 2: option rowptr_scan*/,
     const int *__restrict__ gorder, int gper) {
   extern __shared__ double lds_raw[];
+  constexpr int VA = val_traits<VT>::VA;
+  typedef typename val_traits<VT>::v16 v16_t;
+  typedef typename val_traits<VT>::i16 i16_t;
+  static_assert(sizeof(VT) == 8 || !HALO, "float values: unsharded levels only");
   int g;
   if (gorder) {        // option group_order: workgroup (xcd, idx) → group, in the order of the one-block kernels' plane sweep
     const int idx = blockIdx.x >> 3;
@@ -927,9 +949,9 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(6))) void cs
   } else g = map_block(bm, blockIdx.x);
   if (g < 0) return;
   const int tid = threadIdx.x;
-  double *__restrict__ vals = lds_raw;                                    // capv + 2 doubles
-  int *__restrict__ ints = reinterpret_cast<int *>(lds_raw + capv + 2);   // capi ints: the block's table, or its index slice
-  double *__restrict__ rbuf = lds_raw + capv + 2 + (capi + 1) / 2;        // residuals of the group's row blocks
+  VT *__restrict__ vals = reinterpret_cast<VT *>(lds_raw);                                // capv + 2 doubles (capv + 8 floats)
+  int *__restrict__ ints = reinterpret_cast<int *>(lds_raw + val_region<VT>(capv));       // capi ints: the block's table, or its index slice
+  double *__restrict__ rbuf = lds_raw + val_region<VT>(capv) + (capi + 1) / 2;            // residuals of the group's row blocks
   // group descriptor (one 128-byte record, no dependent loads behind it): blocks, their entry bounds, their aggregate ranges
   const int4_t *__restrict__ gd = reinterpret_cast<const int4_t *>(gdesc + (size_t)GRP_DESC * g);
   const int4_t gb = gd[0], glo = gd[1], ghi = gd[2], galo = gd[3], gahi = gd[4];
@@ -946,9 +968,9 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(6))) void cs
     const int r0 = blk * RB, r1 = min(r0 + RB, n);
     const int lo = GSEL(glo, h), hi = GSEL(ghi, h);
     const int t0 = tptr ? tptr[blk] : 0, tlen = tptr ? tptr[blk + 1] - t0 : 0;
-    const int row = r0 + tid, start = lo & ~1, nent = hi - start;
+    const int row = r0 + tid, start = lo & ~(VA - 1), nent = hi - start;
     const bool coded = tlen > 0 && tlen <= capi;
-    const bool staged = hi - lo <= capv && (coded || nent + 1 <= capi);   // block-uniform
+    const bool staged = hi - lo <= capv && (coded || nent + VA - 1 <= capi);   // block-uniform
     int ga = 0, ge = 0;
     double bi = 0.0;
     unsigned wm = 0u;
@@ -959,7 +981,7 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(6))) void cs
     if (row < r1) { if (!scan) { ga = rowptr[row]; ge = rowptr[row + 1]; } bi = b[row]; wm = wmask[row >> 5]; if (coded) mypid = pid[row]; }
     double s = 0.0;
     if (staged) {
-      const int nch = (nent + 1) >> 1;
+      const int nch = (nent + VA - 1) >> (VA == 4 ? 2 : 1);      // 16-byte pieces of the value slice
       if (coded && nch <= 4 * RB && (nts & 2)) {          // no loop and no staging registers in front of the barrier (see coded_block_body)
         stage_pairs_dma(val + start, vals, nch, tid);
         int tw = 0;
@@ -971,14 +993,14 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(6))) void cs
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       } else if (coded) {
 #pragma unroll 4
-        for (int c = tid; c < nch; c += RB) *reinterpret_cast<double2_t *>(vals + 2 * c) = *reinterpret_cast<const double2_t *>(val + start + 2 * c);
+        for (int c = tid; c < nch; c += RB) *reinterpret_cast<v16_t *>(vals + VA * c) = *reinterpret_cast<const v16_t *>(val + start + VA * c);
         for (int c = tid; c < tlen; c += RB) ints[c] = tab[t0 + c];
       } else {
 #pragma unroll 4
         for (int c = tid; c < nch; c += RB) {
-          const int k = start + 2 * c;
-          *reinterpret_cast<int2_t *>(ints + 2 * c) = *reinterpret_cast<const int2_t *>(idx + k);
-          *reinterpret_cast<double2_t *>(vals + 2 * c) = *reinterpret_cast<const double2_t *>(val + k);
+          const int k = start + VA * c;
+          *reinterpret_cast<i16_t *>(ints + VA * c) = *reinterpret_cast<const i16_t *>(idx + k);
+          *reinterpret_cast<v16_t *>(vals + VA * c) = *reinterpret_cast<const v16_t *>(val + k);
         }
       }
       __syncthreads();
@@ -1017,7 +1039,7 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(6))) void cs
         }
       }
     } else if (row < r1) {
-      for (int k = ga; k < ge; ++k) { const int c = idx[k]; s += val[k] * ((HALO && c >= split) ? hv[c - split] : x[c]); }
+      for (int k = ga; k < ge; ++k) { const int c = idx[k]; s += (double)val[k] * ((HALO && c >= split) ? hv[c - split] : x[c]); }
     }
     // members of stray aggregates also store r — the whole wave does when one of its rows must: 64 consecutive doubles are four full
     // cache lines, while lone 8-byte stores each cost a read-modify-write of an ECC word in HBM.  The vote is taken BEFORE the stores:
@@ -1390,6 +1412,38 @@ static bool use_rowcode(const mgs_csr *A, const mgs_rowcode *c, bool any = false
   return c && A->ctx->opt_rowcode && A->blkptr && A->lds_cap > 0 && A->max_row_len <= 64 &&
          (any || (double)c->coded_blocks >= 0.5 * c->nblocks);
 }
+// LDS sizing of the float forms: capv a multiple of 4 (the integer region behind the values stays 16-byte aligned for the int4 stores of
+// the uncoded blocks), whose index slice may reach capv + 6 entries (both ends of the slice aligned to 4)
+static inline int capv_f32(const mgs_csr *A) { return (A->lds_cap + 3) & ~3; }
+static inline int capi_f32(const mgs_rowcode *c, int capv) {
+  const bool lean = c && (double)c->coded_blocks >= 0.985 * c->nblocks;
+  return lean ? std::max(c->tab_cap, 64) : std::max(c ? c->tab_cap : 0, capv + 8);
+}
+// The pre pass (RESIDUAL on Â) and the post pass (FUSE_POST_MAPPED on A·P) of an FP32 level: the same coded kernel instantiated for float
+// values (A->val32).  Serves any unsharded operator with short rows — c may be NULL or code only a few blocks: the uncoded blocks stage
+// their index slice — so a level switched to FP32 never falls back to a kernel that reads the FP64 values.
+static int launch_coded_f32(const mgs_csr *A, const mgs_rowcode *c, int op, const int *idx, const double *x, const double *b, const double *dinv,
+                            const double *xin, const int *agg, double *out, dim3 grid, BlockMap bm) {
+  mgs_ctx *ctx = A->ctx;
+  if (op != MGS_OP_RESIDUAL && op != FUSE_POST_MAPPED) return mgs_fail(ctx, MGS_ERR_INVALID, "FP32 operand values: op %d has no float form", op);
+  if (c && c->vtab) c = nullptr;      // value tuples are FP64: not this path (the setter refuses option valcode)
+  const int capv = capv_f32(A), capi = capi_f32(c, capv);
+  const size_t lds = (size_t)val_region<float>(capv) * 8 + (size_t)capi * 4 + 16 + (size_t)ctx->opt_lds_pad;
+  const double mean_len = A->rows ? (double)A->nnz / A->rows : 1.0;
+  const int u = mean_len <= 4.5 ? 4 : (mean_len <= 7.5 && A->max_row_len <= 14 ? 7 : 8);
+#define F_(O, UU) hipLaunchKernelGGL((csr_rowblock_coded_kernel<O, UU, false, false, float>), grid, dim3(RB), lds, ctx->stream, A->rows, A->rowptr, idx, A->val32, \
+                                     c ? c->pid : nullptr, c ? c->tptr : nullptr, c ? c->tab : nullptr, x, b, dinv, 0.0, xin, agg, out, capv, \
+                                     (ctx->opt_nt_store > 0 && A->rows >= ctx->opt_nt_store) ? -capi : capi, bm, A->blkptr, nullptr, 0x7fffffff, nullptr, nullptr, \
+                                     nullptr, nullptr, (A->rows + RB - 1) / RB, (A->max_row_len <= UU ? 1 : 0) | (ctx->opt_stage_unroll ? 2 : 0) | (ctx->opt_rowptr_scan ? 4 : 0))
+#define FU_(O) do { if (u == 4) F_(O, 4); else if (u == 7) F_(O, 7); else F_(O, 8); } while (0)
+  if (op == MGS_OP_RESIDUAL) FU_(MGS_OP_RESIDUAL);
+  else if (mean_len > 4.5 && mean_len <= 5.5 && A->max_row_len <= 10) F_(FUSE_POST_MAPPED, 5);
+  else FU_(FUSE_POST_MAPPED);
+#undef FU_
+#undef F_
+  MGS_HIP(ctx, hipGetLastError());
+  return MGS_OK;
+}
 // op ∈ {SPMV, RESIDUAL, JACOBI, FUSE_POST_MAPPED}; for the post pass: x = e_c, b = r, dinv = wd, xin = b, idx = agg[col]
 static dim3 plan_group_map(const mgs_csr *A, const mgs_groups *G, BlockMap &bm);
 static int launch_coded(const mgs_csr *A, const mgs_rowcode *c, int op, const int *idx, const double *x, const double *b, const double *dinv,
@@ -1624,15 +1678,17 @@ int mgs_launch_group_pre(const mgs_csr *A, const mgs_groups *G, const mgs_xfer *
   mgs_ctx *ctx = A->ctx;
   if (A->rows == 0 || G->ngroups == 0) return MGS_OK;
   const mgs_rowcode *c = (use_rowcode(A, A->code, hv != nullptr) && !A->code->vtab) ? A->code : nullptr;
-  const int capv = A->lds_cap;
+  const bool f32 = A->val32 != nullptr;      // FP32 level: the float form (unsharded levels only, the caller sees to that)
+  if (f32 && hv) return mgs_fail(ctx, MGS_ERR_INVALID, "grouped pre pass: FP32 operand values on a row shard");
+  const int capv = f32 ? capv_f32(A) : A->lds_cap;
   const bool lean = c && (double)c->coded_blocks >= 0.985 * c->nblocks;
-  const int capi = lean ? std::max(c->tab_cap, 64) : std::max(c ? c->tab_cap : 0, capv + 2);
-  const size_t lds = (size_t)(capv + 2) * 8 + (size_t)((capi + 1) / 2) * 8 + (size_t)G->max_blocks * RB * 8 + 16 + (size_t)ctx->opt_lds_pad;
+  const int capi = f32 ? capi_f32(c, capv) : (lean ? std::max(c->tab_cap, 64) : std::max(c ? c->tab_cap : 0, capv + 2));
+  const size_t lds = (size_t)(f32 ? val_region<float>(capv) : capv + 2) * 8 + (size_t)((capi + 1) / 2) * 8 + (size_t)G->max_blocks * RB * 8 + 16 + (size_t)ctx->opt_lds_pad;
   BlockMap bm;
   dim3 grid = plan_group_map(A, G, bm);
   const double mean_len = A->rows ? (double)A->nnz / A->rows : 1.0;
   const int u = mean_len <= 4.5 ? 4 : (mean_len <= 7.5 && A->max_row_len <= 14 ? 7 : 8);
-  const bool pairs = G->max_blocks <= 2 && ctx->opt_group_concurrent;     // 512 threads, both blocks of a pair at once
+  const bool pairs = G->max_blocks <= 2 && ctx->opt_group_concurrent && !f32;     // 512 threads, both blocks of a pair at once (FP64 values only)
   const bool ordered = !pairs && G->gorder && ctx->opt_group_order > 0 && ctx->opt_xcd_remap;
   if (ordered) grid = dim3(8 * G->gorder_per_xcd);
   const size_t lds2 = (size_t)2 * ((size_t)(capv + 2) * 8 + (size_t)((capi + 1) / 2) * 8) + (size_t)2 * RB * 8 + 16 + (size_t)ctx->opt_lds_pad;
@@ -1643,9 +1699,14 @@ int mgs_launch_group_pre(const mgs_csr *A, const mgs_groups *G, const mgs_xfer *
                                      c ? c->pid : nullptr, c ? c->tptr : nullptr, c ? c->tab : nullptr, x, b, t_out, r_out, rc_out, G->gdesc, \
                                      G->acode, G->wmask, capv, capi, bm, hv, hv ? split : 0x7fffffff, ((ctx->opt_nt_store > 0 && A->rows >= ctx->opt_nt_store) ? 1 : 0) | (ctx->opt_stage_unroll ? 2 : 0) | (ctx->opt_rowptr_scan ? 4 : 0), \
                                      ordered ? G->gorder : nullptr, G->gorder_per_xcd)
-#define GU_(UU) do { if (pairs) { if (hv) G2_(UU, true); else G2_(UU, false); } else { if (hv) G_(UU, true); else G_(UU, false); } } while (0)
+#define GF_(UU) hipLaunchKernelGGL((csr_group_pre_kernel<UU, false, float>), grid, dim3(RB), lds, ctx->stream, A->rows, A->rowptr, A->col, A->val32, \
+                                   c ? c->pid : nullptr, c ? c->tptr : nullptr, c ? c->tab : nullptr, x, b, t_out, r_out, rc_out, G->gdesc, \
+                                   G->acode, G->wmask, capv, capi, bm, nullptr, 0x7fffffff, ((ctx->opt_nt_store > 0 && A->rows >= ctx->opt_nt_store) ? 1 : 0) | (ctx->opt_stage_unroll ? 2 : 0) | (ctx->opt_rowptr_scan ? 4 : 0), \
+                                   ordered ? G->gorder : nullptr, G->gorder_per_xcd)
+#define GU_(UU) do { if (f32) GF_(UU); else if (pairs) { if (hv) G2_(UU, true); else G2_(UU, false); } else { if (hv) G_(UU, true); else G_(UU, false); } } while (0)
   if (u == 4) GU_(4); else if (u == 7) GU_(7); else GU_(8);
 #undef GU_
+#undef GF_
 #undef G_
 #undef G2_
   MGS_HIP(ctx, hipGetLastError());
@@ -1735,6 +1796,10 @@ int mgs_launch_fused_range(const mgs_csr *A, int which, const double *wd, const 
   dim3 grid(bm.remap ? per_xcd * 8 : bm.nblocks);
   const int cap = A->lds_cap;
   const size_t lds = (size_t)(cap + 2) * 12 + 16;
+  if (A->val32) {      // FP32 level: post pass on the float copy of A·P's values (never the gather kernels, which read FP64 values)
+    if (which != FUSE_POST_MAPPED || hv) return mgs_fail(ctx, MGS_ERR_INVALID, "FP32 operand values: fused pass %d has no float form", which);
+    return launch_coded_f32(A, A->code, FUSE_POST_MAPPED, A->col, ec, bvec, wd, xin, agg, out, grid, bm);
+  }
   if (which == FUSE_POST_MAPPED && use_rowcode(A, A->code))      // A is the view whose col/code are the aggregate-mapped ones
     return launch_coded(A, A->code, FUSE_POST_MAPPED, A->col, ec, bvec, wd, 0.0, xin, agg, out, grid, bm);
   if (which == FUSE_POST_MAPPED) hipLaunchKernelGGL((csr_rowblock_fused_kernel<FUSE_POST_MAPPED>), grid, dim3(RB), lds, ctx->stream, A->rows, A->rowptr, A->col, A->val, wd, bvec, xin, agg, ec, out, out2, cap, bm, hv, A->ctx->opt_blkptr ? A->blkptr : nullptr);
@@ -1768,6 +1833,10 @@ int mgs_launch_csr_op_range(const mgs_csr *A, int op, const double *x, const dou
     if (D >= 512 && bm.chunk >= 2 * D) {
       per_xcd = strip_map(bm, D, ctx->opt_strip > 0 ? ctx->opt_strip : 64);
     }
+  }
+  if (A->val32) {      // FP32 level: pre pass on the float copy of Â's values, whatever the SpMV variant options say
+    const dim3 grid32(bm.remap ? per_xcd * 8 : bm.nblocks);
+    return launch_coded_f32(A, A->code, op, A->col, x, b, dinv, nullptr, nullptr, out, grid32, bm);
   }
   int cap = ctx->opt_spmv_variant == 1 ? -1 : A->lds_cap;
   if (ctx->opt_spmv_variant == 6 && A->max_block_nnz <= 2048 && A->max_block_nnz == A->lds_cap) {

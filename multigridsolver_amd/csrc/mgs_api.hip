@@ -528,6 +528,8 @@ static void level_free(mgs_level &L) {
   mgs_vec_destroy(L.dinv); mgs_vec_destroy(L.r); mgs_vec_destroy(L.tmp); mgs_vec_destroy(L.b); mgs_vec_destroy(L.x); mgs_vec_destroy(L.wd);
   mgs_vec_destroy(L.hbuf);
   if (L.val_wd) mgs_hip_free(L.val_wd);
+  if (L.val_wd32) mgs_hip_free(L.val_wd32);
+  if (L.ap_val32) mgs_hip_free(L.ap_val32);
   if (L.col_agg) mgs_hip_free(L.col_agg);
   if (L.cmap_ext) mgs_hip_free(L.cmap_ext);
   mgs_free_rowcode(L.code_agg);
@@ -545,6 +547,36 @@ static void level_free(mgs_level &L) {
 static void drop_graph(mgs_hier *h) {
   for (auto &g : h->graphs) { if (g.exec) hipGraphExecDestroy(g.exec); g = mgs_hier::GraphSlot(); }
   if (h->coarse_exec) { hipGraphExecDestroy(h->coarse_exec); h->coarse_exec = nullptr; }
+}
+static int prepare_fused(mgs_hier *h);
+// ---- operand precision (mgs_hier_set_operand_precision) ----
+// A level can run its two fused passes on FP32 copies of Â's and A·P's values when both operands exist, the level is square (no halo
+// columns) and both have short rows — then the float forms of the coded / grouped / aggregate-parallel kernels serve every row block.
+static bool level_f32_eligible(const mgs_hier *h, int l) {
+  if (l < 0 || l + 1 >= (int)h->lev.size()) return false;
+  const mgs_level &L = h->lev[l];
+  const mgs_ctx *ctx = h->ctx;
+  return ctx->opt_fuse && ctx->opt_fuse_operands && ctx->opt_merge_ap && !ctx->opt_valcode && L.T && L.T->aggregation && L.A->rows == L.A->cols &&
+         L.val_wd && L.AP && L.A->blkptr && L.AP->blkptr && L.A->lds_cap > 0 && L.AP->lds_cap > 0 && L.A->max_row_len <= 64 && L.AP->max_row_len <= 64;
+}
+// ... and does so in the cycle the hierarchy would run NOW: only the fused zero-guess V(1,1) branch reads the operands at all
+static bool level_runs_f32(const mgs_hier *h, int l) {
+  if (l < 0 || l >= (int)h->lev.size()) return false;
+  const mgs_level &L = h->lev[l];
+  return L.op_bits == 32 && L.val_wd32 && L.ap_val32 && h->nu1 == 1 && h->nu2 == 1 && !h->additive && level_f32_eligible(h, l);
+}
+// (re)builds the FP32 copies of a level switched to 32 bits from the FP64 operands; vals_changed: Â was rescaled (new ω)
+static int level_refresh_f32(mgs_hier *h, mgs_level &L, bool vals_changed) {
+  mgs_ctx *ctx = h->ctx;
+  if (L.op_bits != 32 || !L.val_wd || !L.AP) return MGS_OK;
+  if (!L.val_wd32) { MGS_TRY(mgs_dev_alloc(ctx, &L.val_wd32, (size_t)L.A->nnz + 8)); vals_changed = true; drop_graph(h); }
+  if (vals_changed) MGS_TRY(k_round_vals(ctx, L.val_wd, L.val_wd32, L.A->nnz));
+  if (!L.ap_val32) {
+    MGS_TRY(mgs_dev_alloc(ctx, &L.ap_val32, (size_t)L.AP->nnz + 8));
+    MGS_TRY(k_round_vals(ctx, L.AP->val, L.ap_val32, L.AP->nnz));
+    drop_graph(h);
+  }
+  return MGS_OK;
 }
 
 extern "C" {
@@ -582,6 +614,40 @@ int mgs_hier_destroy(mgs_hier *h) {
 int mgs_hier_set_smoother(mgs_hier *h, double omega, int nu1, int nu2) {
   MGS_CHECK(h->ctx, nu1 >= 0 && nu2 >= 0, MGS_ERR_INVALID, "negative sweep count");
   h->omega = omega; h->nu1 = nu1; h->nu2 = nu2; drop_graph(h);
+  return MGS_OK;
+}
+int mgs_hier_set_operand_precision(mgs_hier *h, int bits, int levels) {
+  MGS_CHECK(nullptr, h, MGS_ERR_INVALID, "mgs_hier_set_operand_precision: NULL hierarchy");
+  mgs_ctx *ctx = h->ctx;
+  MGS_CHECK(ctx, bits == 64 || bits == 32, MGS_ERR_INVALID, "mgs_hier_set_operand_precision: bits must be 64 or 32 (got %d)", bits);
+  MGS_CHECK(ctx, h->finalized, MGS_ERR_INVALID, "mgs_hier_set_operand_precision: call mgs_hier_finalize first");
+  if (bits == 32) {
+    MGS_CHECK(ctx, !ctx->opt_valcode, MGS_ERR_INVALID, "mgs_hier_set_operand_precision: option valcode is on (coded blocks stream no values: nothing to shrink)");
+    bool shard = h->halo || h->halo_begin || h->halo_fused || h->native || h->ntail || h->coarse;
+    for (auto &L : h->lev) shard = shard || L.A->cols > L.A->rows || L.nx;
+    MGS_CHECK(ctx, !shard, MGS_ERR_INVALID, "mgs_hier_set_operand_precision: row-sharded hierarchies (halo columns, native tail) keep FP64 operands");
+    // the operands are prepared lazily, before a hierarchy's first cycle: do it now, so that the query answers right after this call
+    MGS_TRY(prepare_fused(h));
+  }
+  const int nl = (int)h->lev.size();
+  int k = 0;      // the longest eligible prefix, at most `levels` long
+  if (bits == 32) while (k < nl - 1 && (levels < 0 || k < levels) && level_f32_eligible(h, k)) ++k;
+  for (int l = 0; l < nl; ++l) {
+    mgs_level &L = h->lev[l];
+    L.op_bits = l < k ? 32 : 64;
+    if (L.op_bits == 32) MGS_TRY(level_refresh_f32(h, L, false));
+    else {      // the FP64 operands were kept: nothing to rebuild on the way back
+      if (L.val_wd32) { hipStreamSynchronize(ctx->stream); mgs_hip_free(L.val_wd32); L.val_wd32 = nullptr; }
+      if (L.ap_val32) { hipStreamSynchronize(ctx->stream); mgs_hip_free(L.ap_val32); L.ap_val32 = nullptr; }
+    }
+  }
+  drop_graph(h);
+  return MGS_OK;
+}
+int mgs_hier_operand_precision(const mgs_hier *h, int level, int *bits) {
+  MGS_CHECK(nullptr, h && bits, MGS_ERR_INVALID, "mgs_hier_operand_precision: NULL argument");
+  MGS_CHECK(h->ctx, level >= 0 && level < (int)h->lev.size(), MGS_ERR_INVALID, "mgs_hier_operand_precision: level %d out of range", level);
+  *bits = level_runs_f32(h, level) ? 32 : 64;
   return MGS_OK;
 }
 // ---- native RCCL transport of a sharded hierarchy (comm_rccl.hip) ----
@@ -892,7 +958,8 @@ int64_t mgs_hier_vcycle_bytes(const mgs_hier *h) {
     const int64_t restr = 4 * (nc + 1) + 12 * nnzP + 8 * nc;
     const bool fused = h->ctx->opt_fuse && h->nu1 == 1 && h->nu2 == 1 && !h->halo && !h->halo_begin && lv.T && lv.T->aggregation &&
                        lv.A->rows == lv.A->cols;
-    if (fused) { tot += (12 * nnz + 28 * n + 4) + restr + (12 * nnz + 40 * n + 8 * nc + 4); continue; }
+    // FP32 level: 4 instead of 8 value bytes per entry in both passes
+    if (fused) { tot += (12 * nnz + 28 * n + 4) + restr + (12 * nnz + 40 * n + 8 * nc + 4) - (level_runs_f32(h, l) ? 8 * nnz : 0); continue; }
     if (h->nu1 > 0) tot += 24 * n + (int64_t)(h->nu1 - 1) * jac + res;   // shortcut + sweeps + residual
     // ν1 = 0: r = b, no residual pass
     tot += restr;
@@ -1123,6 +1190,9 @@ static int cycle_level(mgs_hier *h, int l, const double *b, double *x, bool zero
     mgs_csr Amap = *L.A; Amap.val = L.A->val; Amap.col = L.col_agg; Amap.code = L.code_agg; Amap.owns = false;
     if (ctx->opt_diag_from_values && L.dpos) { Amap.dpos = L.dpos; Amap.dpos_omega = h->omega; }   // t-form post pass: ω/a_ii from the streamed values
     if (ctx->opt_merge_ap && L.AP) { Amap = *L.AP; Amap.code = L.code_ap; Amap.owns = false; }      // A·P, merged: fewer entries, wd read per row
+    // operand precision: both passes of this level read the FP32 copies of the stored values (float forms of the same kernels), or neither does
+    const bool f32 = level_runs_f32(h, l) && !halo;
+    if (f32) { Ahat.val32 = L.val_wd32; Amap.val32 = L.ap_val32; }
     const bool operands = ctx->opt_fuse_operands && L.val_wd && (L.col_agg || (ctx->opt_merge_ap && L.AP)) &&
                           (!halo || mgs_rowcode_usable(&Ahat, true));
     const int *cmap = L.cmap_ext ? L.cmap_ext : L.T->agg;        // gather forms: coarse column of every local column
@@ -1150,7 +1220,7 @@ static int cycle_level(mgs_hier *h, int l, const double *b, double *x, bool zero
     // small level (a dispatch costs what it costs, whatever it does): pre pass and restriction in one aggregate-parallel kernel
     if (ctx->opt_fuse_operands && L.val_wd && L.A->rows <= ctx->opt_aggpre_max_rows && L.A->max_row_len <= 64) {
       if (halo) MGS_TRY(exchange_now(l, b, L.hbuf->d));
-      MGS_TRY(k_agg_pre(L.A, L.val_wd, b, hv, L.T, L.r->d, C.b->d));
+      MGS_TRY(k_agg_pre(L.A, L.val_wd, b, hv, L.T, L.r->d, C.b->d, f32 ? L.val_wd32 : nullptr));
       MGS_TRY(coarse_solve(h, l + 1, C.b->d, C.x->d));
       if (operands) return post_operand(L.r->d, b);
       return pass_with_exchange(ec_exchange, l + 1, ec, ec_halo, [&](int b0, int b1, int ga, int gl) {
@@ -1284,6 +1354,7 @@ static int prepare_fused(mgs_hier *h) {
         if (shard) MGS_TRY(mgs_build_rowcode(ctx, L.A->rows, L.A->rowptr, L.A->col, nullptr, L.A->rows, &L.code_pre, ctx->opt_valcode ? L.val_wd : nullptr));
         else MGS_TRY(mgs_build_rowcode(ctx, L.A->rows, L.A->rowptr, L.A->col, nullptr, 0x7fffffff, &L.code_hat, L.val_wd));
       }
+      MGS_TRY(level_refresh_f32(h, L, new_vals));      // FP32 copies follow their FP64 operands (a new ω rescales Â)
     }
   }
   return MGS_OK;

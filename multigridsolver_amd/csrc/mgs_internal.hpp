@@ -115,6 +115,8 @@ struct mgs_csr {
   const struct mgs_groups *sweep = nullptr;   // views only: launch the coded kernel group by group over these row-block groups (option group_sweep)
   const unsigned char *dpos = nullptr;   // views of the t-form post pass only (not owned): position of the diagonal inside every row, so the
   double dpos_omega = 0.0;               // kernel takes ω/a_ii from the values it streams anyway instead of reading wd (8 B → 1 B per row)
+  const float *val32 = nullptr;   // views of the fused passes on an FP32 level only (not owned): the values rounded to float; the kernels' float forms read
+                                  // these instead of val (products widened to FP64 before they are added)
   int *origin = nullptr;   // coarse operators built by the device setup: the finest-level row each row descends from (its aggregate's
                            // leader, chained through the levels) — the index space the matching's tie-breaks work in; NULL = identity
 };
@@ -223,6 +225,11 @@ struct mgs_level {
   mgs_rowcode *code_ap = nullptr;    // aggregate summed (5 instead of 7 entries per row on the 7-point operator) and its pattern code (offsets from agg[row])
   mgs_rowcode *code_pre = nullptr;   // row shards: pattern code of col with tagged halo words (pre pass reads b + payload)
   mgs_rowcode *code_hat = nullptr;   // option valcode: pattern code of (col, val_wd) for the pre pass on Â
+  // operand precision (mgs_hier_set_operand_precision): FP32 copies of the two setup-time operands' values, rounded to nearest from the
+  // FP64 arrays above (which stay the source of truth and stay allocated: switching back is free and bit-identical)
+  int op_bits = 64;                  // what the level was switched to; whether a cycle really runs on the copies: level_runs_f32 (mgs_api.hip)
+  float *val_wd32 = nullptr;         // nnz + 8 floats
+  float *ap_val32 = nullptr;         // nnz(A·P) + 8 floats
   unsigned char *dpos = nullptr;     // position of the diagonal entry inside each row (255: none / beyond 254), see mgs_csr::dpos
   mgs_groups *grp = nullptr;         // aggregate-complete row-block groups (grouped pre pass = pre pass + restriction in one kernel)
   bool grp_tried = false;
@@ -342,7 +349,9 @@ int mgs_launch_group_pre(const mgs_csr *Ahat, const mgs_groups *G, const mgs_xfe
 int k_diag_inv(const mgs_csr *A, double *dinv, int *bad_count_host);
 int k_diag_pos(const mgs_csr *A, unsigned char *dpos);
 int k_restrict_agg(mgs_ctx *ctx, int nc, const int *cptr, const int *members, const double *r, double *rc);
-int k_agg_pre(const mgs_csr *A, const double *valhat, const double *b, const double *hv, const mgs_xfer *T, double *r_out, double *rc_out);   // small levels: pre pass + restriction, one dispatch
+int k_agg_pre(const mgs_csr *A, const double *valhat, const double *b, const double *hv, const mgs_xfer *T, double *r_out, double *rc_out,
+              const float *valhat32 = nullptr);   // small levels: pre pass + restriction, one dispatch (valhat32: the FP32 copy of valhat is read instead)
+int k_round_vals(mgs_ctx *ctx, const double *in, float *out, int64_t n);   // out_k = (float)in_k, round to nearest: the FP32 operand copies
 int k_prolong_agg(mgs_ctx *ctx, int n, const int *agg, const double *ec, double *x, int add);
 int k_fill(mgs_ctx *ctx, double *d, int64_t n, double v);
 int k_rand(mgs_ctx *ctx, double *d, int64_t n, uint64_t seed, int64_t off);

@@ -33,9 +33,13 @@ def main(argv=None):
     ap.add_argument("--ktg", type=float, default=10.0)
     ap.add_argument("--npass", type=int, default=2)
     ap.add_argument("--tou", type=float, default=8.0)
+    ap.add_argument("--operand-bits", type=int, choices=[64, 32], default=64,
+                    help="stored precision of the cycle's matrix operands Â and A·P (32: values rounded to float, arithmetic stays FP64; single GPU only)")
     ap.add_argument("--dump-x", default=None, help="write the solution (rank order, raw little-endian f64)")
     args = ap.parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1")); rank = int(os.environ.get("RANK", "0"))
+    if world > 1 and args.operand_bits != 64:
+        raise SystemExit("multi-GPU: FP64 operands only (--operand-bits 32 is a single-GPU option)")
     if world > 1:
         import torch  # noqa: F401  — before libmgs.so: both link a HIP runtime, the first one loaded serves the process
     import multigridsolver_amd as mg
@@ -52,6 +56,8 @@ def main(argv=None):
         if args.P:
             h.push_P(mg.Csr.from_mtx(ctx, args.P))
         h.coarsen(args.ktg, args.npass, args.tou).finalize().set_kcycle(args.kcycle)
+        if args.operand_bits != 64:
+            h.set_operand_precision(args.operand_bits)
         x, b = ctx.vec(rows), ctx.vec(bg)
         ctx.sync(); t0 = time.perf_counter()
         st, it, tol = (mg.bicgstab if args.solver == "bicgstab" else lambda *a: mg.fgcr(a[0], a[1], a[2], a[3], 10, a[4], a[5]))(A, x, b, h, args.max_iter, args.tol)
