@@ -63,7 +63,8 @@ int mgs_ctx_destroy(mgs_ctx *ctx);
 const char *mgs_last_error(const mgs_ctx *ctx); /* ctx may be NULL: last global error */
 int mgs_sync(mgs_ctx *ctx);                      /* hipStreamSynchronize              */
 /* Releases the memory the context keeps between calls (the Krylov solvers' work vectors: eight vectors of the operator's size
- * after a BiCGSTABiml solve, bicg.cpp:75 declares them per call; the scratch of the fused inner products). */
+ * after a BiCGSTABiml solve, bicg.cpp:75 declares them per call, four after an mgs_pcg solve — five when the caller's x has no
+ * halo room on a row shard; the scratch of the fused inner products). */
 int mgs_ctx_trim(mgs_ctx *ctx);
 void *mgs_ctx_stream(mgs_ctx *ctx);              /* the hipStream_t in use            */
 const char *mgs_version(void);
@@ -255,6 +256,23 @@ int mgs_bicgstab(const mgs_csr *A, mgs_vec *x, const mgs_vec *b, mgs_hier *h,
  * reported only with the TRUE residual b − A·x below *tol (recomputed at every restart and before every return).  restart 1..64. */
 int mgs_fgcr(const mgs_csr *A, mgs_vec *x, const mgs_vec *b, mgs_hier *h, int restart,
              int *max_iter, double *tol, int *status);
+
+/* Preconditioned conjugate gradients for symmetric positive definite A — the reference's Matlab driver,
+ * src/CPU_Matlab/solve.m:28-31.  Same in/out convention as mgs_bicgstab.  h may be NULL.
+ * *status: 0 converged (decided on the TRUE residual b − A·x, as mgs_fgcr does) / 1 max_iter / 2 r·z not positive (the
+ * preconditioner is not positive definite) / 3 p·A·p not positive (A is not positive definite along p).  *max_iter returns the
+ * iterations done (for status 2 and 3 the iteration that stopped), *tol the last relative residual; whatever the status, x holds
+ * every completed update.  Four work vectors (BiCGSTAB: eight), one cycle and one SpMV per iteration (BiCGSTAB: two of each);
+ * works on row shards as mgs_bicgstab does.  A's symmetry is the caller's responsibility; statuses 2 and 3 are the net.
+ * flexible = 0: classical β = ρ/ρ_prev; requires a fixed symmetric preconditioner — a hierarchy with nu1 != nu2 or with a K-cycle
+ * (mgs_hier_set_kcycle, mgs_hier_set_kcycle_entry) is refused with MGS_ERR_INVALID.  The additive form, a correction scale and FP32
+ * operand storage are allowed (fixed operators); with 32-bit operands (mgs_hier_set_operand_precision) the cycle is symmetric only
+ * to FP32 rounding: flexible = 1 is recommended there.
+ * flexible = 1: β = z·(r − r_prev)/ρ_prev, computed as −α·(z·q)/ρ_prev from the vectors already held — accepts a preconditioner
+ * that changes from call to call (K-cycle) or is not symmetric (V(2,1)); one more stream in the dots pass (88 instead of 80 B per
+ * row beside cycle and SpMV). */
+int mgs_pcg(const mgs_csr *A, mgs_vec *x, const mgs_vec *b, mgs_hier *h, int flexible,
+            int *max_iter, double *tol, int *status);
 
 /* ------------------------------------------------------------- multi-GPU row shards   */
 /* Halo plan of a row-range shard whose CSR uses LOCAL column numbering: columns

@@ -424,3 +424,12 @@ def fgcr(A, x, b, hier=None, restart=10, max_iter=1000, tol=1e-6):
     mi, t, st = C.c_int(max_iter), C.c_double(tol), C.c_int(-1)
     check(lib().mgs_fgcr(A.h, x.h, b.h, hier.h if hier else None, restart, C.byref(mi), C.byref(t), C.byref(st)), A.ctx.h)
     return st.value, mi.value, t.value
+
+
+def pcg(A, x, b, hier=None, max_iter=10000, tol=1e-6, flexible=False):
+    """preconditioned CG for symmetric positive definite A (reference src/CPU_Matlab/solve.m:28-31) → (status, iterations, achieved_tol);
+    status 0 converged on the true residual / 1 max_iter / 2 r·z ≤ 0 / 3 p·A·p ≤ 0.  flexible=True: β = z·(r − r_prev)/ρ_prev, for a
+    preconditioner that is not a fixed symmetric operator (V(ν1 ≠ ν2), K-cycle)"""
+    mi, t, st = C.c_int(max_iter), C.c_double(tol), C.c_int(-1)
+    check(lib().mgs_pcg(A.h, x.h, b.h, hier.h if hier else None, int(bool(flexible)), C.byref(mi), C.byref(t), C.byref(st)), A.ctx.h)
+    return st.value, mi.value, t.value

@@ -8,6 +8,7 @@
 //   SMatrix / readMatrix / writeMatrix        src/common/MatrixIO.cpp:10,12-37,39-57
 //   MultiGridPrecond(A,P), solve(v)           src/common/bicg.cpp:19-62
 //   dot / norm / BiCGSTABiml                  src/common/bicg.cpp:64-136
+//   CGiml (pcg of the Matlab driver)          src/CPU_Matlab/solve.m:28-31
 //   TicToc / printScreen                      src/CPU_C++/TicToc.cpp:18-53
 #pragma once
 #include <chrono>
@@ -153,7 +154,7 @@ struct PrecondOptions {
 class MultiGridPrecond {
   DeviceMatrix A_;
   std::shared_ptr<mgs_hier> h_;
-  bool use_preconditioner_ = true;
+  bool use_preconditioner_ = true, symmetric_ = true;
  public:
   typedef PrecondOptions Options;
   MultiGridPrecond(const SMatrix &A_in, const SMatrix &P_in, Options o = Options()) : A_(A_in) { build(A_, &P_in, o); }
@@ -165,6 +166,7 @@ class MultiGridPrecond {
     return out;
   }
   bool use_preconditioner() const { return use_preconditioner_; }
+  bool symmetric() const { return symmetric_; }          // nu1 == nu2: the cycle is a fixed symmetric operator (CGiml's classical β applies)
   mgs_hier *handle() const { return h_.get(); }
   const DeviceMatrix &matrix() const { return A_; }
   int levels() const { return mgs_hier_nlev(h_.get()); }
@@ -182,7 +184,7 @@ class MultiGridPrecond {
     check(mgs_hier_finalize(h), context());
     if (!o.multiplicative_precond) check(mgs_hier_set_additive(h, 1), context());
     if (o.correction_scale != 1.0) check(mgs_hier_set_correction_scale(h, o.correction_scale), context());
-    use_preconditioner_ = o.use_preconditioner;
+    use_preconditioner_ = o.use_preconditioner; symmetric_ = o.nu1 == o.nu2;
   }
 };
 
@@ -235,6 +237,54 @@ inline int BiCGSTABiml(const DeviceMatrix &A, Vector &x, const Vector &b, const 
 // from — its device copy lives in M
 inline int BiCGSTABiml(const SMatrix &, Vector &x, const Vector &b, const MultiGridPrecond &M, int &max_iter, double &tol) {
   return BiCGSTABiml(M.matrix(), x, b, M, max_iter, tol);
+}
+
+// Preconditioned CG for symmetric positive definite A (the reference's Matlab driver, src/CPU_Matlab/solve.m:28-31), in the calling
+// shape of BiCGSTABiml.  Status: 0 ok (confirmed on the true residual b − A·x) / 1 max_iter / 2 r·z not positive / 3 p·A·p not
+// positive; max_iter and tol are written back.  Generic form (classical β = ρ/ρ_prev): any Matrix with operator*(Vec), any
+// Preconditioner with solve(Vec) that is a fixed symmetric positive operator.
+template <class Matrix, class Vec, class Preconditioner, class Real>
+int CGiml(const Matrix &A, Vec &x, const Vec &b, const Preconditioner &M, int &max_iter, Real &tol) {
+  Real resid, rho = 0, rho_prev = 0, alpha = 0, pq = 0;
+  Vec p, z, q;
+  Real normb = norm(b);
+  Vec r = b - A * x;
+  if (normb == 0.0) normb = 1;
+  if ((resid = norm(r) / normb) <= tol) { tol = resid; max_iter = 0; return 0; }
+  bool restart = true;
+  for (int i = 1; i <= max_iter; i++) {
+    z = M.solve(r);
+    rho = dot(r, z);
+    if (!(rho > 0)) { tol = resid; max_iter = i; return 2; }
+    if (restart) { p = z; restart = false; }
+    else p = z + (rho / rho_prev) * p;
+    q = A * p;
+    pq = dot(p, q);
+    if (!(pq > 0)) { tol = resid; max_iter = i; return 3; }
+    alpha = rho / pq;
+    x += alpha * p;
+    r -= alpha * q;
+    resid = norm(r) / normb;
+    rho_prev = rho;
+    if (resid < tol) {
+      r = b - A * x;
+      if ((resid = norm(r) / normb) < tol) { tol = resid; max_iter = i; return 0; }
+      restart = true;
+    }
+  }
+  tol = resid;
+  return 1;
+}
+// Device-resident fast path (mgs_pcg: four work vectors, three fused vector passes per iteration beside cycle and SpMV).  The
+// flexible β is chosen where the hierarchy is not a fixed symmetric operator (nu1 != nu2): mgs_pcg refuses the classical form there.
+inline int CGiml(const DeviceMatrix &A, Vector &x, const Vector &b, const MultiGridPrecond &M, int &max_iter, double &tol) {
+  int status = -1;
+  check(mgs_pcg(A.handle(), x.out(), b.handle(), M.use_preconditioner() ? M.handle() : nullptr, M.symmetric() ? 0 : 1, &max_iter, &tol, &status), context());
+  return status;
+}
+// with the host SMatrix the preconditioner was built from, as the reference's main() calls its solver (bicg.cpp:168)
+inline int CGiml(const SMatrix &, Vector &x, const Vector &b, const MultiGridPrecond &M, int &max_iter, double &tol) {
+  return CGiml(M.matrix(), x, b, M, max_iter, tol);
 }
 
 // ---------------------------------------------------------------- TicToc.cpp:18-53

@@ -353,6 +353,89 @@ __global__ __launch_bounds__(TB) void update_dot2_partial_vec_kernel(int64_t n, 
   }
 }
 
+// ------------------------------------------------------------------ preconditioned CG (mgs_pcg): the two passes beside dots, cycle and SpMV
+// Direction pass with the LAGGED x update: x ← x + a·p (the step the previous iteration decided; its p is read here anyway), then
+// p ← z + beta·p.  40 B per row (read x, p, z; write x, p) — applied eagerly the x update is a pass of its own (24 B per row more).
+// FIRST (first direction, and the one after a restart): p ← z only; p is NOT read (a pool vector may hold anything, 0·NaN = NaN)
+// and x is not touched (the caller has flushed every pending update before).
+template <bool FIRST>
+__global__ __launch_bounds__(TB) void pcg_dir_kernel(int64_t n, double a, double beta, double *__restrict__ x, double *__restrict__ p,
+                                                     const double *__restrict__ z) {
+  int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * TB;
+  for (; i < n; i += stride) {
+    if (FIRST) p[i] = z[i];
+    else { const double pi = p[i]; x[i] = x[i] + a * pi; p[i] = z[i] + beta * pi; }
+  }
+}
+// 16-byte form (same per-element expressions: same bits)
+template <bool FIRST>
+__global__ __launch_bounds__(TB) void pcg_dir_vec_kernel(int64_t n, double a, double beta, double *__restrict__ x, double *__restrict__ p,
+                                                         const double *__restrict__ z, int nts) {
+  const int64_t n2 = n >> 1;
+  vd2 *__restrict__ xv = reinterpret_cast<vd2 *>(x);
+  vd2 *__restrict__ pv = reinterpret_cast<vd2 *>(p);
+  const vd2 *__restrict__ zv = reinterpret_cast<const vd2 *>(z);
+  const int64_t stride = (int64_t)gridDim.x * TB;
+  for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < n2; i += stride) {
+    const vd2 zi = zv[i];
+    if (FIRST) st2(pv + i, zi, nts != 0);
+    else {
+      const vd2 pi = pv[i], xi = xv[i]; vd2 xo, po;
+      xo.x = xi.x + a * pi.x; xo.y = xi.y + a * pi.y;
+      po.x = zi.x + beta * pi.x; po.y = zi.y + beta * pi.y;
+      st2(xv + i, xo, nts != 0);
+      st2(pv + i, po, nts != 0);
+    }
+  }
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+    if (FIRST) p[n - 1] = z[n - 1];
+    else { const double pi = p[n - 1]; x[n - 1] = x[n - 1] + a * pi; p[n - 1] = z[n - 1] + beta * pi; }
+  }
+}
+// Residual pass IN PLACE: r ← r − a·q with ‖r‖² (24 B per row: read r, q; write r).  update_dot2_partial*_kernel is out of place
+// (`__restrict__` on source and destination) and must not be aliased.  Partial pair per workgroup, the second sum stays zero so
+// that the staged fold of the pairs (k_dot2_finish) serves.
+__global__ __launch_bounds__(TB) void pcg_resid_kernel(int64_t n, double a, double *__restrict__ r, const double *__restrict__ q, double *__restrict__ part) {
+  __shared__ double sh[TB / 64];
+  double s0 = 0.0;
+  int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * TB;
+  for (; i < n; i += stride) { const double ri = r[i] - a * q[i]; r[i] = ri; s0 += ri * ri; }
+  for (int off = 32; off > 0; off >>= 1) s0 += __shfl_down(s0, off);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s0;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t0 = 0.0;
+    for (int w = 0; w < TB / 64; ++w) t0 += sh[w];
+    part[blockIdx.x] = t0; part[gridDim.x + blockIdx.x] = 0.0;
+  }
+}
+// 16-byte form (same per-element expression; lane t adds its pair x then y, a fixed order that does not depend on scheduling)
+__global__ __launch_bounds__(TB) void pcg_resid_vec_kernel(int64_t n, double a, double *__restrict__ r, const double *__restrict__ q, double *__restrict__ part, int nts) {
+  __shared__ double sh[TB / 64];
+  const int64_t n2 = n >> 1;
+  vd2 *__restrict__ rv = reinterpret_cast<vd2 *>(r);
+  const vd2 *__restrict__ qv = reinterpret_cast<const vd2 *>(q);
+  double s0 = 0.0;
+  const int64_t stride = (int64_t)gridDim.x * TB;
+  for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < n2; i += stride) {
+    const vd2 ri = rv[i], qi = qv[i]; vd2 o;
+    o.x = ri.x - a * qi.x; o.y = ri.y - a * qi.y;
+    st2(rv + i, o, nts != 0);
+    s0 += o.x * o.x; s0 += o.y * o.y;
+  }
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) { const double ri = r[n - 1] - a * q[n - 1]; r[n - 1] = ri; s0 += ri * ri; }
+  for (int off = 32; off > 0; off >>= 1) s0 += __shfl_down(s0, off);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s0;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t0 = 0.0;
+    for (int w = 0; w < TB / 64; ++w) t0 += sh[w];
+    part[blockIdx.x] = t0; part[gridDim.x + blockIdx.x] = 0.0;
+  }
+}
+
 // one or two inner products, one pair of elements per lane, one-shot workgroups (see grid_vec): partial pair per workgroup ([2][gridDim.x];
 // NP = 1 leaves the second sum at zero so that the staged fold of the pairs serves both)
 template <int NP>
@@ -973,6 +1056,40 @@ int k_update_dot2(mgs_ctx *ctx, int64_t n, double a, const double *x, double b, 
   hipLaunchKernelGGL(dot2_final_kernel, dim3(1), dim3(TB), 0, ctx->stream, nb, ctx->red_dev, ctx->red_dev + DOT_BLOCKS, pa);
   if (ctx->ncomm) MGS_TRY(mgs_comm_allreduce_sum(ctx->ncomm, ctx->red_dev + DOT_BLOCKS, 2));
   return fetch_results(ctx, 2, out_host2, pa);
+}
+// mgs_pcg, direction pass: first != 0: p ← z (p not read, x not touched); else x ← x + a·p, p ← z + beta·p
+int k_pcg_direction(mgs_ctx *ctx, int64_t n, int first, double a, double beta, double *x, double *p, const double *z) {
+  if (!n) return MGS_OK;
+  if (ctx->opt_blas1_vec && al16(p) && al16(z) && (first || al16(x))) {
+    const dim3 g(grid_vec((n + 1) / 2, ctx));
+    const int nts = ctx->opt_nt_store > 0 && n >= ctx->opt_nt_store;
+    if (first) hipLaunchKernelGGL(pcg_dir_vec_kernel<true>, g, dim3(TB), 0, ctx->stream, n, a, beta, x, p, z, nts);
+    else hipLaunchKernelGGL(pcg_dir_vec_kernel<false>, g, dim3(TB), 0, ctx->stream, n, a, beta, x, p, z, nts);
+  } else {
+    const dim3 g(grid_cap(n, ctx->n_cu));
+    if (first) hipLaunchKernelGGL(pcg_dir_kernel<true>, g, dim3(TB), 0, ctx->stream, n, a, beta, x, p, z);
+    else hipLaunchKernelGGL(pcg_dir_kernel<false>, g, dim3(TB), 0, ctx->stream, n, a, beta, x, p, z);
+  }
+  MGS_HIP(ctx, hipGetLastError());
+  return MGS_OK;
+}
+// mgs_pcg, residual pass in place: r ← r − a·q, out_host2[0] = ‖r‖² (summed over the row shards), out_host2[1] = 0
+int k_pcg_residual(mgs_ctx *ctx, int64_t n, double a, double *r, const double *q, double *out_host2) {
+  if (ctx->opt_blas1_vec && al16(r) && al16(q)) {
+    const int nb = grid_vec((n + 1) / 2, ctx);
+    const int nts = ctx->opt_nt_store > 0 && n >= ctx->opt_nt_store;
+    double *part = ctx->red_dev;
+    if (nb > DOT_BLOCKS / 2) { MGS_TRY(mgs_ensure_dot_part(ctx, 2 * (int64_t)nb)); part = ctx->dot_part; }
+    hipLaunchKernelGGL(pcg_resid_vec_kernel, dim3(nb), dim3(TB), 0, ctx->stream, n, a, r, q, part, nts);
+    MGS_HIP(ctx, hipGetLastError());
+    return k_dot2_finish(ctx, nb, part, out_host2);
+  }
+  int nb = (int)((n + TB - 1) / TB);
+  if (nb > DOT_BLOCKS / 2) nb = DOT_BLOCKS / 2;
+  if (nb < 1) nb = 1;
+  hipLaunchKernelGGL(pcg_resid_kernel, dim3(nb), dim3(TB), 0, ctx->stream, n, a, r, q, ctx->red_dev);
+  MGS_HIP(ctx, hipGetLastError());
+  return k_dot2_finish(ctx, nb, ctx->red_dev, out_host2);
 }
 int k_dot_dev(mgs_ctx *ctx, int64_t n, const double *x, const double *y, double *out_dev) {
   int nb = (int)((n + TB - 1) / TB);

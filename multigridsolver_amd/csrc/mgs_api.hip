@@ -1546,6 +1546,94 @@ int mgs_bicgstab(const mgs_csr *A, mgs_vec *x, const mgs_vec *b, mgs_hier *h, in
   return mgs_sync(ctx);
 }
 
+// Preconditioned conjugate gradients for symmetric positive definite A: the reference's Matlab driver, src/CPU_Matlab/solve.m:28-31
+// (`symm == 1` → pcg).  Four work vectors (r, z, p, q) where BiCGSTAB holds eight, one cycle and one SpMV per iteration where it runs two.
+// Beside those an iteration is three vector passes, 80 B per row (88 flexible):
+//   * dots:       r·z, flexible also q·z (k_dot / k_dot2);
+//   * direction:  x ← x + α_prev·p and p ← z + β·p in ONE pass (k_pcg_direction): the x update of step i rides on the direction pass of
+//                 step i + 1, which reads the old p anyway.  `pending` says that x is one step behind; it is flushed (k_axpby) before
+//                 every return and before every true-residual pass;
+//   * SpMV q = A·p with p·q from its epilogue (mgs_spmv_dots), then the residual in place r ← r − α·q with ‖r‖² (k_pcg_residual).
+// flexible: β = z·(r − r_prev)/ρ_prev (Polak-Ribière form, Notay, SISC 22 (2000)) = −α·(z·q)/ρ_prev since r − r_prev = −α·q and q is
+// still alive — no fifth vector.  It tolerates a preconditioner that is not a fixed symmetric operator (V(ν1 ≠ ν2), K-cycle).
+// Status 0 is reported only on the TRUE residual b − A·x, as mgs_fgcr does; when the recursion said converged and the true residual
+// does not, the method restarts from it (p = z).  r and z keep their addresses for the whole solve, and — the vectors go back to the
+// pool in reverse order — across solves: the cycle replays from one cached graph slot keyed by (r, z).
+int mgs_pcg(const mgs_csr *A, mgs_vec *x, const mgs_vec *b, mgs_hier *h, int flexible, int *max_iter, double *tol, int *status) {
+  mgs_ctx *ctx = A->ctx;
+  MGS_CHECK(ctx, max_iter && tol && status, MGS_ERR_INVALID, "mgs_pcg: NULL out parameter");
+  MGS_CHECK(ctx, flexible || !h || (h->nu1 == h->nu2 && h->kcycle_levels <= 0 && !h->kcycle_entry), MGS_ERR_INVALID,
+            "mgs_pcg: flexible = 0 needs a fixed symmetric preconditioner (nu1 == nu2, no K-cycle); pass flexible = 1");
+  MGS_TRY(mgs_csr_optimize(const_cast<mgs_csr *>(A)));
+  const int n = A->rows, next = A->cols > n ? A->cols : n;
+  MGS_CHECK(ctx, x->n >= n && b->n >= n, MGS_ERR_INVALID, "mgs_pcg: vectors shorter than %d", n);
+  mgs_vec *r = 0, *z = 0, *p = 0, *q = 0, *xe = 0;
+  // returned last-taken-first so that the next solve takes the same vectors in the same roles
+  struct Guard { mgs_ctx *c; std::vector<mgs_vec **> vs; ~Guard() { hipStreamSynchronize(c->stream); for (size_t k = vs.size(); k-- > 0;) ws_put(c, *vs[k]); } } guard{ctx, {}};
+  for (mgs_vec **w : {&r, &z, &p, &q}) { MGS_TRY(ws_get(ctx, w == &p ? next : n, n, w)); guard.vs.push_back(w); }
+  auto view = [&](mgs_vec *full, mgs_vec &out) { out.ctx = ctx; out.n = n; out.d = full->d; out.owns = false; };
+  mgs_vec xv, bv, pv; view(x, xv); view(const_cast<mgs_vec *>(b), bv); view(p, pv);
+  if (x->n < next) { MGS_TRY(ws_get(ctx, next, n, &xe)); guard.vs.push_back(&xe); }
+  auto halo0 = [&](mgs_vec *w) -> int {
+    if (!h) return 0;
+    if (h->lev[0].nx) return native_exchange(h, 0, w->d, w->d + A->rows);
+    if (h->halo) return h->halo(h->halo_user, 0, w->d);
+    if (h->halo_begin) { int rc = h->halo_begin(h->halo_user, 0, w->d); return rc ? rc : h->halo_end(h->halo_user, 0, w->d); }
+    return 0;
+  };
+  double normb = 0, resid = 0, rho = 0, rho_prev = 0, alpha = 0, beta = 0, d2[2] = {0, 0};
+  bool pending = false;                                    // x is one step behind: x += alpha·p not applied yet
+  auto flush = [&]() -> int {
+    if (pending) { MGS_TRY(mgs_axpby(alpha, &pv, 1.0, &xv)); pending = false; }
+    return MGS_OK;
+  };
+  auto true_residual = [&]() -> int {                     // r = b − A·x (x flushed by the caller), resid = ‖r‖/‖b‖
+    mgs_vec *xin = x;
+    if (xe) { MGS_TRY(mgs_vec_copy(&xv, xe)); xin = xe; }
+    if (halo0(xin)) return mgs_fail(ctx, MGS_ERR_STATE, "halo exchange failed");
+    MGS_TRY(mgs_residual(A, xin, &bv, r));
+    double s = 0;
+    MGS_TRY(k_dot(ctx, n, r->d, r->d, &s));
+    resid = std::sqrt(s) / normb;
+    return MGS_OK;
+  };
+  auto done = [&](int it, int st) -> int { int rc = flush(); *max_iter = it; *tol = resid; *status = st; return rc != MGS_OK ? rc : mgs_sync(ctx); };
+  MGS_TRY(mgs_nrm2(&bv, &normb));
+  if (normb == 0.0) normb = 1;
+  MGS_TRY(true_residual());
+  if (resid <= *tol) return done(0, 0);
+  const int maxit = *max_iter;
+  bool restart = true;                                     // the next direction is p = z
+  for (int i = 1; i <= maxit; ++i) {
+    if (h) MGS_TRY(mgs_vcycle(h, r, z, 1)); else MGS_TRY(mgs_vec_copy(r, z));
+    if (flexible && !restart) { MGS_TRY(k_dot2(ctx, n, r->d, z->d, q->d, z->d, d2)); rho = d2[0]; }
+    else MGS_TRY(k_dot(ctx, n, r->d, z->d, &rho));
+    if (!(rho > 0)) return done(i, 2);                     // preconditioner not positive definite (or not a number)
+    if (restart) {
+      MGS_TRY(flush());
+      MGS_TRY(k_pcg_direction(ctx, n, 1, 0.0, 0.0, xv.d, p->d, z->d));
+      restart = false;
+    } else {
+      beta = flexible ? -alpha * d2[1] / rho_prev : rho / rho_prev;
+      MGS_TRY(k_pcg_direction(ctx, n, 0, alpha, beta, xv.d, p->d, z->d));
+      pending = false;
+    }
+    if (halo0(p)) return mgs_fail(ctx, MGS_ERR_STATE, "halo exchange failed");
+    MGS_TRY(mgs_spmv_dots(A, p->d, q->d, p->d, d2));      // q = A·p with p·q from the same pass
+    if (!(d2[0] > 0)) return done(i, 3);                   // A not positive definite along p
+    alpha = rho / d2[0]; pending = true;
+    MGS_TRY(k_pcg_residual(ctx, n, alpha, r->d, q->d, d2));
+    resid = std::sqrt(d2[0]) / normb; rho_prev = rho;
+    if (resid < *tol) {                                    // the recursion says converged: the true residual decides
+      MGS_TRY(flush());
+      MGS_TRY(true_residual());
+      if (resid < *tol) return done(i, 0);
+      restart = true;                                      // the recursion had drifted: r holds the true residual, start over from it
+    }
+  }
+  return done(maxit, 1);
+}
+
 // Flexible GCR(m): c_k = B_k r (variable preconditioner), v_k = A c_k orthogonalised against the v_j of the restart window, r ← r − α_k v_k.
 // Device passes per iteration beside the preconditioner and the SpMV (round 3 ran 8 vector passes and 3 host round trips PER EARLIER
 // DIRECTION — 39 % of a 512³ solve outside the preconditioner):

@@ -735,6 +735,10 @@ class ShardedHierarchy:
         self.install_allreduce()
         return core.bicgstab(self.A, x, b, self.h, max_iter, tol)
 
+    def pcg(self, x, b, max_iter=1000, tol=1e-10, flexible=False):
+        self.install_allreduce()
+        return core.pcg(self.A, x, b, self.h, max_iter, tol, flexible)
+
 
 # ------------------------------------------------------------------ bench leg for N > 1
 def bench_sharded(args, rank, world, local_rank, log, spmv_bytes, emit_json=None, cpu_baseline=None, pmc_traffic=None):

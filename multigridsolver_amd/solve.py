@@ -24,7 +24,8 @@ def main(argv=None):
     ap.add_argument("--P", default=None, help="prolongation .mtx from the AGMG setup (single GPU only); default: aggregate on device")
     ap.add_argument("--tol", type=float, default=1e-6)           # bicg.cpp:148
     ap.add_argument("--max-iter", type=int, default=10000)       # bicg.cpp:164
-    ap.add_argument("--solver", choices=["bicgstab", "fgcr"], default="bicgstab")
+    ap.add_argument("--solver", choices=["bicgstab", "fgcr", "pcg"], default="bicgstab")
+    ap.add_argument("--pcg-flexible", action="store_true", help="--solver pcg: flexible β, for a preconditioner that is not a fixed symmetric operator (--nu1 != --nu2, --kcycle)")
     ap.add_argument("--kcycle", type=int, default=0)
     ap.add_argument("--kcycle-energy", action="store_true", help="K-cycle coefficients from energy inner products (flexible-CG form; symmetric positive definite operators only)")
     ap.add_argument("--omega", type=float, default=0.6)
@@ -60,15 +61,18 @@ def main(argv=None):
             h.set_operand_precision(args.operand_bits)
         x, b = ctx.vec(rows), ctx.vec(bg)
         ctx.sync(); t0 = time.perf_counter()
-        st, it, tol = (mg.bicgstab if args.solver == "bicgstab" else lambda *a: mg.fgcr(a[0], a[1], a[2], a[3], 10, a[4], a[5]))(A, x, b, h, args.max_iter, args.tol)
+        if args.solver == "pcg":
+            st, it, tol = mg.pcg(A, x, b, h, args.max_iter, args.tol, args.pcg_flexible)
+        else:
+            st, it, tol = (mg.bicgstab if args.solver == "bicgstab" else lambda *a: mg.fgcr(a[0], a[1], a[2], a[3], 10, a[4], a[5]))(A, x, b, h, args.max_iter, args.tol)
         ctx.sync(); dt = time.perf_counter() - t0
         xs = x.numpy()
     else:
         import torch
         import torch.distributed as dist
         from . import dist as mgd
-        if args.P or args.solver != "bicgstab" or args.kcycle:
-            raise SystemExit("multi-GPU: device aggregation + BiCGSTAB + V-cycle only")
+        if args.P or args.solver == "fgcr" or args.kcycle:
+            raise SystemExit("multi-GPU: device aggregation + BiCGSTAB or PCG + V-cycle only")
         dist.init_process_group(backend=os.environ.get("MGS_DIST_BACKEND", "nccl"))
         dev = 0 if os.environ.get("MGS_DIST_SHARE_GPU") else int(os.environ.get("LOCAL_RANK", "0"))
         torch.cuda.set_device(dev)
@@ -81,17 +85,18 @@ def main(argv=None):
         lo, hi = mgd.row_ranges(rows, world)[rank]
         x, b = ctx.vec(ncols), ctx.vec(bg[lo:hi])
         ctx.sync(); comm.barrier(); t0 = time.perf_counter()      # collectives on the side stream (dist.py Comm: the cycle's stream gets captured)
-        st, it, tol = sh.bicgstab(x, b, args.max_iter, args.tol)
+        st, it, tol = sh.pcg(x, b, args.max_iter, args.tol, args.pcg_flexible) if args.solver == "pcg" else sh.bicgstab(x, b, args.max_iter, args.tol)
         ctx.sync(); comm.barrier(); dt = time.perf_counter() - t0
         parts = comm.all_gather_object(x.numpy(plan.n_loc))
         xs = np.concatenate(parts)
     if rank == 0:
-        sys.stderr.write("    \033[1;34m[time] \033[0m%-42s : %f.\n" % ("BiCGStab_SolveTimer", dt))
+        pcg = args.solver == "pcg"
+        sys.stderr.write("    \033[1;34m[time] \033[0m%-42s : %f.\n" % ("PCG_SolveTimer" if pcg else "BiCGStab_SolveTimer", dt))
         if st == 0:
             print("    \033[32m\033[1m[info] \033[00m%-42s : %g." % ("Tolerance ", tol))
-            print("    \033[32m\033[1m[info] \033[00m%-42s : %d." % ("Number of iterations BICG", it))
+            print("    \033[32m\033[1m[info] \033[00m%-42s : %d." % ("Number of iterations PCG" if pcg else "Number of iterations BICG", it))
         else:
-            print("BiCGSTABiml encountered a problem with status code: %d" % st)
+            print(("PCG encountered a problem with status code: %d" if pcg else "BiCGSTABiml encountered a problem with status code: %d") % st)
         if args.dump_x:
             xs.astype("<f8").tofile(args.dump_x)
     if world > 1:
