@@ -96,6 +96,15 @@ int mgs_csr_shape(const mgs_csr *A, int *rows, int *cols, int64_t *nnz);
 int mgs_csr_destroy(mgs_csr *A);
 /* device pointers (for zero-copy interop, e.g. the Eigen CPU baseline after download) */
 int mgs_csr_device_ptrs(const mgs_csr *A, void **rowptr, void **col, void **val);
+/* New values for an uploaded matrix, SAME sparsity pattern, in place: the device arrays do not move, so hierarchies built on A
+ * and their captured cycles stay valid (follow with mgs_hier_refresh).  No reference counterpart: the reference uploads a new
+ * matrix and reruns its constructor per matrix (bicg.cpp:19-44).  host_val / device_val: nnz doubles in A's storage order; the
+ * _dev form is a device-to-device copy on the context's stream (not synchronised).  Every other per-matrix cache (row-block
+ * bounds, launch plan, index pattern code, origin) depends on the pattern only and is kept.
+ * MGS_ERR_INVALID: A or the values NULL; nnz differs from the matrix's; the matrix carries a value-carrying pattern code
+ * (option "valcode": its tables hold the old values).                                                                    */
+int mgs_csr_update_values(mgs_csr *A, const double *host_val, int64_t nnz);
+int mgs_csr_update_values_dev(mgs_csr *A, const void *device_val, int64_t nnz);
 /* Synthetic operator generated on device: 7-point 3-D Poisson on an
  * N^3 grid, 3-D extension of src/common/poisson.cpp:11-33 (diag 6, off-diagonals −1,
  * row e=(i*N+j)*N+k, ascending columns).  Rows of planes [plane_lo, plane_hi) only
@@ -184,6 +193,33 @@ int mgs_hier_coarsen(mgs_hier *h, double ktg, int npass, double tou, int coarse_
  * smoothed by 8 damped-Jacobi sweeps instead.                                          */
 int mgs_hier_finalize(mgs_hier *h);
 int mgs_hier_set_smoother(mgs_hier *h, double omega, int nu1, int nu2);
+/* Values changed, pattern did not (time stepping, Picard / Newton iterations, parameter sweeps): recomputes everything in h
+ * that depends on matrix VALUES from the current values of the fine operator — the mgs_csr handle given to mgs_hier_create,
+ * after mgs_csr_update_values — and keeps what depends on the pattern only: aggregates, coarse patterns, pattern codes,
+ * row-block groups, every buffer.  Nearest reference line: the constructor, bicg.cpp:19-44, which the reference reruns per
+ * matrix; reusing the interpolation has no reference counterpart (hypre / PETSc / AmgX offer it as structure reuse).
+ * Level by level from the top: D⁻¹ from the new diagonal; the next level's values A_c = PᵀAP with the level's (composed)
+ * aggregation, written into that level's existing val array by ONE launch of a numeric Galerkin kernel for the known
+ * pattern (no count pass, scan, allocation or host synchronisation; same summation order as mgs_csr_galerkin /
+ * mgs_hier_push_P, so bit-identical to them for the same A and P); the operands of the fused passes that a cycle has already
+ * built — ωD⁻¹, Â, the values of A·P, their FP32 copies on levels switched to 32 bits — in their existing buffers (operands
+ * not built yet are left to the next cycle); at the end the coarsest dense inverse into its existing buffer.  Smoother,
+ * K-cycle, additive form, correction scale and operand precision are settings and stay.  No device buffer moves, so the
+ * cached cycle graphs (which capture pointers and scalars, not values) are kept and replay with the new values; the host
+ * reads one pair of counters per refresh besides what the dense inverse does.  From the second refresh on the bytes in use
+ * do not change (the first one keeps 8 bytes of device flags: mgs_hier_refresh_info out[3]).
+ * Caveat: mgs_hier_coarsen with npass >= 2 builds A_c as the chained product P2ᵀ(P1ᵀAP1)P2, the refresh forms PᵀAP with the
+ * composed P in one pass: the two agree to rounding, not bit for bit, so a refresh with unchanged values may move coarse
+ * entries in their last bits.  When the aggregates have aged and a rebuild is due is the caller's decision.
+ * MGS_ERR_NUMERIC: a missing or zero diagonal on any level, or a singular coarsest operator — the hierarchy is then left
+ * un-finalized (cycles return MGS_ERR_STATE, cached graphs are dropped) until a later refresh succeeds.
+ * MGS_ERR_STATE: before mgs_hier_finalize; entries of the fine operator fall outside the kept coarse patterns (its pattern is
+ * not the one the hierarchy was built for).  MGS_ERR_INVALID: h NULL; a row-sharded hierarchy (halo columns, halo callbacks,
+ * native plans or tail); a level whose transfer is a general P, not an aggregation; option "valcode".                    */
+int mgs_hier_refresh(mgs_hier *h);
+/* diagnostics: out[0] refreshes done, out[1] = 1 if the last one kept the cached graphs, out[2] levels refreshed by the device
+ * kernel, out[3] bytes the refresh keeps allocated beyond the hierarchy's own */
+int mgs_hier_refresh_info(const mgs_hier *h, int64_t out[4]);
 /* Operand precision of the cycle (the reference's GPU path keeps its matrices in float32: SURVEY G3,
  * src/GPU_CUDAC++/MatrixIO.cu:32-36).  Here only the STORED values of the two setup-time operands of the fused zero-guess
  * V(1,1) passes — Â = A·diag(ωD⁻¹) and A·P — are rounded to FP32 (round to nearest, on the device, from the FP64

@@ -159,6 +159,20 @@ class Csr:
         out = (C.c_int64 * 4)(); lib().mgs_csr_rowcode_info(self.h, out)
         return dict(zip(["coded_blocks", "blocks", "table_ints", "table_budget"], [int(v) for v in out]))
 
+    def update_values(self, val, n=None):
+        """new values, same pattern, in place (mgs_csr_update_values): a host array, or a Vec / a device pointer with its length `n`
+        for the device-to-device form; returns self.  Follow with Hierarchy.refresh() on hierarchies built on this matrix."""
+        if isinstance(val, Vec):
+            check(lib().mgs_csr_update_values_dev(self.h, C.c_void_p(val.ptr), len(val) if n is None else int(n)), self.ctx.h)
+        elif isinstance(val, (int, np.integer)):
+            if n is None:
+                raise ValueError("update_values: a device pointer needs its length n")
+            check(lib().mgs_csr_update_values_dev(self.h, C.c_void_p(int(val)), int(n)), self.ctx.h)
+        else:
+            a = np.ascontiguousarray(val, dtype=np.float64)
+            check(lib().mgs_csr_update_values(self.h, _dp(a), a.size), self.ctx.h)
+        return self
+
     def download(self):
         rows, _ = self.shape; nnz = self.nnz
         rp = np.empty(rows + 1, dtype=np.int32); ci = np.empty(max(nnz, 1), dtype=np.int32); v = np.empty(max(nnz, 1))
@@ -314,6 +328,15 @@ class Hierarchy:
 
     def finalize(self):
         check(lib().mgs_hier_finalize(self.h), self.ctx.h); return self
+
+    def refresh(self):
+        """the fine operator's values changed, its pattern did not (Csr.update_values): recompute the coarse operators, D⁻¹, the fused
+        passes' operands and the coarsest inverse in place; aggregates, patterns, codes and cached graphs are kept (mgs_hier_refresh)"""
+        check(lib().mgs_hier_refresh(self.h), self.ctx.h); return self
+
+    def refresh_info(self):
+        out = (C.c_int64 * 4)(); check(lib().mgs_hier_refresh_info(self.h, out), self.ctx.h)
+        return dict(zip(["refreshes", "kept_graphs", "device_levels", "extra_bytes"], [int(v) for v in out]))
 
     def set_smoother(self, omega, nu1, nu2):
         check(lib().mgs_hier_set_smoother(self.h, omega, nu1, nu2), self.ctx.h); return self

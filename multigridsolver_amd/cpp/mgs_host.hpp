@@ -131,6 +131,21 @@ class DeviceMatrix {
   int rows() const { return rows_; }
   int cols() const { return cols_; }
   mgs_csr *handle() const { return a_.get(); }
+  // New values, same pattern, in place (mgs.h: mgs_csr_update_values; the reference would upload a new matrix).  The pattern of A is
+  // compared with the device copy's on the host: a different rowptr / col throws Error(MGS_ERR_INVALID).
+  void update_values(const SMatrix &A) {
+    int r = 0, c = 0; int64_t nnz = 0;
+    check(mgs_csr_shape(a_.get(), &r, &c, &nnz), context());
+    bool same = r == A.rows() && c == A.cols() && nnz == (int64_t)A.nonZeros() && (int)A.rowptr.size() == r + 1;
+    if (same) {
+      std::vector<int> rp((size_t)r + 1), ci((size_t)nnz + 1);
+      check(mgs_csr_download(a_.get(), rp.data(), ci.data(), nullptr), context());
+      ci.resize((size_t)nnz);
+      same = rp == A.rowptr && ci == A.col;
+    }
+    if (!same) throw Error(MGS_ERR_INVALID, "DeviceMatrix::update_values: the sparsity pattern differs from the uploaded matrix's");
+    check(mgs_csr_update_values(a_.get(), A.val.data(), nnz), context());
+  }
   Vector operator*(const Vector &x) const {            // bicg.cpp:57,82,107,117
     Vector y(rows_); check(mgs_spmv(a_.get(), x.handle(), y.out()), context()); return y;
   }
@@ -174,6 +189,13 @@ class MultiGridPrecond {
   // float32, src/GPU_CUDAC++/MatrixIO.cu:32-36): bits = 64 | 32, on at most `levels` leading levels (< 0: every eligible one)
   void set_operand_precision(int bits, int levels = -1) { check(mgs_hier_set_operand_precision(h_.get(), bits, levels), context()); }
   int operand_precision(int level) const { int bits = 64; check(mgs_hier_operand_precision(h_.get(), level, &bits), context()); return bits; }
+  // Values changed, pattern did not (mgs.h: mgs_hier_refresh; the reference reruns its constructor per matrix, bicg.cpp:19-44): the
+  // aggregates and everything that depends on the pattern only are kept, the numbers are recomputed on the device.  refresh() reads
+  // the device matrix as it stands (after DeviceMatrix::update_values on the matrix handed to the constructor); refresh(A_new)
+  // first writes A_new's values into the preconditioner's matrix — its own upload for the (SMatrix, SMatrix) constructor, the
+  // caller's shared one otherwise — and throws Error(MGS_ERR_INVALID) if A_new's pattern differs.
+  void refresh() { check(mgs_hier_refresh(h_.get()), context()); }
+  void refresh(const SMatrix &A_new) { A_.update_values(A_new); refresh(); }
  private:
   void build(const DeviceMatrix &A, const SMatrix *P, const Options &o) {
     mgs_hier *h = nullptr;

@@ -213,13 +213,12 @@ __global__ void diag_pos_kernel(int n, const int *__restrict__ rowptr, const int
   }
   dpos[i] = (unsigned char)pos;
 }
-__global__ void scale_vals_kernel(int n, const int *__restrict__ rowptr, const int *__restrict__ col, const double *__restrict__ val,
-                                  const double *__restrict__ wd, double *__restrict__ out) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  // row shards: wd's halo part holds the owners' ω/a_jj (fetched once at setup), so a halo column is scaled like an owned one and
-  // the pre pass's payload is the peers' raw right-hand side
-  for (int k = rowptr[i]; k < rowptr[i + 1]; ++k) out[k] = val[k] * wd[col[k]];
+// out_k = a_k·wd[col_k], one lane per ENTRY (the rows play no part: coalesced streams of val, col and out, one gather).
+// Row shards: wd's halo part holds the owners' ω/a_jj (fetched once at setup), so a halo column is scaled like an owned one and
+// the pre pass's payload is the peers' raw right-hand side.
+__global__ void scale_vals_kernel(int64_t nnz, const int *__restrict__ col, const double *__restrict__ val, const double *__restrict__ wd, double *__restrict__ out) {
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < nnz) out[k] = val[k] * wd[col[k]];
 }
 __global__ void map_cols_kernel(int n, const int *__restrict__ rowptr, const int *__restrict__ col, const int *__restrict__ cmap, int *__restrict__ out) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -809,6 +808,15 @@ int k_diag_inv(const mgs_csr *A, double *dinv, int *bad_count_host) {
   return MGS_OK;
 }
 
+// the same kernel without the host round trip (mgs_hier_refresh): the count of bad rows is ADDED to *bad_dev, which the caller reads later
+int k_diag_inv_async(const mgs_csr *A, double *dinv, int *bad_dev) {
+  mgs_ctx *ctx = A->ctx;
+  if (A->rows)
+    hipLaunchKernelGGL(diag_inv_kernel, dim3(mgs_grid(A->rows, TB)), dim3(TB), 0, ctx->stream, A->rows, A->rowptr, A->col, A->val, dinv, bad_dev);
+  MGS_HIP(ctx, hipGetLastError());
+  return MGS_OK;
+}
+
 int k_diag_pos(const mgs_csr *A, unsigned char *dpos) {
   mgs_ctx *ctx = A->ctx;
   if (A->rows) hipLaunchKernelGGL(diag_pos_kernel, dim3(mgs_grid(A->rows, TB)), dim3(TB), 0, ctx->stream, A->rows, A->rowptr, A->col, dpos);
@@ -895,7 +903,7 @@ int k_round_vals(mgs_ctx *ctx, const double *in, float *out, int64_t n) {
   return MGS_OK;
 }
 int k_scale_vals(mgs_ctx *ctx, const mgs_csr *A, const double *wd, double *out) {
-  if (A->rows) hipLaunchKernelGGL(scale_vals_kernel, dim3(mgs_grid(A->rows, TB)), dim3(TB), 0, ctx->stream, A->rows, A->rowptr, A->col, A->val, wd, out);
+  if (A->nnz) hipLaunchKernelGGL(scale_vals_kernel, dim3(mgs_grid(A->nnz, TB)), dim3(TB), 0, ctx->stream, A->nnz, A->col, A->val, wd, out);
   MGS_HIP(ctx, hipGetLastError());
   return MGS_OK;
 }
@@ -1180,13 +1188,16 @@ int k_dense_gemv(mgs_ctx *ctx, int n, const double *M, const double *b, double *
   return MGS_OK;
 }
 
+// *inv_out == NULL: the n·n result is allocated here (and released again on failure); else it is written into the caller's buffer
+// (mgs_hier_refresh: the cached graphs hold that pointer), which stays the caller's whatever happens
 int k_dense_inverse(mgs_ctx *ctx, const mgs_csr *A, double **inv_out) {
   const int n = A->rows;
+  double *const into = *inv_out;
   MGS_CHECK(ctx, A->cols == n, MGS_ERR_INVALID, "coarsest operator is not square (%d x %d)", A->rows, A->cols);
   double *W = nullptr, *colk = nullptr, *inv = nullptr; int *piv = nullptr;
   MGS_TRY(mgs_dev_alloc(ctx, &W, (size_t)n * 2 * n));
   MGS_TRY(mgs_dev_alloc(ctx, &colk, (size_t)n + 1));
-  MGS_TRY(mgs_dev_alloc(ctx, &inv, (size_t)n * n));
+  if (into) inv = into; else MGS_TRY(mgs_dev_alloc(ctx, &inv, (size_t)n * n));
   MGS_TRY(mgs_dev_alloc(ctx, &piv, 2));
   hipStream_t s = ctx->stream;
   MGS_HIP(ctx, hipMemsetAsync(W, 0, sizeof(double) * (size_t)n * 2 * n, s));
@@ -1203,7 +1214,7 @@ int k_dense_inverse(mgs_ctx *ctx, const mgs_csr *A, double **inv_out) {
   MGS_HIP(ctx, hipMemcpyAsync(h, piv, sizeof h, hipMemcpyDeviceToHost, s));
   MGS_HIP(ctx, hipStreamSynchronize(s));
   MGS_HIP(ctx, mgs_hip_free(W)); MGS_HIP(ctx, mgs_hip_free(colk)); MGS_HIP(ctx, mgs_hip_free(piv));
-  if (h[1]) { mgs_hip_free(inv); return mgs_fail(ctx, MGS_ERR_NUMERIC, "coarsest operator (%d rows) is singular", n); }
+  if (h[1]) { if (!into) mgs_hip_free(inv); return mgs_fail(ctx, MGS_ERR_NUMERIC, "coarsest operator (%d rows) is singular", n); }
   *inv_out = inv;
   return MGS_OK;
 }

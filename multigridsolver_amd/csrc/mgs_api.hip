@@ -356,6 +356,30 @@ int mgs_csr_set_origin(mgs_csr *A, const int *origin) {
   MGS_HIP(ctx, hipMemcpy(A->origin, origin, sizeof(int) * (size_t)A->rows, hipMemcpyHostToDevice));
   return MGS_OK;
 }
+// New values for an uploaded matrix, same pattern, in place: the device arrays do not move, so hierarchies and captured cycles that
+// hold their addresses stay valid.  Every per-matrix cache is pattern-only (blkptr, launch plan, index code, origin) and stays —
+// except a value-carrying pattern code (option valcode), which is why that case is refused.
+static int update_values_check(mgs_csr *A, const void *src, int64_t nnz, const char *who) {
+  MGS_CHECK(nullptr, A, MGS_ERR_INVALID, "%s: NULL matrix", who);
+  mgs_ctx *ctx = A->ctx;
+  MGS_CHECK(ctx, nnz == A->nnz, MGS_ERR_INVALID, "%s: %lld values given, the matrix has %lld entries", who, (long long)nnz, (long long)A->nnz);
+  MGS_CHECK(ctx, src || nnz == 0, MGS_ERR_INVALID, "%s: NULL values", who);
+  MGS_CHECK(ctx, !(A->code && A->code->vtab), MGS_ERR_INVALID, "%s: the matrix carries a value-carrying pattern code (option valcode): upload it again instead", who);
+  return MGS_OK;
+}
+int mgs_csr_update_values(mgs_csr *A, const double *host_val, int64_t nnz) {
+  MGS_TRY(update_values_check(A, host_val, nnz, "mgs_csr_update_values"));
+  mgs_ctx *ctx = A->ctx;
+  if (nnz) MGS_HIP(ctx, hipMemcpyAsync(A->val, host_val, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream));
+  MGS_HIP(ctx, hipStreamSynchronize(ctx->stream));      // the caller may reuse host_val right away
+  return MGS_OK;
+}
+int mgs_csr_update_values_dev(mgs_csr *A, const void *device_val, int64_t nnz) {
+  MGS_TRY(update_values_check(A, device_val, nnz, "mgs_csr_update_values_dev"));
+  mgs_ctx *ctx = A->ctx;
+  if (nnz && device_val != (const void *)A->val) MGS_HIP(ctx, hipMemcpyAsync(A->val, device_val, sizeof(double) * (size_t)nnz, hipMemcpyDeviceToDevice, ctx->stream));
+  return MGS_OK;
+}
 int mgs_csr_destroy(mgs_csr *A) {
   if (!A) return MGS_OK;
   if (A->owns) { if (A->rowptr) mgs_hip_free(A->rowptr); if (A->col) mgs_hip_free(A->col); if (A->val) mgs_hip_free(A->val); }
@@ -607,6 +631,7 @@ int mgs_hier_destroy(mgs_hier *h) {
   for (hipEvent_t e : h->fork_events) hipEventDestroy(e);
   for (auto &L : h->lev) level_free(L);
   if (h->inv) mgs_hip_free(h->inv);
+  if (h->refresh_flags) mgs_hip_free(h->refresh_flags);
   free_native_tail(h);
   delete h;
   return MGS_OK;
@@ -823,7 +848,7 @@ static int push_level(mgs_hier *h, mgs_xfer *T, mgs_csr *Ac) {
   h->lev.back().T = T;
   h->lev.emplace_back();
   int rc = level_init(h, h->lev.back(), Ac, true);
-  h->finalized = false; drop_graph(h);
+  h->finalized = false; h->refresh_failed = false; drop_graph(h);
   if (h->inv) { mgs_hip_free(h->inv); h->inv = nullptr; }
   return rc;
 }
@@ -910,6 +935,7 @@ int mgs_hier_finalize(mgs_hier *h) {
   if (h->inv) { mgs_hip_free(h->inv); h->inv = nullptr; }
   h->nc = Ac->rows;
   h->coarse_sweeps = 0;
+  h->refresh_failed = false;
   if (Ac->rows > 8192) {
     // Coarsening stopped far above the dense limit (e.g. every row is in G0: the operator is so diagonally
     // dominant that Jacobi alone converges, AGMG.cpp:118-123).  The coarsest level is then smoothed
@@ -920,6 +946,66 @@ int mgs_hier_finalize(mgs_hier *h) {
   }
   MGS_TRY(k_dense_inverse(ctx, Ac, &h->inv));
   h->finalized = true; drop_graph(h);
+  return MGS_OK;
+}
+
+// Values changed, pattern did not: everything in h that depends on matrix VALUES is recomputed from the fine operator's current
+// values, level by level from the top — D⁻¹, the next level's operator (numeric Galerkin product into the existing val array), and
+// whichever operands of the fused passes prepare_fused has already built (wd, Â, A·P, their FP32 copies), each in its existing
+// buffer.  Aggregates, patterns, pattern codes, row-block groups, buffers and — because no device buffer moves — the cached cycle
+// graphs are kept.  Everything is enqueued on the context's stream; the host reads two counters once, before the dense inverse.
+int mgs_hier_refresh(mgs_hier *h) {
+  MGS_CHECK(nullptr, h, MGS_ERR_INVALID, "mgs_hier_refresh: NULL hierarchy");
+  mgs_ctx *ctx = h->ctx;
+  MGS_CHECK(ctx, h->finalized || h->refresh_failed, MGS_ERR_STATE, "mgs_hier_refresh: call mgs_hier_finalize first");
+  MGS_CHECK(ctx, !ctx->opt_valcode, MGS_ERR_INVALID, "mgs_hier_refresh: option valcode is on (pattern codes carry the values): rebuild the hierarchy instead");
+  bool shard = h->halo || h->halo_begin || h->halo_fused || h->native || h->ntail || h->coarse;
+  for (auto &L : h->lev) shard = shard || L.A->cols > L.A->rows || L.nx;
+  MGS_CHECK(ctx, !shard, MGS_ERR_INVALID, "mgs_hier_refresh: row-sharded hierarchies (halo columns, halo callbacks, native plans or tail) are not refreshed: rebuild them");
+  const int nl = (int)h->lev.size();
+  for (int l = 0; l < nl; ++l) {
+    const mgs_level &L = h->lev[l];
+    MGS_CHECK(ctx, l + 1 >= nl || (L.T && L.T->aggregation), MGS_ERR_INVALID, "mgs_hier_refresh: the transfer of level %d is a general P, not an aggregation", l);
+    MGS_CHECK(ctx, !(L.A->code && L.A->code->vtab) && !L.code_hat && !(L.code_ap && L.code_ap->vtab), MGS_ERR_INVALID,
+              "mgs_hier_refresh: level %d carries a value-carrying pattern code (built under option valcode)", l);
+  }
+  bool kept = true;
+  if (!h->refresh_flags) MGS_TRY(mgs_dev_alloc(ctx, &h->refresh_flags, 2));
+  MGS_HIP(ctx, hipMemsetAsync(h->refresh_flags, 0, 2 * sizeof(int), ctx->stream));
+  int rc = MGS_OK;
+  for (int l = 0; l < nl && rc == MGS_OK; ++l) {
+    mgs_level &L = h->lev[l];
+    rc = k_diag_inv_async(L.A, L.dinv->d, h->refresh_flags);
+    if (l + 1 >= nl) break;
+    if (rc == MGS_OK) rc = k_galerkin_numeric(L.A, L.T->n_coarse, L.T->cptr, L.T->members, L.T->agg, const_cast<mgs_csr *>(h->lev[l + 1].A), h->refresh_flags + 1);
+    if (!L.wd) continue;      // operands not built yet: the next cycle's prepare_fused sees the new values anyway
+    if (rc == MGS_OK) rc = k_axpby(ctx, L.n_ext, h->omega, L.dinv->d, 0.0, L.wd->d);
+    L.wd_omega = h->omega;    // (a new ω set since the last cycle: mgs_hier_set_smoother has dropped the graphs already)
+    if (rc == MGS_OK && L.val_wd) rc = k_scale_vals(ctx, L.A, L.wd->d, L.val_wd);
+    if (rc == MGS_OK && L.AP) rc = k_galerkin_numeric(L.A, L.A->rows, nullptr, nullptr, L.T->agg, L.AP, h->refresh_flags + 1);
+    if (rc == MGS_OK && L.val_wd && L.val_wd32) rc = k_round_vals(ctx, L.val_wd, L.val_wd32, L.A->nnz);
+    if (rc == MGS_OK && L.AP && L.ap_val32) rc = k_round_vals(ctx, L.AP->val, L.ap_val32, L.AP->nnz);
+  }
+  int flags[2] = {0, 0};
+  if (rc == MGS_OK && hipMemcpyAsync(flags, h->refresh_flags, sizeof flags, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = mgs_fail(ctx, MGS_ERR_HIP, "mgs_hier_refresh: flag copy failed");
+  if (rc == MGS_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = mgs_fail(ctx, MGS_ERR_HIP, "mgs_hier_refresh: %s", hipGetErrorString(hipGetLastError()));
+  if (rc == MGS_OK && flags[1]) rc = mgs_fail(ctx, MGS_ERR_STATE, "mgs_hier_refresh: %d entries fall outside the kept coarse patterns (the fine pattern is not the one the hierarchy was built for)", flags[1]);
+  if (rc == MGS_OK && flags[0]) rc = mgs_fail(ctx, MGS_ERR_NUMERIC, "mgs_hier_refresh: %d rows of the refreshed operators have a missing or zero diagonal", flags[0]);
+  if (rc == MGS_OK && !h->coarse_sweeps) {      // coarsest dense inverse, into the buffer the cached graphs know
+    if (!h->inv) { kept = false; drop_graph(h); }
+    rc = k_dense_inverse(ctx, h->lev.back().A, &h->inv);
+  }
+  if (rc != MGS_OK) {      // half-refreshed state must not be replayed: no cycle until a later refresh (or finalize) succeeds
+    h->finalized = false; h->refresh_failed = true; h->refresh_kept_graphs = 0; drop_graph(h);
+    return rc;
+  }
+  h->finalized = true; h->refresh_failed = false;
+  ++h->refresh_count; h->refresh_kept_graphs = kept ? 1 : 0; h->refresh_dev_levels = nl - 1;
+  return MGS_OK;
+}
+int mgs_hier_refresh_info(const mgs_hier *h, int64_t out[4]) {
+  MGS_CHECK(nullptr, h && out, MGS_ERR_INVALID, "mgs_hier_refresh_info: NULL argument");
+  out[0] = h->refresh_count; out[1] = h->refresh_kept_graphs; out[2] = h->refresh_dev_levels; out[3] = h->refresh_flags ? (int64_t)(2 * sizeof(int)) : 0;
   return MGS_OK;
 }
 

@@ -277,6 +277,10 @@ struct mgs_hier {
   bool capturing = false;
   hipGraphExec_t coarse_exec = nullptr;  // split launch (opt_graph_split_rows): coarse_solve(level 1) on the level's own buffers, captured once
   bool coarse_launch = false;            // set around the eager fine-level passes: coarse_solve(h, 1, ..) replays coarse_exec
+  // mgs_hier_refresh: counters of mgs_hier_refresh_info and the device flags one refresh reads back at its end
+  int64_t refresh_count = 0, refresh_kept_graphs = 0, refresh_dev_levels = 0;
+  int *refresh_flags = nullptr;   // [0] rows with a missing or zero diagonal (all levels), [1] entries outside the kept coarse patterns
+  bool refresh_failed = false;    // the last refresh ended with MGS_ERR_NUMERIC: un-finalized until a later refresh succeeds
   std::vector<hipEvent_t> fork_events;   // fork/join events of the captured native cycle (two per overlapped exchange)
   size_t fork_used = 0;
 };
@@ -347,6 +351,7 @@ int mgs_launch_group_pre(const mgs_csr *Ahat, const mgs_groups *G, const mgs_xfe
                          double *t_out, double *r_out, double *rc_out, const double *hv, int split);
 // (kernels_aux.hip)
 int k_diag_inv(const mgs_csr *A, double *dinv, int *bad_count_host);
+int k_diag_inv_async(const mgs_csr *A, double *dinv, int *bad_dev);   // no host round trip: bad rows are added to *bad_dev
 int k_diag_pos(const mgs_csr *A, unsigned char *dpos);
 int k_restrict_agg(mgs_ctx *ctx, int nc, const int *cptr, const int *members, const double *r, double *rc);
 int k_agg_pre(const mgs_csr *A, const double *valhat, const double *b, const double *hv, const mgs_xfer *T, double *r_out, double *rc_out,
@@ -376,7 +381,7 @@ int k_maxpy_dot2(mgs_ctx *ctx, int64_t n, int K, const double *x, const double *
 int k_kc_update_r(mgs_ctx *ctx, int n, const double *scal, const double *r, const double *v1, double *rp);
 int k_kc_orth_dots(mgs_ctx *ctx, int n, bool energy, double *scal, const double *c1, const double *c2, const double *v1, const double *v2, const double *rp);
 int k_kc_combine(mgs_ctx *ctx, int n, const double *scal, const double *c1, const double *c2, double *x);
-int k_dense_inverse(mgs_ctx *ctx, const mgs_csr *A, double **inv_out);
+int k_dense_inverse(mgs_ctx *ctx, const mgs_csr *A, double **inv_out);   // *inv_out != NULL on entry: written in place
 int k_poisson3d(mgs_ctx *ctx, int N, int plane_lo, int plane_hi, int local_cols, mgs_csr **out);
 int k_poisson2d(mgs_ctx *ctx, int n, mgs_csr **out);
 int k_gather(mgs_ctx *ctx, const double *x, const int *idx, int64_t n, double *out);
@@ -386,6 +391,8 @@ int k_transpose(const mgs_csr *A, mgs_csr **out);
 int k_exclusive_scan_i32(mgs_ctx *ctx, const int *in, int *out, int64_t n, int64_t *total_host);
 int k_galerkin_agg(const mgs_csr *A, const mgs_xfer *T, mgs_csr **out);
 int k_build_ap(const mgs_csr *A, const mgs_xfer *T, const int *cmap_ext, int ncols, mgs_csr **out);   // cmap_ext = NULL: square level, T->agg
+// values of C = PᵀAP (or A·P with cptr == NULL) for C's existing pattern, one launch, no host synchronisation (mgs_hier_refresh)
+int k_galerkin_numeric(const mgs_csr *A, int nc, const int *cptr, const int *members, const int *colmap, mgs_csr *C, int *miss_dev);
 int k_galerkin_agg_ext(const mgs_csr *A, const mgs_xfer *T, const int *halo_map_dev, int n_halo_c, mgs_csr **out);
 int k_xfer_from_agg_host(mgs_ctx *ctx, int n_fine, int n_coarse, const int *agg_host, mgs_xfer **out);
 int k_galerkin_general(const mgs_csr *A, const mgs_xfer *T, mgs_csr **out);

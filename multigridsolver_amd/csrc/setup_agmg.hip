@@ -196,6 +196,61 @@ __global__ __launch_bounds__(TBK) void galerkin_lds_kernel(int nc, const int *__
   if (!spilled) for (int q = 0; q < cnt; ++q) { ccol[dst + q] = keys[q * TBK + t]; cval[dst + q] = vals[q * TBK + t]; }
 }
 
+// Numeric Galerkin product for a KNOWN output pattern (mgs_hier_refresh): the coarse operator's rowptr / ccol exist, only cval is
+// recomputed.  One lane per coarse row as in the fill pass above, but nothing is inserted or shifted: the row's sorted coarse columns
+// are loaded into LDS ([slot][lane]), an accumulator sits beside each, and an entry finds its slot by binary search in that short list.
+// Same sum order as galerkin_lds_kernel<…, FILL> — member rows in list order, entries in storage order, every entry added to its
+// column's accumulator in the order met — so the values are bit-identical to the fill pass's.  The accumulators start at −0.0:
+// −0.0 + v == v for every v (signed zeros included), which is the fill pass's "first entry is stored, later ones are added".
+// A row longer than CAP accumulates in its global segment.  An entry whose coarse column is not in the row (the pattern is not the
+// product's: cannot happen while the fine pattern is the one the hierarchy was built for) is counted in *miss.
+template <int CAP, int TBK>
+__global__ __launch_bounds__(TBK) void galerkin_numeric_kernel(int nc, const int *__restrict__ cptr, const int *__restrict__ members, const int *__restrict__ agg,
+                                                               const int *__restrict__ rowptr, const int *__restrict__ col, const double *__restrict__ val,
+                                                               const int *__restrict__ crowptr, const int *__restrict__ ccol, double *__restrict__ cval, int *__restrict__ miss) {
+  __shared__ int keys[CAP * TBK];
+  __shared__ double vals[CAP * TBK];
+  const int c = blockIdx.x * TBK + threadIdx.x, t = threadIdx.x;
+  if (c >= nc) return;
+  const int dst = crowptr[c], len = crowptr[c + 1] - dst;
+  const bool lds = len <= CAP;
+  if (lds) for (int q = 0; q < len; ++q) { keys[q * TBK + t] = ccol[dst + q]; vals[q * TBK + t] = -0.0; }
+  else for (int q = 0; q < len; ++q) cval[dst + q] = -0.0;
+  const int m0 = cptr ? cptr[c] : c, m1 = cptr ? cptr[c + 1] : c + 1;
+  int last_a = -1, last_pos = -1, missed = 0;      // neighbouring entries of a fine row often fall into one aggregate
+  constexpr int U = 8;      // entries fetched ahead of the searches: U independent col → agg gathers in flight per lane instead of one dependent chain
+  for (int m = m0; m < m1; ++m) {
+    const int i = cptr ? members[m] : m;
+    const int k1 = rowptr[i + 1];
+    for (int k0 = rowptr[i]; k0 < k1; k0 += U) {
+      int av[U]; double vv[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) { const bool in = k0 + u < k1; av[u] = in ? agg[col[k0 + u]] : -1; vv[u] = in ? val[k0 + u] : 0.0; }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {      // storage order, as the fill pass
+        const int a = av[u];
+        if (a < 0) continue;
+        int pos = last_pos;
+        if (a != last_a) {
+          pos = -1;
+          int lo = 0, hi = len - 1;
+          while (lo <= hi) {
+            const int mid = (lo + hi) >> 1;
+            const int key = lds ? keys[mid * TBK + t] : ccol[dst + mid];
+            if (key == a) { pos = mid; break; }
+            if (key < a) lo = mid + 1; else hi = mid - 1;
+          }
+          if (pos < 0) { ++missed; continue; }
+          last_a = a; last_pos = pos;
+        }
+        if (lds) vals[pos * TBK + t] += vv[u]; else cval[dst + pos] += vv[u];
+      }
+    }
+  }
+  if (lds) for (int q = 0; q < len; ++q) cval[dst + q] = vals[q * TBK + t];
+  if (missed) atomicAdd(miss, missed);
+}
+
 // ------------------------------------------------------------------ pairwise aggregation
 __device__ __forceinline__ double csr_lookup(const int *__restrict__ rowptr, const int *__restrict__ col, const double *__restrict__ val, int i, int j) {
   int lo = rowptr[i], hi = rowptr[i + 1] - 1;   // reference getElementMatrixCSR, MatrixAccess.cu:28-47
@@ -549,6 +604,24 @@ int k_build_ap(const mgs_csr *A, const mgs_xfer *T, const int *cmap_ext, int nco
     return galerkin_core(A, A->rows, nullptr, nullptr, T->agg, T->n_coarse, out);
   }
   return galerkin_core(A, A->rows, nullptr, nullptr, cmap_ext, ncols, out);
+}
+
+// New values of C = PᵀAP (cptr/members = the transfer's member lists) or of C = A·P (cptr == NULL: identity member lists) into C's
+// existing val array; C's pattern is the product's own (built by galerkin_core for the same A pattern and the same colmap).  One
+// launch on the context's stream: no count pass, no scan, no allocation, no host synchronisation.  The LDS slots per lane follow the
+// longest row of C, which is known exactly (mgs_plan_csr); *miss_dev counts entries that found no slot.
+int k_galerkin_numeric(const mgs_csr *A, int nc, const int *cptr, const int *members, const int *colmap, mgs_csr *C, int *miss_dev) {
+  mgs_ctx *ctx = A->ctx;
+  MGS_CHECK(ctx, C->rows == nc && (cptr || nc == A->rows), MGS_ERR_INVALID, "numeric galerkin: shape mismatch");
+  if (!nc || !C->nnz) return MGS_OK;
+  const int ml = C->max_row_len;
+#define GALN_(CAPV, TBV) hipLaunchKernelGGL((galerkin_numeric_kernel<CAPV, TBV>), dim3(mgs_grid(nc, TBV)), dim3(TBV), 0, ctx->stream, nc, cptr, members, colmap, \
+                                            A->rowptr, A->col, A->val, C->rowptr, C->col, C->val, miss_dev)
+  // (8 slots: A·P of a stencil operator has 5–7 entries per row — half the LDS of the 16-slot form, twice the resident waves)
+  if (ml <= 8) GALN_(8, 256); else if (ml <= 16) GALN_(16, 256); else if (ml <= 32) GALN_(32, 128); else GALN_(64, 64);
+#undef GALN_
+  MGS_HIP(ctx, hipGetLastError());
+  return MGS_OK;
 }
 
 // general P (not an aggregation): host Gustavson product, as the reference does with Eigen on
