@@ -188,9 +188,14 @@ int mgs_hier_push_P(mgs_hier *h, const mgs_csr *P);
  * (src/CPU_C++/main.cpp:155-182; benchmarks use 10 2 8, results.txt:22-24).           */
 int mgs_hier_coarsen(mgs_hier *h, double ktg, int npass, double tou, int coarse_rows,
                      int max_levels);
-/* factor the coarsest operator (dense inverse on device, ≤ 8192 rows); must be called once before
- * mgs_vcycle.  If coarsening stalled above that size (e.g. all rows in G0) the coarsest level is
- * smoothed by 8 damped-Jacobi sweeps instead.                                          */
+/* factor the coarsest operator (dense inverse on device, ≤ 8192 rows: Gauss-Jordan with partial
+ * pivoting); must be called once before mgs_vcycle.  If coarsening stalled above that size (e.g.
+ * all rows in G0) the coarsest level is smoothed by 8 damped-Jacobi sweeps instead.
+ * MGS_ERR_NUMERIC: the coarsest operator is singular to working precision — a pivot is not
+ * greater than 8·n·DBL_EPSILON·max|a_ij| (n its rows, a_ij its entries) — or holds a NaN or Inf.
+ * A one-level hierarchy (no mgs_hier_push_P / mgs_hier_coarsen) is this dense solve alone and
+ * is never smoothed: its operator may have zero or missing diagonal entries.  They are refused
+ * with MGS_ERR_NUMERIC as soon as a level is pushed below it or it is smoothed itself.      */
 int mgs_hier_finalize(mgs_hier *h);
 int mgs_hier_set_smoother(mgs_hier *h, double omega, int nu1, int nu2);
 /* Values changed, pattern did not (time stepping, Picard / Newton iterations, parameter sweeps): recomputes everything in h
@@ -211,7 +216,9 @@ int mgs_hier_set_smoother(mgs_hier *h, double omega, int nu1, int nu2);
  * Caveat: mgs_hier_coarsen with npass >= 2 builds A_c as the chained product P2ᵀ(P1ᵀAP1)P2, the refresh forms PᵀAP with the
  * composed P in one pass: the two agree to rounding, not bit for bit, so a refresh with unchanged values may move coarse
  * entries in their last bits.  When the aggregates have aged and a rebuild is due is the caller's decision.
- * MGS_ERR_NUMERIC: a missing or zero diagonal on any level, or a singular coarsest operator — the hierarchy is then left
+ * MGS_ERR_NUMERIC: a missing or zero diagonal on any level (not counted on a one-level hierarchy, see mgs_hier_finalize), or a
+ * coarsest operator that mgs_hier_finalize's singularity rule refuses (pivot not greater than 8·n·DBL_EPSILON·max|a_ij|, NaN,
+ * Inf) — the hierarchy is then left
  * un-finalized (cycles return MGS_ERR_STATE, cached graphs are dropped) until a later refresh succeeds.
  * MGS_ERR_STATE: before mgs_hier_finalize; entries of the fine operator fall outside the kept coarse patterns (its pattern is
  * not the one the hierarchy was built for).  MGS_ERR_INVALID: h NULL; a row-sharded hierarchy (halo columns, halo callbacks,

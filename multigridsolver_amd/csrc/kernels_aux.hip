@@ -2,6 +2,7 @@
 // on-device operator generators, halo pack.  gfx950 only.
 #include "mgs_internal.hpp"
 
+#include <cfloat>
 #include <chrono>
 #include <time.h>
 
@@ -641,7 +642,26 @@ __global__ void dense_scatter_kernel(int n, const int *__restrict__ rowptr, cons
   for (int k = rowptr[i]; k < rowptr[i + 1]; ++k) w[col[k]] += val[k];
   w[n + i] = 1.0;
 }
-__global__ __launch_bounds__(TB) void gj_pivot_kernel(int n, int k, const double *__restrict__ W, int *__restrict__ piv, double *__restrict__ pivval) {
+// max |a_ij| of the operator, as the bits of a non-negative double (they order like unsigned integers; a NaN sorts above +Inf and so wins):
+// the scale of the singularity test in gj_pivot_kernel
+__global__ __launch_bounds__(TB) void dense_absmax_kernel(int64_t nnz, const double *__restrict__ val, unsigned long long *__restrict__ amax_bits) {
+  unsigned long long m = 0ull;
+  const int64_t stride = (int64_t)gridDim.x * TB;
+  for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < nnz; i += stride) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(fabs(val[i]));
+    m = b > m ? b : m;
+  }
+  for (int off = 32; off > 0; off >>= 1) { const unsigned long long o = __shfl_down(m, off); m = o > m ? o : m; }
+  if ((threadIdx.x & 63) == 0) atomicMax(amax_bits, m);      // one atomic per wavefront
+}
+// Singularity rule: the operator is refused (piv[1] = 1) when a pivot is not greater than GJ_SINGULAR_FACTOR·n·DBL_EPSILON·max|a_ij|.
+// Written as !(|pivot| > threshold) so that a NaN pivot and a NaN or Inf scale are refused as well.  Basis of the constant (NumPy model
+// of this algorithm, FP64): singular weighted graph Laplacians of n = 4..500 end with a pivot <= 0.31·n·eps·max|a|; regular matrices of
+// cond 1e12 keep every pivot >= 4.8e3·n·eps·max|a|, cond 1e10 >= 5.9e5, the Dirichlet Laplacian >= 5e12.  8 sits 25x above the first
+// group and 600x below the second.
+constexpr double GJ_SINGULAR_FACTOR = 8.0;
+__global__ __launch_bounds__(TB) void gj_pivot_kernel(int n, int k, const double *__restrict__ W, int *__restrict__ piv, double *__restrict__ pivval,
+                                                      const unsigned long long *__restrict__ amax_bits) {
   __shared__ double bv[TB]; __shared__ int bi[TB];
   double best = -1.0; int idx = k;
   for (int i = k + threadIdx.x; i < n; i += TB) {
@@ -657,7 +677,10 @@ __global__ __launch_bounds__(TB) void gj_pivot_kernel(int n, int k, const double
     }
     __syncthreads();
   }
-  if (threadIdx.x == 0) { piv[0] = bi[0]; if (bv[0] == 0.0) piv[1] = 1; pivval[0] = W[(size_t)bi[0] * 2 * n + k]; }
+  if (threadIdx.x == 0) {
+    const double thr = GJ_SINGULAR_FACTOR * (double)n * DBL_EPSILON * __longlong_as_double((long long)amax_bits[0]);
+    piv[0] = bi[0]; if (!(bv[0] > thr)) piv[1] = 1; pivval[0] = W[(size_t)bi[0] * 2 * n + k];
+  }
 }
 __global__ void gj_swap_scale_kernel(int n, int k, double *__restrict__ W, const int *__restrict__ piv, const double *__restrict__ pivval) {
   int j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1189,32 +1212,48 @@ int k_dense_gemv(mgs_ctx *ctx, int n, const double *M, const double *b, double *
 }
 
 // *inv_out == NULL: the n·n result is allocated here (and released again on failure); else it is written into the caller's buffer
-// (mgs_hier_refresh: the cached graphs hold that pointer), which stays the caller's whatever happens
+// (mgs_hier_refresh: the cached graphs hold that pointer), which stays the caller's whatever happens.  MGS_ERR_NUMERIC: a pivot not
+// greater than 8·n·DBL_EPSILON·max|a_ij| (see gj_pivot_kernel), which also refuses NaN and Inf among the values.  The work buffers are
+// released on every exit.
 int k_dense_inverse(mgs_ctx *ctx, const mgs_csr *A, double **inv_out) {
   const int n = A->rows;
   double *const into = *inv_out;
   MGS_CHECK(ctx, A->cols == n, MGS_ERR_INVALID, "coarsest operator is not square (%d x %d)", A->rows, A->cols);
-  double *W = nullptr, *colk = nullptr, *inv = nullptr; int *piv = nullptr;
-  MGS_TRY(mgs_dev_alloc(ctx, &W, (size_t)n * 2 * n));
-  MGS_TRY(mgs_dev_alloc(ctx, &colk, (size_t)n + 1));
-  if (into) inv = into; else MGS_TRY(mgs_dev_alloc(ctx, &inv, (size_t)n * n));
-  MGS_TRY(mgs_dev_alloc(ctx, &piv, 2));
+  double *W = nullptr, *colk = nullptr, *inv = into; int *piv = nullptr;
+  unsigned long long *amax = nullptr;
   hipStream_t s = ctx->stream;
-  MGS_HIP(ctx, hipMemsetAsync(W, 0, sizeof(double) * (size_t)n * 2 * n, s));
-  MGS_HIP(ctx, hipMemsetAsync(piv, 0, 2 * sizeof(int), s));
-  if (n) hipLaunchKernelGGL(dense_scatter_kernel, dim3(mgs_grid(n, TB)), dim3(TB), 0, s, n, A->rowptr, A->col, A->val, W);
-  for (int k = 0; k < n; ++k) {
-    hipLaunchKernelGGL(gj_pivot_kernel, dim3(1), dim3(TB), 0, s, n, k, W, piv, colk + n);
-    hipLaunchKernelGGL(gj_swap_scale_kernel, dim3(mgs_grid(2 * n, TB)), dim3(TB), 0, s, n, k, W, piv, colk + n);
-    hipLaunchKernelGGL(gj_colsave_kernel, dim3(mgs_grid(n, TB)), dim3(TB), 0, s, n, k, W, colk);
-    hipLaunchKernelGGL(gj_eliminate_kernel, dim3(mgs_grid(2 * n, TB), n), dim3(TB), 0, s, n, k, W, colk);
-  }
-  if (n) hipLaunchKernelGGL(gj_extract_kernel, dim3(mgs_grid(n, TB), n), dim3(TB), 0, s, n, W, inv);
   int h[2] = {0, 0};
-  MGS_HIP(ctx, hipMemcpyAsync(h, piv, sizeof h, hipMemcpyDeviceToHost, s));
-  MGS_HIP(ctx, hipStreamSynchronize(s));
-  MGS_HIP(ctx, mgs_hip_free(W)); MGS_HIP(ctx, mgs_hip_free(colk)); MGS_HIP(ctx, mgs_hip_free(piv));
-  if (h[1]) { if (!into) mgs_hip_free(inv); return mgs_fail(ctx, MGS_ERR_NUMERIC, "coarsest operator (%d rows) is singular", n); }
+  auto run = [&]() -> int {
+    MGS_TRY(mgs_dev_alloc(ctx, &W, (size_t)n * 2 * n));
+    MGS_TRY(mgs_dev_alloc(ctx, &colk, (size_t)n + 1));
+    if (!into) MGS_TRY(mgs_dev_alloc(ctx, &inv, (size_t)n * n));
+    MGS_TRY(mgs_dev_alloc(ctx, &piv, 2));
+    MGS_TRY(mgs_dev_alloc(ctx, &amax, 1));
+    MGS_HIP(ctx, hipMemsetAsync(W, 0, sizeof(double) * (size_t)n * 2 * n, s));
+    MGS_HIP(ctx, hipMemsetAsync(piv, 0, 2 * sizeof(int), s));
+    MGS_HIP(ctx, hipMemsetAsync(amax, 0, sizeof(unsigned long long), s));
+    if (A->nnz) hipLaunchKernelGGL(dense_absmax_kernel, dim3(grid_cap(A->nnz, ctx->n_cu)), dim3(TB), 0, s, (int64_t)A->nnz, A->val, amax);
+    if (n) hipLaunchKernelGGL(dense_scatter_kernel, dim3(mgs_grid(n, TB)), dim3(TB), 0, s, n, A->rowptr, A->col, A->val, W);
+    for (int k = 0; k < n; ++k) {
+      hipLaunchKernelGGL(gj_pivot_kernel, dim3(1), dim3(TB), 0, s, n, k, W, piv, colk + n, amax);
+      hipLaunchKernelGGL(gj_swap_scale_kernel, dim3(mgs_grid(2 * n, TB)), dim3(TB), 0, s, n, k, W, piv, colk + n);
+      hipLaunchKernelGGL(gj_colsave_kernel, dim3(mgs_grid(n, TB)), dim3(TB), 0, s, n, k, W, colk);
+      hipLaunchKernelGGL(gj_eliminate_kernel, dim3(mgs_grid(2 * n, TB), n), dim3(TB), 0, s, n, k, W, colk);
+    }
+    if (n) hipLaunchKernelGGL(gj_extract_kernel, dim3(mgs_grid(n, TB), n), dim3(TB), 0, s, n, W, inv);
+    MGS_HIP(ctx, hipGetLastError());
+    MGS_HIP(ctx, hipMemcpyAsync(h, piv, sizeof h, hipMemcpyDeviceToHost, s));
+    MGS_HIP(ctx, hipStreamSynchronize(s));
+    return MGS_OK;
+  };
+  int rc = run();
+  if (rc != MGS_OK) hipStreamSynchronize(s);      // nothing enqueued above may still touch the buffers released below
+  if (W) mgs_hip_free(W);
+  if (colk) mgs_hip_free(colk);
+  if (piv) mgs_hip_free(piv);
+  if (amax) mgs_hip_free(amax);
+  if (rc == MGS_OK && h[1]) rc = mgs_fail(ctx, MGS_ERR_NUMERIC, "coarsest operator (%d rows) is singular to working precision, or holds NaN/Inf", n);
+  if (rc != MGS_OK) { if (!into && inv) mgs_hip_free(inv); return rc; }
   *inv_out = inv;
   return MGS_OK;
 }

@@ -537,14 +537,22 @@ extern "C" int mgs_prolong_add(const mgs_xfer *T, const mgs_vec *ec, mgs_vec *x)
 }
 
 // ------------------------------------------------------------------ hierarchy
-static int level_init(mgs_hier *h, mgs_level &L, const mgs_csr *A, bool own) {
+// bad_out != NULL (the finest level, mgs_hier_create): rows with a missing or zero diagonal are counted there instead of refused — a
+// level that is never smoothed (one-level hierarchy: the dense solve alone, which pivots) does not need D⁻¹; see diag0_needed
+static int level_init(mgs_hier *h, mgs_level &L, const mgs_csr *A, bool own, int *bad_out = nullptr) {
   mgs_ctx *ctx = h->ctx;
   L.A = A; L.own_A = own; L.n = A->rows; L.n_ext = A->cols > A->rows ? A->cols : A->rows;
   MGS_TRY(mgs_vec_create(ctx, L.n_ext, &L.dinv));      // row shards: the halo part receives the owners' values once (prepare_fused)
   MGS_TRY(mgs_vec_create(ctx, L.n_ext, &L.r));
   MGS_TRY(mgs_vec_create(ctx, L.n_ext, &L.tmp));
   MGS_TRY(mgs_vec_create(ctx, L.n_ext, &L.b)); MGS_TRY(mgs_vec_create(ctx, L.n_ext, &L.x));
+  if (bad_out) return k_diag_inv(A, L.dinv->d, bad_out);
   return mgs_diag_inv(A, L.dinv);
+}
+// the finest level is about to be smoothed (a level below it, or the smoothed coarsest form): its diagonal must be complete
+static int diag0_needed(mgs_hier *h, const char *who) {
+  MGS_CHECK(h->ctx, h->bad_diag0 == 0, MGS_ERR_NUMERIC, "%s: %d rows of the fine operator have a missing or zero diagonal", who, h->bad_diag0);
+  return MGS_OK;
 }
 static void level_free(mgs_level &L) {
   if (L.own_A && L.A) mgs_csr_destroy(const_cast<mgs_csr *>(L.A));
@@ -612,7 +620,7 @@ int mgs_hier_create(mgs_ctx *ctx, const mgs_csr *A, double omega, int nu1, int n
   mgs_hier *h = new mgs_hier();
   h->ctx = ctx; h->omega = omega; h->nu1 = nu1; h->nu2 = nu2;
   h->lev.emplace_back();
-  int rc = level_init(h, h->lev.back(), A, false);
+  int rc = level_init(h, h->lev.back(), A, false, &h->bad_diag0);
   if (rc != MGS_OK) { mgs_hier_destroy(h); return rc; }
   *out = h;
   return MGS_OK;
@@ -859,6 +867,7 @@ int mgs_hier_push_P(mgs_hier *h, const mgs_csr *P) {
   MGS_CHECK(ctx, A->rows == A->cols, MGS_ERR_STATE, "mgs_hier_push_P: sharded operators take their hierarchy from mgs_hier_coarsen");
   MGS_CHECK(ctx, P->rows == A->rows, MGS_ERR_INVALID, "mgs_hier_push_P: P has %d rows, coarsest operator has %d", P->rows, A->rows);
   MGS_CHECK(ctx, P->cols > 0, MGS_ERR_INVALID, "mgs_hier_push_P: P has no columns");
+  MGS_TRY(diag0_needed(h, "mgs_hier_push_P"));
   mgs_xfer *T = nullptr; mgs_csr *Ac = nullptr;
   MGS_TRY(k_xfer_from_csr(P, &T));
   int rc = mgs_csr_galerkin(A, T, &Ac);
@@ -907,6 +916,7 @@ int mgs_galerkin_shard(const mgs_csr *A, const mgs_xfer *T, const int *halo_coar
 int mgs_hier_push_level(mgs_hier *h, mgs_xfer *T, mgs_csr *Ac) {
   mgs_ctx *ctx = h->ctx;
   MGS_CHECK(ctx, T && Ac && T->n_fine == h->lev.back().A->rows && T->n_coarse == Ac->rows && Ac->rows <= Ac->cols, MGS_ERR_INVALID, "mgs_hier_push_level: shape mismatch");
+  MGS_TRY(diag0_needed(h, "mgs_hier_push_level"));
   return push_level(h, T, Ac);
 }
 int mgs_xfer_from_agg(mgs_ctx *ctx, int n_fine, int n_coarse, const int *agg, mgs_xfer **out) { return k_xfer_from_agg_host(ctx, n_fine, n_coarse, agg, out); }
@@ -917,6 +927,7 @@ int mgs_hier_coarsen(mgs_hier *h, double ktg, int npass, double tou, int coarse_
   while ((int)h->lev.size() < max_levels && h->lev.back().A->rows > coarse_rows) {
     const mgs_csr *A = h->lev.back().A;
     MGS_CHECK(ctx, A->rows == A->cols, MGS_ERR_STATE, "mgs_hier_coarsen: operator is not square");
+    MGS_TRY(diag0_needed(h, "mgs_hier_coarsen"));
     mgs_xfer *T = nullptr; mgs_csr *Ac = nullptr;
     MGS_TRY(k_pairwise_aggregate(A, ktg, npass, tou, &T, &Ac));
     if (Ac->rows == 0 || Ac->rows > (int)(0.9 * A->rows)) {  // coarsening stalled (or everything in G0)
@@ -940,6 +951,7 @@ int mgs_hier_finalize(mgs_hier *h) {
     // Coarsening stopped far above the dense limit (e.g. every row is in G0: the operator is so diagonally
     // dominant that Jacobi alone converges, AGMG.cpp:118-123).  The coarsest level is then smoothed
     // (8 damped-Jacobi sweeps from 0) instead of solved; the cycle stays a fixed linear operator.
+    if (h->lev.size() == 1) MGS_TRY(diag0_needed(h, "mgs_hier_finalize (smoothed coarsest level)"));
     h->coarse_sweeps = 8;
     h->finalized = true; drop_graph(h);
     return MGS_OK;
@@ -990,6 +1002,7 @@ int mgs_hier_refresh(mgs_hier *h) {
   if (rc == MGS_OK && hipMemcpyAsync(flags, h->refresh_flags, sizeof flags, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = mgs_fail(ctx, MGS_ERR_HIP, "mgs_hier_refresh: flag copy failed");
   if (rc == MGS_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = mgs_fail(ctx, MGS_ERR_HIP, "mgs_hier_refresh: %s", hipGetErrorString(hipGetLastError()));
   if (rc == MGS_OK && flags[1]) rc = mgs_fail(ctx, MGS_ERR_STATE, "mgs_hier_refresh: %d entries fall outside the kept coarse patterns (the fine pattern is not the one the hierarchy was built for)", flags[1]);
+  if (rc == MGS_OK && nl == 1 && !h->coarse_sweeps) { h->bad_diag0 = flags[0]; flags[0] = 0; }   // one level, solved densely: D⁻¹ is not used (mgs_hier_create)
   if (rc == MGS_OK && flags[0]) rc = mgs_fail(ctx, MGS_ERR_NUMERIC, "mgs_hier_refresh: %d rows of the refreshed operators have a missing or zero diagonal", flags[0]);
   if (rc == MGS_OK && !h->coarse_sweeps) {      // coarsest dense inverse, into the buffer the cached graphs know
     if (!h->inv) { kept = false; drop_graph(h); }

@@ -246,6 +246,7 @@ struct mgs_hier {
   double omega = 0.5;
   int nu1 = 1, nu2 = 1;
   bool finalized = false;
+  int bad_diag0 = 0;       // rows of the finest operator with a missing or zero diagonal: refused as soon as that level would be smoothed
   int kcycle_levels = 0;   // levels 1..kcycle_levels solve their coarse problem with 2 GCR steps (K-cycle)
   bool kcycle_entry = false;   // ... and so does level 0 when the hierarchy is entered from x = 0 (replicated tail of a row-sharded hierarchy whose
                                // K-cycle reaches the last sharded level: that level IS the tail's level 0)
