@@ -467,6 +467,11 @@ int mgs_csr_rowcode_info(const mgs_csr *A, int64_t out[4]);
  * level runs the separate pre pass + restriction kernels), out[1] groups made of two row blocks, out[2] stray aggregates (restricted by
  * the trailing kernel), out[3] row blocks. */
 int mgs_hier_group_info(const mgs_hier *h, int level, int64_t out[4]);
+/* The grouped pre pass of level `level` alone, into the caller's vectors (tests and diagnostics; unsharded levels that mgs_hier_group_info
+ * reports as grouped): t = b + r and rc = Pᵀr with r = b − Â·b, Â = A·diag(ωD⁻¹); r receives the residual of the rows whose aggregate
+ * leaves its row-block group (other entries are not written).  *nodiag (may be NULL): 1 if the pass ran on the operand without Â's
+ * diagonal entries (option "pre_nodiag": coded row blocks stream val_nd and a byte per row; the result has the same bits either way).  Enqueued on the context's stream. */
+int mgs_hier_pre_pass(mgs_hier *h, int level, const mgs_vec *b, mgs_vec *t, mgs_vec *r, mgs_vec *rc, int *nodiag);
 /* hipGraph state of the cycle (diagnostics): out[0] captured cycles cached, out[1] = 1 on the native RCCL transport, out[2] = 1 if
  * capturing the native cycle failed (eager launches since), out[3] eager native cycles run before the first capture.
  * Option "native_graph" (default 1): capture the row-sharded cycle including its RCCL exchanges (two eager cycles first).
@@ -485,7 +490,9 @@ int mgs_hier_graph_info(const mgs_hier *h, int64_t out[4]);
  * overlaps its halo exchange with interior row blocks, default 400000), "fuse_operands" (setup-time operands of the fused cycle passes,
  * +12 B of HBM per matrix entry; default 1), "merge_ap" (fused post pass on A·P with the entries of one aggregate summed at setup instead of A with
  * aggregate-mapped columns; default 1; equal to rounding, not bit for bit), "fuse_restrict" / "group_blocks" / "group_stray_pct" / "group_min_blocks" / "group_strip"
- * (grouped pre pass: restriction inside the pre-smoothing pass, see mgs_hier_group_info), "diag_from_values", "fuse_dots", "lds_pad", "blkptr".
+ * (grouped pre pass: restriction inside the pre-smoothing pass, see mgs_hier_group_info), "pre_nodiag" (the grouped pre pass of an unsharded FP64 level whose rows
+ * hold exactly one diagonal entry streams Â's diagonal entry — ω up to three roundings for every row — as one byte, its distance from ω in units of the last place: 7 B per row less, +8 B of HBM per
+ * off-diagonal entry and 1 B per row; default 1, the same bits as with 0), "diag_from_values", "fuse_dots", "lds_pad", "blkptr".
  * Unknown key: MGS_ERR_INVALID. */
 int mgs_ctx_set_option(mgs_ctx *ctx, const char *key, int value);
 

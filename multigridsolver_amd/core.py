@@ -395,6 +395,11 @@ class Hierarchy:
         out = (C.c_int64 * 4)(); check(lib().mgs_hier_group_info(self.h, level, out), self.ctx.h)
         return dict(zip(["groups", "paired_groups", "stray_aggregates", "blocks"], [int(v) for v in out]))
 
+    def pre_pass(self, level, b, t, r, rc):
+        """the grouped pre pass of one level alone (mgs_hier_pre_pass); returns True if it ran without Â's streamed diagonal"""
+        nd = C.c_int(0); check(lib().mgs_hier_pre_pass(self.h, level, b.h, t.h, r.h, rc.h, C.byref(nd)), self.ctx.h)
+        return bool(nd.value)
+
     def graph_info(self):
         out = (C.c_int64 * 4)(); check(lib().mgs_hier_graph_info(self.h, out), self.ctx.h)
         return dict(zip(["captured_cycles", "native_transport", "native_capture_failed", "native_eager_runs"], [int(v) for v in out]))

@@ -221,6 +221,31 @@ __global__ void scale_vals_kernel(int64_t nnz, const int *__restrict__ col, cons
   const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (k < nnz) out[k] = val[k] * wd[col[k]];
 }
+// Compact operand of the grouped pre pass (option pre_nodiag): Â's values in storage order without each row's diagonal entry.  Every row
+// holds exactly one (diag_count_kernel), so row i's remaining entries start at rowptr[i] − i.  The diagonal entry itself is ω up to a few
+// units of the last place; code[i] keeps its distance from omega, counted on the bit patterns (consecutive doubles of one sign are consecutive
+// integers), so that the kernel rebuilds the stored entry exactly.  Rows whose entry lies further away than a byte holds are counted in *bad.
+__global__ void diag_count_kernel(int n, const int *__restrict__ rowptr, const int *__restrict__ col, int *__restrict__ bad) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  int cnt = 0;
+  for (int k = rowptr[i]; k < rowptr[i + 1]; ++k) cnt += col[k] == i;
+  if (cnt != 1) atomicAdd(bad, 1);
+}
+__global__ void drop_diag_vals_kernel(int n, const int *__restrict__ rowptr, const int *__restrict__ col, const double *__restrict__ val, double omega,
+                                      double *__restrict__ out, signed char *__restrict__ code, int *__restrict__ bad) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int a = rowptr[i], e = rowptr[i + 1];
+  int o = a - i;
+  long long d = 0;
+  for (int k = a; k < e; ++k) {
+    if (col[k] != i) out[o++] = val[k];
+    else d = (long long)((unsigned long long)__double_as_longlong(val[k]) - (unsigned long long)__double_as_longlong(omega));
+  }
+  if (d < -127 || d > 127) { atomicAdd(bad, 1); d = 0; }
+  code[i] = (signed char)d;
+}
 __global__ void map_cols_kernel(int n, const int *__restrict__ rowptr, const int *__restrict__ col, const int *__restrict__ cmap, int *__restrict__ out) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -927,6 +952,22 @@ int k_round_vals(mgs_ctx *ctx, const double *in, float *out, int64_t n) {
 }
 int k_scale_vals(mgs_ctx *ctx, const mgs_csr *A, const double *wd, double *out) {
   if (A->nnz) hipLaunchKernelGGL(scale_vals_kernel, dim3(mgs_grid(A->nnz, TB)), dim3(TB), 0, ctx->stream, A->nnz, A->col, A->val, wd, out);
+  MGS_HIP(ctx, hipGetLastError());
+  return MGS_OK;
+}
+int k_diag_count(const mgs_csr *A, int *bad_count_host) {
+  mgs_ctx *ctx = A->ctx;
+  int *bad = nullptr;
+  MGS_TRY(mgs_dev_alloc(ctx, &bad, 1));
+  MGS_HIP(ctx, hipMemsetAsync(bad, 0, sizeof(int), ctx->stream));
+  if (A->rows) hipLaunchKernelGGL(diag_count_kernel, dim3(mgs_grid(A->rows, TB)), dim3(TB), 0, ctx->stream, A->rows, A->rowptr, A->col, bad);
+  MGS_HIP(ctx, hipMemcpyAsync(bad_count_host, bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  MGS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  MGS_HIP(ctx, mgs_hip_free(bad));
+  return MGS_OK;
+}
+int k_drop_diag_vals(mgs_ctx *ctx, const mgs_csr *A, const double *val, double omega, double *out, signed char *code, int *bad_dev) {
+  if (A->rows) hipLaunchKernelGGL(drop_diag_vals_kernel, dim3(mgs_grid(A->rows, TB)), dim3(TB), 0, ctx->stream, A->rows, A->rowptr, A->col, val, omega, out, code, bad_dev);
   MGS_HIP(ctx, hipGetLastError());
   return MGS_OK;
 }

@@ -928,19 +928,26 @@ __global__ void restrict_stray_kernel(int ns, const int *__restrict__ stray, con
 // unstaged walk — block-uniform choices), then the in-LDS restriction of the group's aggregates
 // (six waves per SIMD: the halo variants of U = 7 / 8 came out at 82 / 89 registers — one wave less than the 80 of the others — and ran 6 % behind
 // their share on a row shard)
-template <int U, bool HALO, class VT = double>
+// ND (option pre_nodiag; unsharded FP64 levels whose rows hold exactly one diagonal entry): Â's diagonal entry is fl(a_ii·fl(ω·fl(1/a_ii))), ω up to
+// three roundings whatever the coefficients, so it is not streamed as a double.  A coded + staged block stages its slice of val_nd (Â's values
+// without the diagonal entries: row i from rowptr[i] − i, block blk from lo − r0 to hi − r1) and walks the pattern as before; at the offset 0 the
+// value is rebuilt from omega and the row's byte of nd_code (the distance of the stored entry from omega in units of the last place, taken on
+// the bit patterns) and multiplies b_i — no LDS value, no gather — and behind it the value index is the pattern position minus one.  The rebuilt
+// value IS the stored one, so the sum keeps its bits; the other branches read val as they always did.
+template <int U, bool HALO, class VT = double, bool ND = false>
 __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(6))) void csr_group_pre_kernel(
     int n, const int *__restrict__ rowptr, const int *__restrict__ idx, const VT *__restrict__ val,
     const unsigned char *__restrict__ pid, const int *__restrict__ tptr, const int *__restrict__ tab,
     const double *__restrict__ x, const double *__restrict__ b, double *__restrict__ t_out, double *__restrict__ r_out,
     double *__restrict__ rc_out, const int *__restrict__ gdesc, const unsigned long long *__restrict__ acode,
     const unsigned *__restrict__ wmask, int capv, int capi, BlockMap bm, const double *__restrict__ hv, int split, int nts /*bit 0: streaming store of t; bit 1: slice staged by LDS-DMA, no loop; bit 2: option rowptr_scan*/,
-    const int *__restrict__ gorder, int gper) {
+    const int *__restrict__ gorder, int gper, const double *__restrict__ val_nd, const signed char *__restrict__ nd_code, double omega) {
   extern __shared__ double lds_raw[];
   constexpr int VA = val_traits<VT>::VA;
   typedef typename val_traits<VT>::v16 v16_t;
   typedef typename val_traits<VT>::i16 i16_t;
   static_assert(sizeof(VT) == 8 || !HALO, "float values: unsharded levels only");
+  static_assert(!ND || (sizeof(VT) == 8 && !HALO), "no streamed diagonal: unsharded FP64 levels only");
   int g;
   if (gorder) {        // option group_order: workgroup (xcd, idx) → group, in the order of the one-block kernels' plane sweep
     const int idx = blockIdx.x >> 3;
@@ -975,15 +982,19 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(6))) void cs
     double bi = 0.0;
     unsigned wm = 0u;
     int mypid = 0;                                                        // loaded with the other per-row loads, not behind the barrier
+    int dc = 0;                                                           // ND: the row's diagonal entry of Â, as its distance from omega
     const bool scan = coded && staged && (nts & 4);                       // block-uniform (coded_row_range)
     int wave_first = 0;
     if (scan) wave_first = rowptr[min(r0 + (tid & ~63), n)];
-    if (row < r1) { if (!scan) { ga = rowptr[row]; ge = rowptr[row + 1]; } bi = b[row]; wm = wmask[row >> 5]; if (coded) mypid = pid[row]; }
+    if (row < r1) { if (!scan) { ga = rowptr[row]; ge = rowptr[row + 1]; } bi = b[row]; wm = wmask[row >> 5]; if (coded) mypid = pid[row]; if (ND && coded) dc = nd_code[row]; }
     double s = 0.0;
+    // ND, coded block: its slice of val_nd (256 entries less; r1 − r0 less in the last block)
+    const int nd_start = (lo - r0) & ~1, nd_nent = (hi - r1) - nd_start;
     if (staged) {
-      const int nch = (nent + VA - 1) >> (VA == 4 ? 2 : 1);      // 16-byte pieces of the value slice
+      const int nch = (ND && coded) ? (nd_nent + 1) >> 1 : (nent + VA - 1) >> (VA == 4 ? 2 : 1);      // 16-byte pieces of the value slice
       if (coded && nch <= 4 * RB && (nts & 2)) {          // no loop and no staging registers in front of the barrier (see coded_block_body)
-        stage_pairs_dma(val + start, vals, nch, tid);
+        if (ND) stage_pairs_dma(val_nd + nd_start, reinterpret_cast<double *>(vals), nch, tid);
+        else stage_pairs_dma(val + start, vals, nch, tid);
         int tw = 0;
         if (tid < tlen) tw = tab[t0 + tid];
         if (tid < tlen) ints[tid] = tw;
@@ -992,8 +1003,9 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(6))) void cs
         // wave drains its own before it arrives (spelled out; the compiler happens to place the same wait in front of s_barrier today)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       } else if (coded) {
+        const VT *__restrict__ src = ND ? reinterpret_cast<const VT *>(val_nd) + nd_start : val + start;
 #pragma unroll 4
-        for (int c = tid; c < nch; c += RB) *reinterpret_cast<v16_t *>(vals + VA * c) = *reinterpret_cast<const v16_t *>(val + start + VA * c);
+        for (int c = tid; c < nch; c += RB) *reinterpret_cast<v16_t *>(vals + VA * c) = *reinterpret_cast<const v16_t *>(src + VA * c);
         for (int c = tid; c < tlen; c += RB) ints[c] = tab[t0 + c];
       } else {
 #pragma unroll 4
@@ -1007,7 +1019,26 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(6))) void cs
       if (scan) coded_row_range(ints, 0, tlen, mypid, row < r1, wave_first, ga, ge);
       if (row < r1 && ge > ga) {
         const int my_a = ga - start, my_e = ge - start, lim = nent - 1;
-        if (coded) {
+        if (ND && coded) {
+          const int ps = ints[mypid];
+          const int last = ge - ga - 1;
+          const int na = ga - row - nd_start, nlim = max(nd_nent - 1, 0);      // the row's first off-diagonal value in the staged slice
+          int behind = 0;                                                       // 1 once the walk has passed the diagonal
+          const double om = __longlong_as_double(__double_as_longlong(omega) + (long long)dc);      // Â_ii as val holds it
+          for (int k = ga, j = 0; k < ge; k += U, j += U) {
+            int oq[U], bq[U]; double xv[U], vq[U];
+#pragma unroll
+            for (int q = 0; q < U; ++q) oq[q] = ints[ps + min(j + q, last)];
+#pragma unroll
+            for (int q = 0; q < U; ++q) { bq[q] = behind; if (oq[q] == 0) behind = 1; }
+#pragma unroll
+            for (int q = 0; q < U; ++q) xv[q] = oq[q] == 0 ? bi : x[row + oq[q]];
+#pragma unroll
+            for (int q = 0; q < U; ++q) { const double v = reinterpret_cast<const double *>(vals)[min(na + j + q - bq[q], nlim)]; vq[q] = oq[q] == 0 ? om : v; }
+#pragma unroll
+            for (int q = 0; q < U; ++q) s += (k + q < ge) ? vq[q] * xv[q] : 0.0;
+          }
+        } else if (coded) {
           const int ps = ints[mypid];
           const int last = my_e - my_a - 1;
           for (int k = my_a, j = 0; k < my_e; k += U, j += U) {
@@ -1674,12 +1705,13 @@ int mgs_build_groups(mgs_ctx *ctx, const mgs_csr *A, const mgs_xfer *T, mgs_grou
 }
 
 int mgs_launch_group_pre(const mgs_csr *A, const mgs_groups *G, const mgs_xfer *T, const double *x, const double *b,
-                         double *t_out, double *r_out, double *rc_out, const double *hv, int split) {
+                         double *t_out, double *r_out, double *rc_out, const double *hv, int split, const double *val_nd, const signed char *nd_code, double omega) {
   mgs_ctx *ctx = A->ctx;
   if (A->rows == 0 || G->ngroups == 0) return MGS_OK;
   const mgs_rowcode *c = (use_rowcode(A, A->code, hv != nullptr) && !A->code->vtab) ? A->code : nullptr;
   const bool f32 = A->val32 != nullptr;      // FP32 level: the float form (unsharded levels only, the caller sees to that)
   if (f32 && hv) return mgs_fail(ctx, MGS_ERR_INVALID, "grouped pre pass: FP32 operand values on a row shard");
+  if (val_nd && (f32 || hv || !nd_code)) return mgs_fail(ctx, MGS_ERR_INVALID, "grouped pre pass: the operand without diagonal serves unsharded FP64 levels only");
   const int capv = f32 ? capv_f32(A) : A->lds_cap;
   const bool lean = c && (double)c->coded_blocks >= 0.985 * c->nblocks;
   const int capi = f32 ? capi_f32(c, capv) : (lean ? std::max(c->tab_cap, 64) : std::max(c ? c->tab_cap : 0, capv + 2));
@@ -1695,15 +1727,17 @@ int mgs_launch_group_pre(const mgs_csr *A, const mgs_groups *G, const mgs_xfer *
 #define G2_(UU, H) hipLaunchKernelGGL((csr_group2_pre_kernel<UU, H>), grid, dim3(2 * RB), lds2, ctx->stream, A->rows, A->rowptr, A->col, A->val, \
                                       c ? c->pid : nullptr, c ? c->tptr : nullptr, c ? c->tab : nullptr, x, b, t_out, r_out, rc_out, G->gdesc, \
                                       G->acode, G->wmask, capv, capi, bm, hv, hv ? split : 0x7fffffff)
-#define G_(UU, H) hipLaunchKernelGGL((csr_group_pre_kernel<UU, H>), grid, dim3(RB), lds, ctx->stream, A->rows, A->rowptr, A->col, A->val, \
+#define G_(UU, H, N) hipLaunchKernelGGL((csr_group_pre_kernel<UU, H, double, N>), grid, dim3(RB), lds, ctx->stream, A->rows, A->rowptr, A->col, A->val, \
                                      c ? c->pid : nullptr, c ? c->tptr : nullptr, c ? c->tab : nullptr, x, b, t_out, r_out, rc_out, G->gdesc, \
                                      G->acode, G->wmask, capv, capi, bm, hv, hv ? split : 0x7fffffff, ((ctx->opt_nt_store > 0 && A->rows >= ctx->opt_nt_store) ? 1 : 0) | (ctx->opt_stage_unroll ? 2 : 0) | (ctx->opt_rowptr_scan ? 4 : 0), \
-                                     ordered ? G->gorder : nullptr, G->gorder_per_xcd)
+                                     ordered ? G->gorder : nullptr, G->gorder_per_xcd, val_nd, nd_code, omega)
 #define GF_(UU) hipLaunchKernelGGL((csr_group_pre_kernel<UU, false, float>), grid, dim3(RB), lds, ctx->stream, A->rows, A->rowptr, A->col, A->val32, \
                                    c ? c->pid : nullptr, c ? c->tptr : nullptr, c ? c->tab : nullptr, x, b, t_out, r_out, rc_out, G->gdesc, \
                                    G->acode, G->wmask, capv, capi, bm, nullptr, 0x7fffffff, ((ctx->opt_nt_store > 0 && A->rows >= ctx->opt_nt_store) ? 1 : 0) | (ctx->opt_stage_unroll ? 2 : 0) | (ctx->opt_rowptr_scan ? 4 : 0), \
-                                   ordered ? G->gorder : nullptr, G->gorder_per_xcd)
-#define GU_(UU) do { if (f32) GF_(UU); else if (pairs) { if (hv) G2_(UU, true); else G2_(UU, false); } else { if (hv) G_(UU, true); else G_(UU, false); } } while (0)
+                                   ordered ? G->gorder : nullptr, G->gorder_per_xcd, nullptr, nullptr, 0.0)
+#define GU_(UU) do { if (f32) GF_(UU); \
+                     else if (pairs) { if (hv) G2_(UU, true); else G2_(UU, false); } \
+                     else { if (hv) G_(UU, true, false); else if (val_nd) G_(UU, false, true); else G_(UU, false, false); } } while (0)
   if (u == 4) GU_(4); else if (u == 7) GU_(7); else GU_(8);
 #undef GU_
 #undef GF_

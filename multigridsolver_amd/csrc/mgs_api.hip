@@ -269,6 +269,7 @@ int mgs_ctx_set_option(mgs_ctx *ctx, const char *key, int value) {
   else if (k == "blas1_pairs") ctx->opt_blas1_pairs = value;
   else if (k == "stage_unroll") ctx->opt_stage_unroll = value;
   else if (k == "rowptr_scan") ctx->opt_rowptr_scan = value;
+  else if (k == "pre_nodiag") ctx->opt_pre_nodiag = value;
   else if (k == "kcycle_energy") ctx->opt_kcycle_energy = value;
   else if (k == "aggpre_max_rows") ctx->opt_aggpre_max_rows = value;
   else if (k == "emu_split_self") ctx->opt_emu_split_self = value;
@@ -560,6 +561,8 @@ static void level_free(mgs_level &L) {
   mgs_vec_destroy(L.dinv); mgs_vec_destroy(L.r); mgs_vec_destroy(L.tmp); mgs_vec_destroy(L.b); mgs_vec_destroy(L.x); mgs_vec_destroy(L.wd);
   mgs_vec_destroy(L.hbuf);
   if (L.val_wd) mgs_hip_free(L.val_wd);
+  if (L.val_nd) mgs_hip_free(L.val_nd);
+  if (L.nd_code) mgs_hip_free(L.nd_code);
   if (L.val_wd32) mgs_hip_free(L.val_wd32);
   if (L.ap_val32) mgs_hip_free(L.ap_val32);
   if (L.col_agg) mgs_hip_free(L.col_agg);
@@ -592,6 +595,10 @@ static bool level_f32_eligible(const mgs_hier *h, int l) {
          L.val_wd && L.AP && L.A->blkptr && L.AP->blkptr && L.A->lds_cap > 0 && L.AP->lds_cap > 0 && L.A->max_row_len <= 64 && L.AP->max_row_len <= 64;
 }
 // ... and does so in the cycle the hierarchy would run NOW: only the fused zero-guess V(1,1) branch reads the operands at all
+// option pre_nodiag: the grouped pre pass of this level runs on val_nd (an eligible unsharded FP64 level whose compact operand is in step with val_wd)
+static bool level_pre_nodiag(const mgs_hier *h, const mgs_level &L, bool halo, bool f32) {
+  return h->ctx->opt_pre_nodiag && L.val_nd && L.nd_code && L.nd_ok && !L.nd_stale && !halo && !f32 && !h->ctx->opt_valcode;
+}
 static bool level_runs_f32(const mgs_hier *h, int l) {
   if (l < 0 || l >= (int)h->lev.size()) return false;
   const mgs_level &L = h->lev[l];
@@ -640,6 +647,7 @@ int mgs_hier_destroy(mgs_hier *h) {
   for (auto &L : h->lev) level_free(L);
   if (h->inv) mgs_hip_free(h->inv);
   if (h->refresh_flags) mgs_hip_free(h->refresh_flags);
+  if (h->nd_flag) mgs_hip_free(h->nd_flag);
   free_native_tail(h);
   delete h;
   return MGS_OK;
@@ -981,9 +989,10 @@ int mgs_hier_refresh(mgs_hier *h) {
     MGS_CHECK(ctx, !(L.A->code && L.A->code->vtab) && !L.code_hat && !(L.code_ap && L.code_ap->vtab), MGS_ERR_INVALID,
               "mgs_hier_refresh: level %d carries a value-carrying pattern code (built under option valcode)", l);
   }
-  bool kept = true;
+  bool kept = true, nd_built = false;
   if (!h->refresh_flags) MGS_TRY(mgs_dev_alloc(ctx, &h->refresh_flags, 2));
   MGS_HIP(ctx, hipMemsetAsync(h->refresh_flags, 0, 2 * sizeof(int), ctx->stream));
+  if (h->nd_flag) MGS_HIP(ctx, hipMemsetAsync(h->nd_flag, 0, sizeof(int), ctx->stream));
   int rc = MGS_OK;
   for (int l = 0; l < nl && rc == MGS_OK; ++l) {
     mgs_level &L = h->lev[l];
@@ -994,16 +1003,22 @@ int mgs_hier_refresh(mgs_hier *h) {
     if (rc == MGS_OK) rc = k_axpby(ctx, L.n_ext, h->omega, L.dinv->d, 0.0, L.wd->d);
     L.wd_omega = h->omega;    // (a new ω set since the last cycle: mgs_hier_set_smoother has dropped the graphs already)
     if (rc == MGS_OK && L.val_wd) rc = k_scale_vals(ctx, L.A, L.wd->d, L.val_wd);
+    if (rc == MGS_OK && L.val_wd && L.val_nd && L.nd_ok) { rc = k_drop_diag_vals(ctx, L.A, L.val_wd, h->omega, L.val_nd, L.nd_code, h->nd_flag); L.nd_omega = h->omega; nd_built = true; }
     if (rc == MGS_OK && L.AP) rc = k_galerkin_numeric(L.A, L.A->rows, nullptr, nullptr, L.T->agg, L.AP, h->refresh_flags + 1);
     if (rc == MGS_OK && L.val_wd && L.val_wd32) rc = k_round_vals(ctx, L.val_wd, L.val_wd32, L.A->nnz);
     if (rc == MGS_OK && L.AP && L.ap_val32) rc = k_round_vals(ctx, L.AP->val, L.ap_val32, L.AP->nnz);
   }
-  int flags[2] = {0, 0};
+  int flags[2] = {0, 0}, nd_bad = 0;
+  if (rc == MGS_OK && nd_built && hipMemcpyAsync(&nd_bad, h->nd_flag, sizeof nd_bad, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = mgs_fail(ctx, MGS_ERR_HIP, "mgs_hier_refresh: flag copy failed");
   if (rc == MGS_OK && hipMemcpyAsync(flags, h->refresh_flags, sizeof flags, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = mgs_fail(ctx, MGS_ERR_HIP, "mgs_hier_refresh: flag copy failed");
   if (rc == MGS_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = mgs_fail(ctx, MGS_ERR_HIP, "mgs_hier_refresh: %s", hipGetErrorString(hipGetLastError()));
   if (rc == MGS_OK && flags[1]) rc = mgs_fail(ctx, MGS_ERR_STATE, "mgs_hier_refresh: %d entries fall outside the kept coarse patterns (the fine pattern is not the one the hierarchy was built for)", flags[1]);
   if (rc == MGS_OK && nl == 1 && !h->coarse_sweeps) { h->bad_diag0 = flags[0]; flags[0] = 0; }   // one level, solved densely: D⁻¹ is not used (mgs_hier_create)
   if (rc == MGS_OK && flags[0]) rc = mgs_fail(ctx, MGS_ERR_NUMERIC, "mgs_hier_refresh: %d rows of the refreshed operators have a missing or zero diagonal", flags[0]);
+  if (rc == MGS_OK && nd_bad) {      // a diagonal entry of some Â no longer fits its byte: those levels stream val_wd again (cached graphs read val_nd)
+    for (auto &L : h->lev) L.nd_ok = false;
+    kept = false; drop_graph(h);
+  }
   if (rc == MGS_OK && !h->coarse_sweeps) {      // coarsest dense inverse, into the buffer the cached graphs know
     if (!h->inv) { kept = false; drop_graph(h); }
     rc = k_dense_inverse(ctx, h->lev.back().A, &h->inv);
@@ -1036,6 +1051,23 @@ int mgs_hier_group_info(const mgs_hier *h, int level, int64_t out[4]) {
   const mgs_groups *G = h->lev[level].grp;
   out[0] = G ? G->ngroups : 0; out[1] = G ? G->nblocks - G->ngroups : 0;   /* blocks merged into another block's group */ out[2] = G ? G->nstray : 0; out[3] = (h->lev[level].A->rows + 255) / 256;
   return MGS_OK;
+}
+int mgs_hier_pre_pass(mgs_hier *h, int level, const mgs_vec *b, mgs_vec *t, mgs_vec *r, mgs_vec *rc, int *nodiag) {
+  MGS_CHECK(nullptr, h && b && t && r && rc, MGS_ERR_INVALID, "mgs_hier_pre_pass: NULL argument");
+  mgs_ctx *ctx = h->ctx;
+  MGS_CHECK(ctx, h->finalized, MGS_ERR_STATE, "mgs_hier_pre_pass: call mgs_hier_finalize first");
+  MGS_CHECK(ctx, level >= 0 && level + 1 < (int)h->lev.size(), MGS_ERR_INVALID, "mgs_hier_pre_pass: level %d has no coarser level", level);
+  MGS_TRY(prepare_fused(h));
+  mgs_level &L = h->lev[level];
+  const bool plain = L.A->cols == L.A->rows && !L.nx && !(L.A->code && L.A->code->vtab) && !L.code_hat;
+  MGS_CHECK(ctx, ctx->opt_fuse_restrict && L.grp && L.val_wd && plain, MGS_ERR_STATE, "mgs_hier_pre_pass: level %d does not run the grouped pre pass (see mgs_hier_group_info), or is sharded / value-coded", level);
+  MGS_CHECK(ctx, b->n >= L.n && t->n >= L.n && r->n >= L.n && rc->n >= L.T->n_coarse, MGS_ERR_INVALID, "mgs_hier_pre_pass: vectors shorter than the level (%d rows, %d aggregates)", L.n, L.T->n_coarse);
+  mgs_csr Ahat = *L.A; Ahat.val = L.val_wd; Ahat.owns = false;
+  const bool f32 = level_runs_f32(h, level);
+  if (f32) Ahat.val32 = L.val_wd32;
+  const bool nd = level_pre_nodiag(h, L, false, f32);
+  if (nodiag) *nodiag = nd ? 1 : 0;
+  return mgs_launch_group_pre(&Ahat, L.grp, L.T, b->d, b->d, t->d, r->d, rc->d, nullptr, L.A->rows, nd ? L.val_nd : nullptr, L.nd_code, L.nd_omega);
 }
 int mgs_hier_graph_info(const mgs_hier *h, int64_t out[4]) {
   int n = 0; for (auto &g : h->graphs) n += g.exec != nullptr;
@@ -1311,7 +1343,9 @@ static int cycle_level(mgs_hier *h, int l, const double *b, double *x, bool zero
                          (!halo || L.nx || !split || (h->capturing));
     if (grouped) {
       if (halo) MGS_TRY(exchange_now(l, b, L.hbuf->d));
-      MGS_TRY(mgs_launch_group_pre(&Ahat, L.grp, L.T, b, b, L.r->d, L.tmp->d, C.b->d, hv, L.A->rows));
+      // option pre_nodiag: an eligible FP64 level streams Â's diagonal as a byte per row (the same bits as from val_wd)
+      const bool nodiag = level_pre_nodiag(h, L, halo, f32);
+      MGS_TRY(mgs_launch_group_pre(&Ahat, L.grp, L.T, b, b, L.r->d, L.tmp->d, C.b->d, hv, L.A->rows, nodiag ? L.val_nd : nullptr, L.nd_code, L.nd_omega));
       MGS_TRY(coarse_solve(h, l + 1, C.b->d, C.x->d));
       if (ctx->opt_group_sweep & 1) Amap.sweep = L.grp;
       return post_operand(L.r->d, nullptr);
@@ -1425,6 +1459,7 @@ static int prepare_fused(mgs_hier *h) {
       bool new_vals = false;
       if (!L.val_wd) { MGS_TRY(mgs_dev_alloc(ctx, &L.val_wd, (size_t)L.A->nnz + 4)); MGS_TRY(k_scale_vals(ctx, L.A, L.wd->d, L.val_wd)); drop_graph(h); new_vals = true; }
       else if (rescale) { MGS_TRY(k_scale_vals(ctx, L.A, L.wd->d, L.val_wd)); new_vals = true; }
+      if (new_vals) L.nd_stale = true;
       const int ncols_c = h->lev[l + 1].A->cols;      // coarse level's local columns: its rows + its halo slots
       if (ctx->opt_merge_ap && !L.AP) {
         MGS_TRY(k_build_ap(L.A, L.T, L.cmap_ext, ncols_c, &L.AP)); drop_graph(h);
@@ -1454,6 +1489,36 @@ static int prepare_fused(mgs_hier *h) {
         else MGS_TRY(mgs_build_rowcode(ctx, L.A->rows, L.A->rowptr, L.A->col, nullptr, 0x7fffffff, &L.code_hat, L.val_wd));
       }
       MGS_TRY(level_refresh_f32(h, L, new_vals));      // FP32 copies follow their FP64 operands (a new ω rescales Â)
+    }
+  }
+  // Compact operand of the grouped pre pass (option pre_nodiag), allocated behind everything above: the other operands stay where the
+  // arena places them without it.  Eligibility is decided once per level; the values follow val_wd.
+  for (size_t l = 0; ctx->opt_fuse_operands && ctx->opt_pre_nodiag && l + 1 < h->lev.size(); ++l) {
+    mgs_level &L = h->lev[l];
+    if (!L.val_wd || !L.grp) continue;
+    if (!L.nd_tried) {
+      L.nd_tried = true;
+      int bad = 1;
+      if (L.A->cols == L.A->rows && !L.nx && L.A->max_row_len <= 64 && L.A->nnz >= L.A->rows) MGS_TRY(k_diag_count(L.A, &bad));
+      L.nd_ok = bad == 0;
+    }
+    if (!L.nd_ok) continue;
+    if (!L.val_nd) {
+      const size_t m = (size_t)(L.A->nnz - L.A->rows);
+      MGS_TRY(mgs_dev_alloc(ctx, &L.val_nd, m + 8));
+      MGS_HIP(ctx, hipMemsetAsync(L.val_nd + m, 0, 8 * sizeof(double), ctx->stream));
+      MGS_TRY(mgs_dev_alloc(ctx, &L.nd_code, (size_t)L.A->rows));
+      if (!h->nd_flag) MGS_TRY(mgs_dev_alloc(ctx, &h->nd_flag, 1));
+      L.nd_stale = true; drop_graph(h);
+    }
+    if (L.nd_stale) {      // values and the diagonal's bytes follow val_wd; a diagonal entry further from ω than a byte holds (1/a_ii under- or overflowed) ends it
+      int bad = 0;
+      MGS_HIP(ctx, hipMemsetAsync(h->nd_flag, 0, sizeof(int), ctx->stream));
+      MGS_TRY(k_drop_diag_vals(ctx, L.A, L.val_wd, L.wd_omega, L.val_nd, L.nd_code, h->nd_flag));
+      MGS_HIP(ctx, hipMemcpyAsync(&bad, h->nd_flag, sizeof bad, hipMemcpyDeviceToHost, ctx->stream));
+      MGS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+      L.nd_omega = L.wd_omega; L.nd_stale = false;
+      if (bad) { L.nd_ok = false; drop_graph(h); }
     }
   }
   return MGS_OK;

@@ -63,6 +63,8 @@ struct mgs_ctx {
   int opt_post_results = 1;   // inner products reach the host through a mapped buffer + ticket the host polls (no copy engine, no interrupt)
   int opt_rowptr_scan = 1;    // coded row blocks take a row's entry range from its pattern's length (wave prefix sum, one rowptr load per wave) instead of
                               // two rowptr loads per row: 4 B per row less to stream (kernels_spmv.hip: coded_row_range)
+  int opt_pre_nodiag = 1;     // grouped pre pass of an unsharded FP64 level: Â's diagonal entries (ω up to three roundings) are streamed as one byte per row,
+                              // their distance from ω, instead of a double (7 B per row less, the same bits; 0: the kernels read val_wd as it is)
   int opt_stage_unroll = 1;   // row-block kernels stage their value slice without a loop in front of the barrier (predicated 16-byte loads / LDS-DMA): −4 … −7 % per cycle
   int opt_blas1_pairs = 1;    // ... pairs per lane of those kernels: 1 = one-shot workgroups (0: capped persistent grid, k: k pairs per lane)
   int opt_blas1_vec = 1;      // axpby / axpbypcz / update+dots move 16 B per lane with four loads per stream in flight (same per-element bits)
@@ -233,6 +235,12 @@ struct mgs_level {
   unsigned char *dpos = nullptr;     // position of the diagonal entry inside each row (255: none / beyond 254), see mgs_csr::dpos
   mgs_groups *grp = nullptr;         // aggregate-complete row-block groups (grouped pre pass = pre pass + restriction in one kernel)
   bool grp_tried = false;
+  // option pre_nodiag: Â's diagonal entry is ω after three roundings for every row, so the grouped pre pass streams val_wd without it
+  double *val_nd = nullptr;          // nnz − rows + 8 doubles: val_wd in storage order, each row's diagonal entry left out (row i from rowptr[i] − i)
+  signed char *nd_code = nullptr;    // rows bytes: bit pattern of Â_ii minus bit pattern of nd_omega (a few units of the last place)
+  double nd_omega = 0.0;             // ω that nd_code counts from
+  bool nd_tried = false, nd_ok = false;   // eligibility, decided once: grouped, unsharded, every row holds exactly one diagonal entry
+  bool nd_stale = false;             // val_wd was rebuilt since val_nd was
   mgs_vec *kc1 = nullptr, *kv1 = nullptr, *kc2 = nullptr, *kv2 = nullptr, *kr = nullptr;   // K-cycle work vectors
   double *kscal = nullptr;     // K-cycle scalars (device)
   double wd_omega = 0.0;       // ω that wd was built with
@@ -280,6 +288,7 @@ struct mgs_hier {
   bool coarse_launch = false;            // set around the eager fine-level passes: coarse_solve(h, 1, ..) replays coarse_exec
   // mgs_hier_refresh: counters of mgs_hier_refresh_info and the device flags one refresh reads back at its end
   int64_t refresh_count = 0, refresh_kept_graphs = 0, refresh_dev_levels = 0;
+  int *nd_flag = nullptr;          // option pre_nodiag: rows whose diagonal entry of Â does not fit nd_code (device counter)
   int *refresh_flags = nullptr;   // [0] rows with a missing or zero diagonal (all levels), [1] entries outside the kept coarse patterns
   bool refresh_failed = false;    // the last refresh ended with MGS_ERR_NUMERIC: un-finalized until a later refresh succeeds
   std::vector<hipEvent_t> fork_events;   // fork/join events of the captured native cycle (two per overlapped exchange)
@@ -333,6 +342,10 @@ int mgs_launch_fused_range(const mgs_csr *A, int which, const double *wd, const 
                            const double *ec, double *out, double *out2, const double *hv, int blk_lo, int blk_hi,
                            int gap_at = 0x7fffffff, int gap_len = 0);
 int k_scale_vals(mgs_ctx *ctx, const mgs_csr *A, const double *wd, double *out);            // out_k = a_k·wd[col_k] (row shards: wd covers the halo columns too)
+int k_diag_count(const mgs_csr *A, int *bad_count_host);                                       // rows that do not hold exactly one entry with col == row
+int k_drop_diag_vals(mgs_ctx *ctx, const mgs_csr *A, const double *val, double omega, double *out, signed char *code, int *bad_dev);
+                                                                                               // out: val without each row's diagonal entry (row i from rowptr[i] − i); code[i]: that entry's distance
+                                                                                               // from omega in units of the last place; rows beyond ±127 are added to *bad_dev
 int k_map_cols(mgs_ctx *ctx, const mgs_csr *A, const int *cmap, int *out);                     // out_k = cmap[col_k]
 int k_concat_i32(mgs_ctx *ctx, const int *a, int na, const int *b, int nb, int *out);
 int k_tail_scatter(mgs_ctx *ctx, const double *xt, int my_off, int n_loc, const int *halo_global, int n_halo, double *x);   // x[0..n_loc) = xt[my_off..], x[n_loc+s] = xt[halo_global[s]]
@@ -348,8 +361,11 @@ int mgs_build_groups(mgs_ctx *ctx, const mgs_csr *A, const mgs_xfer *T, mgs_grou
 void mgs_free_groups(mgs_groups *g);
 // t = b + (b − Â·x) and r_c = Pᵀ(b − Â·x) in one pass over the groups of G; x = gather source (b itself, or with hv/split the
 // halo payload of a row shard); strays' member rows also store r into r_out, restricted by the trailing small kernel
+// val_nd, nd_code (option pre_nodiag, unsharded FP64 levels): Â's values without the diagonal entries, and each diagonal entry as its distance
+// from omega (k_drop_diag_vals); coded + staged blocks then stream these instead of val — the same bits, 7 bytes per row less
 int mgs_launch_group_pre(const mgs_csr *Ahat, const mgs_groups *G, const mgs_xfer *T, const double *x, const double *b,
-                         double *t_out, double *r_out, double *rc_out, const double *hv, int split);
+                         double *t_out, double *r_out, double *rc_out, const double *hv, int split,
+                         const double *val_nd = nullptr, const signed char *nd_code = nullptr, double omega = 0.0);
 // (kernels_aux.hip)
 int k_diag_inv(const mgs_csr *A, double *dinv, int *bad_count_host);
 int k_diag_inv_async(const mgs_csr *A, double *dinv, int *bad_dev);   // no host round trip: bad rows are added to *bad_dev
