@@ -185,7 +185,11 @@ int mgs_hier_push_P(mgs_hier *h, const mgs_csr *P);
 /* append levels by on-device pairwise aggregation (Notay AGMG: src/CPU_C++/AGMG.cpp:
  * 299-315, src/GPU_CUDAC++/main.cu:95-277) until the coarsest has <= coarse_rows rows,
  * max_levels is reached or coarsening stalls.  ktg/npass/tou as the reference's argv
- * (src/CPU_C++/main.cpp:155-182; benchmarks use 10 2 8, results.txt:22-24).           */
+ * (src/CPU_C++/main.cpp:155-182; benchmarks use 10 2 8, results.txt:22-24).
+ * The matching is deterministic: every undecided row picks its best admissible neighbour and mutual picks pair up.  A row's
+ * neighbours are the entries of its row in the stored pattern when that pattern is symmetric, else in the union of the stored
+ * patterns of A and Aᵀ; {i,j} is a candidate when a_ij != 0 or a_ji != 0, so a coupling stored (or non-zero) on one side only
+ * pairs like any other, as in the reference (AGMG.cpp:151-174 scans row i of A).                                       */
 int mgs_hier_coarsen(mgs_hier *h, double ktg, int npass, double tou, int coarse_rows,
                      int max_levels);
 /* factor the coarsest operator (dense inverse on device, ≤ 8192 rows: Gauss-Jordan with partial
@@ -348,7 +352,8 @@ int mgs_hier_set_halo_exchange_fused(mgs_hier *h, mgs_halo_fused_fn fn, void *us
 /* Building blocks of a row-sharded hierarchy (one process per GPU; orchestration in
  * multigridsolver_amd/dist.py).  mgs_aggregate_shard: pairwise aggregation of the OWNED
  * rows only (aggregates never straddle a shard; couplings to halo columns enter s_i and the
- * G0 test as symmetric).  The caller then learns the remote aggregate of every halo slot from
+ * G0 test as symmetric and never pair; among the owned columns the matching runs on the pattern
+ * mgs_hier_coarsen describes: the union of A's and Aᵀ's when A's is not symmetric).  The caller then learns the remote aggregate of every halo slot from
  * its peers and passes the coarse column of each halo slot (host array, n_halo ints, values
  * in [n_coarse, n_coarse+n_halo_coarse) or −1) to mgs_galerkin_shard, which returns the coarse
  * shard (n_coarse rows, n_coarse+n_halo_coarse local columns).  mgs_hier_push_level appends
@@ -389,7 +394,10 @@ int mgs_csr_plan_info(const mgs_csr *A, int64_t out[8]);
  * (nearest first, then even multiples of the stride), which keeps aggregates aligned on grid-like problems on every level.  A row-sharded
  * hierarchy hands the origins of its last sharded level (shifted to global finest-level rows) to the replicated tail with these two
  * calls.  get: returns 1 and writes nothing when the operator carries none (= identity).  No reference counterpart (the reference's
- * sequential matching scans neighbours in index order, AGMG.cpp:149-179). */
+ * sequential matching scans neighbours in index order, AGMG.cpp:149-179).
+ * set: the origins must be non-negative and distinct (the tie-break key divides by the distance of two origins); they may exceed the
+ * row count (the shifted origins of a replicated tail).  Anything else is refused with MGS_ERR_INVALID before the matrix changes.
+ * origin_host = NULL removes the origins (= identity). */
 int mgs_csr_get_origin(const mgs_csr *A, int *origin_host);
 int mgs_csr_set_origin(mgs_csr *A, const int *origin_host);
 /* ---- native RCCL transport of a row-sharded hierarchy (no reference counterpart: the reference is single-process) ----

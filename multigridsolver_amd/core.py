@@ -370,10 +370,14 @@ class Hierarchy:
         return r.value, n.value
 
     def level_A(self, l):
-        return Csr(self.ctx, C.c_void_p(lib().mgs_hier_level_A(self.h, l)), owned=False)
+        M = Csr(self.ctx, C.c_void_p(lib().mgs_hier_level_A(self.h, l)), owned=False)
+        M._hier = self      # a view into this hierarchy: it keeps the hierarchy alive, so h.level_A(l) may outlive the name h
+        return M
 
     def level_P(self, l):
-        return Xfer(self.ctx, C.c_void_p(lib().mgs_hier_level_P(self.h, l)), owned=False)
+        T = Xfer(self.ctx, C.c_void_p(lib().mgs_hier_level_P(self.h, l)), owned=False)
+        T._hier = self      # as level_A: Hierarchy(...).coarsen(...).level_P(0).agg() must not read a destroyed hierarchy
+        return T
 
     @property
     def vcycle_bytes(self):

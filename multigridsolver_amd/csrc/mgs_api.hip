@@ -8,6 +8,7 @@
 thread_local std::string g_mgs_last_error;
 
 // ------------------------------------------------------------------ device memory arena (see mgs_internal.hpp)
+#include <algorithm>
 #include <map>
 #include <mutex>
 namespace {
@@ -351,6 +352,13 @@ int mgs_csr_get_origin(const mgs_csr *A, int *origin) {
 }
 int mgs_csr_set_origin(mgs_csr *A, const int *origin) {
   mgs_ctx *ctx = A->ctx;
+  if (origin && A->rows > 0) {      // the tie-break key divides by the distance of two origins: distinct and non-negative, checked before anything changes
+    std::vector<int> o(origin, origin + A->rows);
+    std::sort(o.begin(), o.end());
+    MGS_CHECK(ctx, o.front() >= 0, MGS_ERR_INVALID, "mgs_csr_set_origin: negative origin %d", o.front());
+    const auto dup = std::adjacent_find(o.begin(), o.end());
+    MGS_CHECK(ctx, dup == o.end(), MGS_ERR_INVALID, "mgs_csr_set_origin: origin %d given to more than one row", dup == o.end() ? 0 : *dup);
+  }
   if (A->origin) { mgs_hip_free(A->origin); A->origin = nullptr; }
   if (!origin || A->rows == 0) return MGS_OK;
   MGS_TRY(mgs_dev_alloc(ctx, &A->origin, (size_t)A->rows));

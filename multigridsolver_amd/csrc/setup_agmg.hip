@@ -9,11 +9,14 @@
 //     src/GPU_CUDAC++/Aggregation.cu:17-270) with a DETERMINISTIC matching: instead of the
 //     reference GPU's race-dependent atomicCAS claim (Aggregation.cu:203) every undecided
 //     node picks its best admissible neighbour from a snapshot and mutual picks pair up
-//     (locally-dominant edges), so P is reproducible run to run.
+//     (locally-dominant edges), so P is reproducible run to run.  A node's neighbours are the entries of its row in
+//     M's stored pattern when that is symmetric, else in the union of M's and Mᵀ's patterns on the owned columns:
+//     {i,j} is a candidate when a_ij != 0 or a_ji != 0, whichever side stores it.
 // FP64 throughout (the reference GPU setup is float32, MatrixIO.cu:32-36).
 #include "mgs_internal.hpp"
 
 #include <algorithm>
+#include <climits>
 
 namespace {
 constexpr int TB = 256;
@@ -309,10 +312,38 @@ __global__ void agg_node_stats_kernel(int n, const int *__restrict__ rowptr, con
   int g0 = first_pass && (aii >= (ktg / (ktg - 2)) * asum);
   state[i] = g0 ? -2 : -1;
 }
-// μ({i,j}) per stored entry (AGMG.cpp:92-99, Aggregation.cu:96-105), +inf if the pair is not
-// admissible: j==i, a_ij==0, i or j in G0, a_ii−s_i+a_jj−s_j<0 (`okay`, Aggregation.cu:157-159),
-// μ≤0 or μ>ktg (AGMG.cpp:163,171).
+// Union of the stored patterns of M and Mᵀ on the owned columns (asymmetric patterns only): row i lists every owned j with a_ij or
+// a_ji stored, ascending, with both values (0 where one side stores nothing).  The matching runs on this pattern: a node picks only
+// among the entries of its own row and a pair needs a mutual pick, so on M's own pattern a coupling stored on one side only could
+// never pair (the reference pairs along it: AGMG.cpp:151-174 scans row i of A).  Halo columns never pair and are left out.
+// uptr != nullptr: fill pass (uptr = scanned counts); else count pass into ucnt.
+__global__ void union_pattern_kernel(int n, const int *__restrict__ rowptr, const int *__restrict__ col, const double *__restrict__ val,
+                                     const int *__restrict__ trowptr, const int *__restrict__ tcol, const double *__restrict__ tval,
+                                     const int *__restrict__ uptr, int *__restrict__ ucnt, int *__restrict__ ucol, double *__restrict__ uij, double *__restrict__ uji) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > n) return;
+  if (i == n) { if (!uptr) ucnt[n] = 0; return; }
+  int r = rowptr[i], re = rowptr[i + 1], c = trowptr[i], ce = trowptr[i + 1];
+  int cnt = 0; const int dst = uptr ? uptr[i] : 0;
+  while (r < re || c < ce) {
+    int jr = r < re ? col[r] : 0x7fffffff, jc = c < ce ? tcol[c] : 0x7fffffff;
+    int j = min(jr, jc);
+    if (j >= n) break;                              // halo columns: sorted last, present in the row only
+    double aij = 0.0, aji = 0.0;
+    if (jr == j) aij = val[r++];
+    if (jc == j) aji = tval[c++];
+    if (uptr) { ucol[dst + cnt] = j; uij[dst + cnt] = aij; uji[dst + cnt] = aji; }
+    ++cnt;
+  }
+  if (!uptr) ucnt[i] = cnt;
+}
+// μ({i,j}) per entry of the matching pattern (AGMG.cpp:92-99, Aggregation.cu:96-105), +inf if the pair is not
+// admissible: j==i, halo column, i or j in G0, different zones, a_ii−s_i+a_jj−s_j<0 (`okay`, Aggregation.cu:157-159),
+// a_ij==0 and a_ji==0, μ≤0 or μ>ktg (AGMG.cpp:163,171).  μ is symmetric in (i,j) bit for bit (every sum in it is
+// commutative), so the smallest key of a neighbourhood is mutual.  vji == nullptr: the pattern is M's own, symmetric,
+// and a_ji is looked up; else (rowptr, col, val, vji) is the union pattern with both values.
 __global__ void agg_edge_weight_kernel(int n, const int *__restrict__ rowptr, const int *__restrict__ col, const double *__restrict__ val,
+                                       const double *__restrict__ vji,
                                        const double *__restrict__ diag, const double *__restrict__ s, const int *__restrict__ state,
                                        double ktg, const int *__restrict__ zone /*NULL: none; rows of different zones never pair*/, double *__restrict__ w) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -323,14 +354,16 @@ __global__ void agg_edge_weight_kernel(int n, const int *__restrict__ rowptr, co
   for (int k = rowptr[i]; k < rowptr[i + 1]; ++k) {
     int j = col[k]; double aij = val[k];
     double wk = INFINITY;
-    if (j != i && j < n && aij != 0.0 && !gi && state[j] != -2 && (!zone || zone[j] == zi)) {
+    if (j != i && j < n && !gi && state[j] != -2 && (!zone || zone[j] == zi)) {
       double ajj = diag[j], sj = s[j];
       if (aii - si + ajj - sj >= 0) {
-        double aji = csr_lookup(rowptr, col, val, j, i);
-        double num = 2 / (1 / aii + 1 / ajj);
-        double den = (-(aij + aji) / 2) + 1 / (1 / (aii - si) + 1 / (ajj - sj));
-        double mu = num / den;
-        if (mu > 0 && mu <= ktg) wk = mu;
+        double aji = vji ? vji[k] : csr_lookup(rowptr, col, val, j, i);
+        if (aij != 0.0 || aji != 0.0) {
+          double num = 2 / (1 / aii + 1 / ajj);
+          double den = (-(aij + aji) / 2) + 1 / (1 / (aii - si) + 1 / (ajj - sj));
+          double mu = num / den;
+          if (mu > 0 && mu <= ktg) wk = mu;
+        }
       }
     }
     w[k] = wk;
@@ -659,13 +692,40 @@ int k_galerkin_general(const mgs_csr *A, const mgs_xfer *T, mgs_csr **out) {
   return mgs_csr_upload(ctx, T->n_coarse, T->n_coarse, (int64_t)c2.size(), r2.data(), c2.data(), v2.data(), out);
 }
 
+// the union pattern of M and Mᵀ (union_pattern_kernel) in device buffers; returns with the stream idle, so the caller may free Mᵀ
+static int union_pattern(const mgs_csr *M, const mgs_csr *Mt, DevBuf &uptr, DevBuf &ucol, DevBuf &uij, DevBuf &uji, int *unnz_out) {
+  mgs_ctx *ctx = M->ctx;
+  const int n = M->rows;
+  hipStream_t st = ctx->stream;
+  // at most 2·nnz entries; the row counts are scanned in int
+  MGS_CHECK(ctx, 2 * (int64_t)M->nnz <= (int64_t)INT_MAX, MGS_ERR_INVALID,
+            "aggregate: an operator with an asymmetric pattern may hold at most %d stored entries, this one has %lld", INT_MAX / 2, (long long)M->nnz);
+  MGS_TRY(dalloc<int>(ctx, uptr, (size_t)n + 1));
+  const dim3 g1(mgs_grid(n + 1, TB)), b(TB);
+  hipLaunchKernelGGL(union_pattern_kernel, g1, b, 0, st, n, M->rowptr, M->col, M->val, Mt->rowptr, Mt->col, Mt->val, (const int *)nullptr, uptr.as<int>(),
+                     (int *)nullptr, (double *)nullptr, (double *)nullptr);
+  MGS_HIP(ctx, hipGetLastError());
+  MGS_TRY(scan_rec(ctx, uptr.as<int>(), uptr.as<int>(), (int64_t)n + 1));
+  int unnz = 0;
+  MGS_HIP(ctx, hipMemcpyAsync(&unnz, uptr.as<int>() + n, sizeof(int), hipMemcpyDeviceToHost, st));
+  MGS_HIP(ctx, hipStreamSynchronize(st));
+  const size_t len = (size_t)std::max(unnz, 1);
+  MGS_TRY(dalloc<int>(ctx, ucol, len)); MGS_TRY(dalloc<double>(ctx, uij, len)); MGS_TRY(dalloc<double>(ctx, uji, len));
+  hipLaunchKernelGGL(union_pattern_kernel, g1, b, 0, st, n, M->rowptr, M->col, M->val, Mt->rowptr, Mt->col, Mt->val, (const int *)uptr.as<int>(), (int *)nullptr,
+                     ucol.as<int>(), uij.as<double>(), uji.as<double>());
+  MGS_HIP(ctx, hipGetLastError());
+  MGS_HIP(ctx, hipStreamSynchronize(st));
+  *unnz_out = unnz;
+  return MGS_OK;
+}
+
 // one pairwise pass on matrix M → agg ids (device array, caller frees) and count
 static int pairwise_pass(const mgs_csr *M, double ktg, int first_pass, const int *origin, const int *zone, int **agg_out, int *nc_out) {
   mgs_ctx *ctx = M->ctx;
   const int n = M->rows;
   DevBuf diag, s, state, w, pick, cnt, flag, asym;
   MGS_TRY(dalloc<double>(ctx, diag, (size_t)n)); MGS_TRY(dalloc<double>(ctx, s, (size_t)n));
-  MGS_TRY(dalloc<int>(ctx, state, (size_t)n)); MGS_TRY(dalloc<double>(ctx, w, (size_t)M->nnz));
+  MGS_TRY(dalloc<int>(ctx, state, (size_t)n));
   MGS_TRY(dalloc<int>(ctx, pick, (size_t)n)); MGS_TRY(dalloc<int>(ctx, cnt, 2)); MGS_TRY(dalloc<int>(ctx, flag, (size_t)n + 1));
   MGS_TRY(dalloc<int>(ctx, asym, 1));
   hipStream_t st = ctx->stream;
@@ -679,21 +739,33 @@ static int pairwise_pass(const mgs_csr *M, double ktg, int first_pass, const int
   if (hasym) MGS_TRY(k_transpose(M, &Mt));
   hipLaunchKernelGGL(agg_node_stats_kernel, g, b, 0, st, n, M->rowptr, M->col, M->val, Mt ? Mt->rowptr : nullptr, Mt ? Mt->col : nullptr,
                      Mt ? Mt->val : nullptr, ktg, first_pass, diag.as<double>(), s.as<double>(), state.as<int>());
-  hipLaunchKernelGGL(agg_edge_weight_kernel, g, b, 0, st, n, M->rowptr, M->col, M->val, diag.as<double>(), s.as<double>(), state.as<int>(), ktg, zone, w.as<double>());
+  // the pattern the matching runs on: M's own when it is symmetric, else the union of M's and Mᵀ's on the owned columns
+  const int *mrp = M->rowptr, *mcol = M->col; const double *mij = M->val, *mji = nullptr;
+  DevBuf uptr, ucol, uij, uji;
+  int64_t wlen = M->nnz;
+  if (Mt) {
+    int unnz = 0;
+    const int rc = union_pattern(M, Mt, uptr, ucol, uij, uji, &unnz);
+    mgs_csr_destroy(Mt);                            // Mᵀ is read by nothing after the union's fill pass
+    MGS_TRY(rc);
+    mrp = uptr.as<int>(); mcol = ucol.as<int>(); mij = uij.as<double>(); mji = uji.as<double>(); wlen = unnz;
+  }
+  MGS_HIP(ctx, hipGetLastError());
+  MGS_TRY(dalloc<double>(ctx, w, (size_t)std::max<int64_t>(wlen, 1)));
+  hipLaunchKernelGGL(agg_edge_weight_kernel, g, b, 0, st, n, mrp, mcol, mij, mji, diag.as<double>(), s.as<double>(), state.as<int>(), ktg, zone, w.as<double>());
   MGS_HIP(ctx, hipGetLastError());
   const int MAX_ROUNDS = 96, MU_ROUNDS = 24;
   for (int round = 0; round < MAX_ROUNDS; ++round) {
     const int hash_only = round >= MU_ROUNDS;
     const int force = round == MAX_ROUNDS - 1;
     MGS_HIP(ctx, hipMemsetAsync(cnt.p, 0, 2 * sizeof(int), st));
-    hipLaunchKernelGGL(agg_pick_kernel, g, b, 0, st, n, M->rowptr, M->col, w.as<double>(), state.as<int>(), hash_only, origin, pick.as<int>());
+    hipLaunchKernelGGL(agg_pick_kernel, g, b, 0, st, n, mrp, mcol, w.as<double>(), state.as<int>(), hash_only, origin, pick.as<int>());
     hipLaunchKernelGGL(agg_match_kernel, g, b, 0, st, n, pick.as<int>(), state.as<int>(), force, cnt.as<int>());
     int left = 0;
     MGS_HIP(ctx, hipMemcpyAsync(&left, cnt.p, sizeof(int), hipMemcpyDeviceToHost, st));
     MGS_HIP(ctx, hipStreamSynchronize(st));
     if (left == 0) break;
   }
-  if (Mt) mgs_csr_destroy(Mt);
   hipLaunchKernelGGL(agg_leader_flag_kernel, dim3(mgs_grid(n + 1, TB)), b, 0, st, n, state.as<int>(), flag.as<int>());
   MGS_TRY(scan_rec(ctx, flag.as<int>(), flag.as<int>(), (int64_t)n + 1));
   int nc = 0;

@@ -8,6 +8,8 @@ import os
 import numpy as np
 import pytest
 
+import agmg_ref
+
 pytestmark = pytest.mark.gpu
 
 
@@ -1258,11 +1260,19 @@ def test_pattern_asymmetric_operator_setup(ctx, mg, orc):
     Ad = A_sp.toarray(); s = -np.asarray(S.sum(axis=1)).ravel()
     h1 = mg.Hierarchy(A, 0.6, 1, 1).coarsen(10.0, 1, 8.0, coarse_rows=0, max_levels=2)        # one pass: plain pairs
     a1 = h1.level_P(0).agg()
-    for I in np.nonzero(np.bincount(a1[a1 >= 0]) == 2)[0][:200]:
+    # the matching runs on the union of the patterns of A and Aᵀ: a coupling stored on one side only pairs like any other.  At least as
+    # many pairs as the host restatement of the matching forms on this input (tests/agmg_ref.py; 252 pairs, 146 singletons, 4 rounds)
+    ref_pairs = agmg_ref.pass_counts(agmg_ref.pairwise_pass(A_sp, 10.0, 1)[0])[0]
+    pairs = np.nonzero(np.bincount(a1[a1 >= 0]) == 2)[0]
+    assert ref_pairs == 252 and pairs.size >= ref_pairs, (pairs.size, ref_pairs)
+    visited = 0
+    for I in pairs[:200]:
+        visited += 1
         i, j = np.nonzero(a1 == I)[0]
         num = 2 / (1 / Ad[i, i] + 1 / Ad[j, j])
         den = -(Ad[i, j] + Ad[j, i]) / 2 + 1 / (1 / (Ad[i, i] - s[i]) + 1 / (Ad[j, j] - s[j]))
         assert 0 < num / den <= 10.0 * (1 + 1e-12), (i, j, num / den)
+    assert visited >= 1
     h = mg.Hierarchy(A, 0.6, 1, 1).coarsen(10.0, 2, 8.0, coarse_rows=50, max_levels=8).finalize()
     b_np = rng.standard_normal(n)
     x = ctx.vec(n); st, it, tol = mg.bicgstab(A, x, ctx.vec(b_np), h, 500, 1e-10)
