@@ -105,6 +105,47 @@ int mgs_csr_device_ptrs(const mgs_csr *A, void **rowptr, void **col, void **val)
  * (option "valcode": its tables hold the old values).                                                                    */
 int mgs_csr_update_values(mgs_csr *A, const double *host_val, int64_t nnz);
 int mgs_csr_update_values_dev(mgs_csr *A, const void *device_val, int64_t nnz);
+/* ---- matrices that already live in device memory: no host round trip of the data ----
+ * Common to the two constructors below.  index_bits: 32 or 64, the width of the index arrays given (int32_t / int64_t); 64-bit
+ * indices are range-checked as 64-bit values before they are narrowed to the library's int32.  nnz resp. ntrip must be below
+ * 2^31.  The inputs are only read and are copied: the caller may release them once the call has returned.  The work is enqueued on
+ * the context's stream and the call synchronises before it returns, as mgs_csr_upload does (it needs counts on the host); making
+ * the inputs visible to that stream — synchronising the stream that produced them — is the caller's job.  No kernel uses an input
+ * index as an address before it has been range-checked: bad input comes back as MGS_ERR_INVALID and never faults; *out is then not
+ * written and everything the call allocated is released.  Both end with the launch plan of mgs_csr_upload: the result is
+ * indistinguishable from an uploaded matrix (mgs_csr_optimize, hierarchies, Krylov solvers, mgs_csr_update_values*). */
+/* CSR arrays in device memory.  Nearest reference line: deepCopyMatrixCSRCPUtoGPU, src/GPU_CUDAC++/MatrixOperations.cu:121-146 (host
+ * to device, unchecked); taking device arrays has no reference counterpart.  The acceptance rules are mgs_csr_upload's, checked on
+ * the device in the passes that copy and narrow the arrays: rowptr[0] == 0 and rowptr[rows] == nnz, rowptr monotone, every column in
+ * [0, cols), columns strictly ascending inside a row (never compared across a row boundary).  MGS_ERR_INVALID: a NULL argument,
+ * index_bits neither 32 nor 64, a violated rule — the message names the lowest offending row and the kind of violation in
+ * mgs_csr_upload's wording, so it is deterministic. */
+int mgs_csr_from_device(mgs_ctx *ctx, int rows, int cols, int64_t nnz, const void *rowptr_dev, const void *col_dev,
+                        int index_bits, const void *val_dev, mgs_csr **out);
+/* Triples (row[k], col[k], val[k]), 0-based, in any order, in device memory — readMatrix's assembly, src/common/MatrixIO.cpp:12-37
+ * (bucket by row, sort each row), on the device; summing duplicates has no reference counterpart (the reference keeps them apart).
+ * Entries with equal (row, col) are summed in input order (ascending k), the sum starting from the first value itself: a lone -0.0
+ * stays -0.0 and the result is bit-reproducible, whatever the order the device handled the triples in.  Explicit zeros and sums that
+ * cancel stay entries (the pattern is what mgs_hier_refresh keys on).  Columns come out ascending inside a row.
+ * keep_map != 0: the matrix keeps the sorted source positions (4 B per triple) and the run boundaries (4 B per entry + 4) for
+ * mgs_csr_update_values_coo_dev; mgs_csr_destroy frees them.
+ * MGS_ERR_INVALID: a NULL argument; index_bits neither 32 nor 64; a row outside [0, rows) or a column outside [0, cols) (the message
+ * names the lowest such triple); a row that receives more than MGS_COO_MAX_ROW triples, duplicates included (the message names the
+ * lowest such row) — a documented limit: such a row is sorted by one workgroup in 64 KB of LDS. */
+#define MGS_COO_MAX_ROW 8192   /* most triples (duplicates included) one row may receive */
+int mgs_csr_from_coo_device(mgs_ctx *ctx, int rows, int cols, int64_t ntrip, const void *row_dev, const void *col_dev,
+                            int index_bits, const void *val_dev, int keep_map, mgs_csr **out);
+/* New triple values for a matrix assembled with keep_map, same triples in the same input order: the gather kernel of the assembly
+ * runs again through the kept map into A's existing val array, so the result is bit-identical to assembling from scratch.  Enqueued
+ * on the context's stream and not synchronised, like mgs_csr_update_values_dev; the arrays do not move, so hierarchies and cached
+ * graphs stay valid (follow with mgs_hier_refresh).  Nearest reference line: MatrixIO.cpp:12-37, which the reference reruns per
+ * matrix; re-assembling values only has no reference counterpart.
+ * MGS_ERR_STATE: the matrix keeps no map.  MGS_ERR_INVALID: A or the values NULL; ntrip differs from the number of triples the
+ * matrix was assembled from; a value-carrying pattern code (option "valcode"). */
+int mgs_csr_update_values_coo_dev(mgs_csr *A, const void *val_dev, int64_t ntrip);
+/* diagnostics (no reference counterpart): out[0] triples the matrix was assembled from (0: not from COO / no map kept), out[1]
+ * entries, out[2] most triples in one row (0: not from COO), out[3] bytes the kept map occupies.  MGS_ERR_INVALID: NULL argument. */
+int mgs_csr_coo_info(const mgs_csr *A, int64_t out[4]);
 /* Synthetic operator generated on device: 7-point 3-D Poisson on an
  * N^3 grid, 3-D extension of src/common/poisson.cpp:11-33 (diag 6, off-diagonals −1,
  * row e=(i*N+j)*N+k, ascending columns).  Rows of planes [plane_lo, plane_hi) only

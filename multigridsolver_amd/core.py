@@ -23,6 +23,7 @@ class Context:
         h = C.c_void_p()
         check(lib().mgs_ctx_create(device, C.c_void_p(stream) if stream else None, C.byref(h)))
         self.h = h
+        self.device = int(device)
         self._cbs = []
 
     def close(self):
@@ -101,6 +102,38 @@ def write_mtx(path, rows, cols, rowptr, col, val):
     check(lib().mgs_mtx_write(path.encode(), rows, cols, len(col), _ip(rowptr), _ip(col), _dp(val)))
 
 
+_INDEX_BITS = {"int32": 32, "int64": 64, "<i4": 32, "<i8": 64}
+_FLOAT64 = ("float64", "<f8")
+
+
+def _dev_array(ctx, a, name, index):
+    """(device pointer, element count, index bits or 0) of an array that lives on ctx's device: a torch tensor, an object with
+    __cuda_array_interface__, or (values only) a Vec.  Wrong dtype, layout or device: TypeError — nothing is converted."""
+    want = "int32 or int64" if index else "float64"
+    if isinstance(a, Vec):
+        if index:
+            raise TypeError(f"{name}: a Vec holds float64 values, {want} indices expected")
+        return a.ptr, len(a), 0
+    if hasattr(a, "data_ptr") and hasattr(a, "is_contiguous"):          # torch tensor
+        dt = str(a.dtype).replace("torch.", "")
+        if not a.is_cuda or a.device.index != ctx.device:
+            raise TypeError(f"{name}: tensor on {a.device}, the context runs on device {ctx.device}")
+        if a.dim() != 1 or not a.is_contiguous():
+            raise TypeError(f"{name}: a contiguous one-dimensional tensor expected")
+        ptr, n = a.data_ptr(), a.numel()
+    elif hasattr(a, "__cuda_array_interface__"):
+        cai = a.__cuda_array_interface__
+        dt, shape = cai["typestr"], tuple(cai["shape"])
+        if len(shape) != 1 or cai.get("strides") not in (None, (int(dt[2:]),)):
+            raise TypeError(f"{name}: a contiguous one-dimensional array expected")
+        ptr, n = int(cai["data"][0] or 0), shape[0]
+    else:
+        raise TypeError(f"{name}: a torch tensor, an object with __cuda_array_interface__" + ("" if index else " or a Vec") + f" expected, got {type(a).__name__}")
+    if (dt not in _INDEX_BITS) if index else (dt not in _FLOAT64):
+        raise TypeError(f"{name}: dtype {dt}, {want} expected (nothing is converted silently)")
+    return ptr, n, _INDEX_BITS[dt] if index else 0
+
+
 class Csr:
     def __init__(self, ctx, h, owned=True):
         self.ctx, self.h, self.owned = ctx, h, owned
@@ -123,6 +156,77 @@ class Csr:
     @staticmethod
     def from_mtx(ctx, path):
         return Csr.upload(ctx, *read_mtx(path))
+
+    @staticmethod
+    def from_device(ctx, rows, cols, rowptr, col, val):
+        """CSR arrays that live on the context's device (mgs_csr_from_device): int32 or int64 indices, float64 values, checked on the
+        device by mgs_csr_upload's rules and copied.  Make them visible first (e.g. torch.cuda.synchronize())."""
+        rp, nrp, bits = _dev_array(ctx, rowptr, "rowptr", True)
+        ci, nnz, cbits = _dev_array(ctx, col, "col", True)
+        v, nv, _ = _dev_array(ctx, val, "val", False)
+        if cbits != bits:
+            raise TypeError(f"rowptr holds {bits}-bit indices, col {cbits}-bit ones")
+        if nrp != rows + 1 or nv != nnz:
+            raise ValueError(f"rowptr has {nrp} entries for {rows} rows, col {nnz} and val {nv}")
+        h = C.c_void_p()
+        check(lib().mgs_csr_from_device(ctx.h, rows, cols, nnz, C.c_void_p(rp), C.c_void_p(ci), bits, C.c_void_p(v), C.byref(h)), ctx.h)
+        return Csr(ctx, h)
+
+    @staticmethod
+    def from_coo_device(ctx, rows, cols, row, col, val, keep_map=False):
+        """triples on the context's device, any order, duplicates summed in input order (mgs_csr_from_coo_device); keep_map=True keeps
+        what update_values_coo needs"""
+        ri, n, bits = _dev_array(ctx, row, "row", True)
+        ci, nc, cbits = _dev_array(ctx, col, "col", True)
+        v, nv, _ = _dev_array(ctx, val, "val", False)
+        if cbits != bits:
+            raise TypeError(f"row holds {bits}-bit indices, col {cbits}-bit ones")
+        if nc != n or nv != n:
+            raise ValueError(f"row has {n} entries, col {nc} and val {nv}")
+        h = C.c_void_p()
+        check(lib().mgs_csr_from_coo_device(ctx.h, rows, cols, n, C.c_void_p(ri), C.c_void_p(ci), bits, C.c_void_p(v), int(bool(keep_map)), C.byref(h)), ctx.h)
+        return Csr(ctx, h)
+
+    @staticmethod
+    def from_torch(ctx, t, keep_map=False):
+        """a 2-D float64 torch.sparse_csr or torch.sparse_coo tensor (coalesced or not) on the context's device; torch's current stream
+        on that device is synchronised first"""
+        import torch
+        if t.dim() != 2 or t.layout not in (torch.sparse_csr, torch.sparse_coo):
+            raise TypeError(f"from_torch: a 2-D sparse_csr or sparse_coo tensor expected, got layout {t.layout} with {t.dim()} dimensions")
+        if t.dtype != torch.float64:
+            raise TypeError(f"from_torch: dtype {t.dtype}, float64 expected (nothing is converted silently)")
+        if not t.is_cuda or t.device.index != ctx.device:
+            raise TypeError(f"from_torch: tensor on {t.device}, the context runs on device {ctx.device}")
+        rows, cols = t.shape
+        if t.layout == torch.sparse_csr:
+            arrays = (t.crow_indices().contiguous(), t.col_indices().contiguous(), t.values().contiguous())
+        else:
+            if t.sparse_dim() != 2:
+                raise TypeError("from_torch: a sparse_coo tensor with two sparse dimensions expected")
+            idx = t._indices()
+            arrays = (idx[0].contiguous(), idx[1].contiguous(), t._values().contiguous())
+        torch.cuda.current_stream(t.device).synchronize()
+        if t.layout == torch.sparse_csr:
+            return Csr.from_device(ctx, rows, cols, *arrays)
+        return Csr.from_coo_device(ctx, rows, cols, *arrays, keep_map=keep_map)
+
+    def update_values_coo(self, val):
+        """new triple values (same triples, same order) for a matrix assembled with keep_map=True, through the kept map into the
+        existing value array (mgs_csr_update_values_coo_dev; enqueued, not synchronised); returns self.  Follow with Hierarchy.refresh()."""
+        v, n, _ = _dev_array(self.ctx, val, "val", False)
+        check(lib().mgs_csr_update_values_coo_dev(self.h, C.c_void_p(v), n), self.ctx.h)
+        return self
+
+    def coo_info(self):
+        out = (C.c_int64 * 4)(); check(lib().mgs_csr_coo_info(self.h, out), self.ctx.h)
+        return dict(zip(["triples", "entries", "max_row_triples", "map_bytes"], [int(v) for v in out]))
+
+    def device_ptrs(self):
+        """(rowptr, col, val) device addresses of the library's own arrays (mgs_csr_device_ptrs)"""
+        a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        check(lib().mgs_csr_device_ptrs(self.h, C.byref(a), C.byref(b), C.byref(c)), self.ctx.h)
+        return a.value or 0, b.value or 0, c.value or 0
 
     @property
     def shape(self):

@@ -121,6 +121,11 @@ typedef Vector VectorXd;
 class DeviceMatrix {
   std::shared_ptr<mgs_csr> a_;
   int rows_ = 0, cols_ = 0;
+  static DeviceMatrix adopt(mgs_csr *p, int rows, int cols) {
+    DeviceMatrix M; M.rows_ = rows; M.cols_ = cols;
+    M.a_ = std::shared_ptr<mgs_csr>(p, [](mgs_csr *q) { mgs_csr_destroy(q); });
+    return M;
+  }
  public:
   DeviceMatrix() {}
   DeviceMatrix(const SMatrix &A) : rows_(A.rows()), cols_(A.cols()) {
@@ -128,6 +133,21 @@ class DeviceMatrix {
     check(mgs_csr_upload(context(), A.rows(), A.cols(), A.nonZeros(), A.rowptr.data(), A.col.data(), A.val.data(), &p), context());
     a_ = std::shared_ptr<mgs_csr>(p, [](mgs_csr *q) { mgs_csr_destroy(q); });
   }
+  // Arrays that already live in device memory (mgs.h: mgs_csr_from_device / mgs_csr_from_coo_device; index_bits 32 or 64).  The
+  // inputs are checked on the device and copied; bad input throws Error(MGS_ERR_INVALID).  Triples may come in any order and
+  // duplicates are summed in input order; keep_map keeps what update_values_coo needs.
+  static DeviceMatrix fromDevice(int rows, int cols, int64_t nnz, const void *rowptr, const void *col, int index_bits, const void *val) {
+    mgs_csr *p = nullptr;
+    check(mgs_csr_from_device(context(), rows, cols, nnz, rowptr, col, index_bits, val, &p), context());
+    return adopt(p, rows, cols);
+  }
+  static DeviceMatrix fromCooDevice(int rows, int cols, int64_t ntrip, const void *row, const void *col, int index_bits, const void *val, bool keep_map = false) {
+    mgs_csr *p = nullptr;
+    check(mgs_csr_from_coo_device(context(), rows, cols, ntrip, row, col, index_bits, val, keep_map ? 1 : 0, &p), context());
+    return adopt(p, rows, cols);
+  }
+  // new triple values (device memory, same triples in the same order) through the kept map; enqueued, not synchronised
+  void update_values_coo(const void *val_dev, int64_t ntrip) { check(mgs_csr_update_values_coo_dev(a_.get(), val_dev, ntrip), context()); }
   int rows() const { return rows_; }
   int cols() const { return cols_; }
   mgs_csr *handle() const { return a_.get(); }

@@ -322,6 +322,20 @@ int mgs_csr_upload(mgs_ctx *ctx, int rows, int cols, int64_t nnz, const int *row
   *out = A;
   return MGS_OK;
 }
+// matrices that already live in device memory (ingest.hip)
+int mgs_csr_from_device(mgs_ctx *ctx, int rows, int cols, int64_t nnz, const void *rowptr_dev, const void *col_dev, int index_bits, const void *val_dev, mgs_csr **out) {
+  return k_csr_from_device(ctx, rows, cols, nnz, rowptr_dev, col_dev, index_bits, val_dev, out);
+}
+int mgs_csr_from_coo_device(mgs_ctx *ctx, int rows, int cols, int64_t ntrip, const void *row_dev, const void *col_dev, int index_bits, const void *val_dev, int keep_map,
+                            mgs_csr **out) {
+  return k_csr_from_coo_device(ctx, rows, cols, ntrip, row_dev, col_dev, index_bits, val_dev, keep_map, out);
+}
+int mgs_csr_coo_info(const mgs_csr *A, int64_t out[4]) {
+  MGS_CHECK(nullptr, A && out, MGS_ERR_INVALID, "mgs_csr_coo_info: NULL argument");
+  out[0] = A->coo_map ? A->coo_ntrip : 0; out[1] = A->nnz; out[2] = A->coo_max_row;
+  out[3] = A->coo_map ? (int64_t)sizeof(int) * (A->coo_ntrip + A->nnz + 1) : 0;
+  return MGS_OK;
+}
 int mgs_csr_download(const mgs_csr *A, int *rowptr, int *col, double *val) {
   mgs_ctx *ctx = A->ctx;
   if (rowptr) MGS_HIP(ctx, hipMemcpyAsync(rowptr, A->rowptr, sizeof(int) * ((size_t)A->rows + 1), hipMemcpyDeviceToHost, ctx->stream));
@@ -389,8 +403,19 @@ int mgs_csr_update_values_dev(mgs_csr *A, const void *device_val, int64_t nnz) {
   if (nnz && device_val != (const void *)A->val) MGS_HIP(ctx, hipMemcpyAsync(A->val, device_val, sizeof(double) * (size_t)nnz, hipMemcpyDeviceToDevice, ctx->stream));
   return MGS_OK;
 }
+int mgs_csr_update_values_coo_dev(mgs_csr *A, const void *val_dev, int64_t ntrip) {
+  MGS_CHECK(nullptr, A, MGS_ERR_INVALID, "mgs_csr_update_values_coo_dev: NULL matrix");
+  mgs_ctx *ctx = A->ctx;
+  MGS_CHECK(ctx, A->coo_map, MGS_ERR_STATE, "mgs_csr_update_values_coo_dev: the matrix keeps no triple map (mgs_csr_from_coo_device with keep_map != 0 does)");
+  MGS_CHECK(ctx, ntrip == A->coo_ntrip, MGS_ERR_INVALID, "mgs_csr_update_values_coo_dev: %lld values given, the matrix was assembled from %lld triples", (long long)ntrip,
+            (long long)A->coo_ntrip);
+  MGS_TRY(update_values_check(A, val_dev, A->nnz, "mgs_csr_update_values_coo_dev"));
+  return k_csr_update_values_coo(A, val_dev);
+}
 int mgs_csr_destroy(mgs_csr *A) {
   if (!A) return MGS_OK;
+  if (A->coo_src) mgs_hip_free(A->coo_src);
+  if (A->coo_run) mgs_hip_free(A->coo_run);
   if (A->owns) { if (A->rowptr) mgs_hip_free(A->rowptr); if (A->col) mgs_hip_free(A->col); if (A->val) mgs_hip_free(A->val); }
   if (A->blkptr) mgs_hip_free(A->blkptr);
   if (A->origin) mgs_hip_free(A->origin);

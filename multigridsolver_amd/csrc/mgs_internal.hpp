@@ -121,6 +121,12 @@ struct mgs_csr {
                                   // these instead of val (products widened to FP64 before they are added)
   int *origin = nullptr;   // coarse operators built by the device setup: the finest-level row each row descends from (its aggregate's
                            // leader, chained through the levels) — the index space the matching's tie-breaks work in; NULL = identity
+  // matrices assembled from device triples (ingest.hip); the map is kept on request (keep_map) for mgs_csr_update_values_coo_dev
+  bool coo_map = false;
+  int *coo_src = nullptr;   // coo_ntrip: source position of every triple in (row, column, input order) order
+  int *coo_run = nullptr;   // nnz + 1: first sorted triple of every entry; entry e sums coo_src[coo_run[e] .. coo_run[e + 1])
+  int64_t coo_ntrip = 0;
+  int coo_max_row = 0;      // most triples one row received
 };
 
 struct mgs_vec {
@@ -414,6 +420,11 @@ int k_galerkin_agg_ext(const mgs_csr *A, const mgs_xfer *T, const int *halo_map_
 int k_xfer_from_agg_host(mgs_ctx *ctx, int n_fine, int n_coarse, const int *agg_host, mgs_xfer **out);
 int k_galerkin_general(const mgs_csr *A, const mgs_xfer *T, mgs_csr **out);
 int k_pairwise_aggregate(const mgs_csr *A, double ktg, int npass, double tou, mgs_xfer **T_out, mgs_csr **Ac_out, const int *zone_dev = nullptr);
+// (ingest.hip) matrices from device memory: checked CSR copy, COO assembly, re-assembly of the values through the kept map
+int k_csr_from_device(mgs_ctx *ctx, int rows, int cols, int64_t nnz, const void *rowptr_dev, const void *col_dev, int index_bits, const void *val_dev, mgs_csr **out);
+int k_csr_from_coo_device(mgs_ctx *ctx, int rows, int cols, int64_t ntrip, const void *row_dev, const void *col_dev, int index_bits, const void *val_dev, int keep_map,
+                          mgs_csr **out);
+int k_csr_update_values_coo(mgs_csr *A, const void *val_dev);
 
 // helpers (mgs_api.hip)
 int mgs_csr_alloc(mgs_ctx *ctx, int rows, int cols, int64_t nnz, mgs_csr **out);
