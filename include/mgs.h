@@ -521,6 +521,27 @@ int mgs_hier_group_info(const mgs_hier *h, int level, int64_t out[4]);
  * leaves its row-block group (other entries are not written).  *nodiag (may be NULL): 1 if the pass ran on the operand without Â's
  * diagonal entries (option "pre_nodiag": coded row blocks stream val_nd and a byte per row; the result has the same bits either way).  Enqueued on the context's stream. */
 int mgs_hier_pre_pass(mgs_hier *h, int level, const mgs_vec *b, mgs_vec *t, mgs_vec *r, mgs_vec *rc, int *nodiag);
+/* The fused post pass of level `level` alone, into the caller's vectors (tests and diagnostics): the operand, the kernel and the launch are
+ * the ones the level's own cycle uses under the options as they stand — merged A·P, aggregate-mapped A (ω/a_ii from the streamed diagonal
+ * with option "diag_from_values") or the gather form on A; FP64 or FP32 operand values; option "group_sweep" (whole-level launches of a grouped level).
+ *   xin == NULL, the t-form:   bvec holds t = b + r,           x_i = pe_i + d_i·(t_i − s_i)
+ *   xin given, the (r, b)-form: bvec holds r and xin holds b,  x_i = (d_i·b_i + pe_i) + d_i·(r_i − s_i)
+ * with s_i = Σ_k v_ik·ec[c_ik] over the row of the operand in stored order (summed from 0, one rounding per product and per sum; an entry
+ * whose column lies outside every aggregate adds nothing), pe_i = ec[agg_i] (0 for a row outside every aggregate) and d_i = fl(ω·fl(1/a_ii)).
+ * Either form may be asked of any eligible level, whichever its own cycle runs.
+ * range (may be NULL: the whole level) = {blk_lo, blk_hi, gap_at, gap_len}: the launch covers blk_hi − blk_lo row blocks of 256 rows starting at
+ * blk_lo, and those at or behind gap_at are shifted by gap_len — the interior / boundary split of a row shard; INT_MAX, 0: no gap.  Rows of
+ * other row blocks are not written.
+ * info: [0] operand (0 A through the column-to-aggregate map, 1 aggregate-mapped A, 2 merged A·P), [1] kernel (0 gather kernel, 1 pattern-coded
+ * kernel FP64, 2 the same on FP32 values, 3 FP64 swept group by group), [2] gather width U, [3] the kernel's flags word (bit 0: no row is longer than U, one
+ * step without a loop; bit 1 option "stage_unroll"; bit 2 option "rowptr_scan"; 0 for the gather kernel), [4] / [5] LDS budget of a row block in values / ints,
+ * [6] row blocks of the operand with more entries than [4] (they walk their rows from global memory), [7] 1 if the level's own cycle runs the t-form
+ * (grouped pre pass).  [1..5] are −1 / 0 when the range is empty.
+ * Served: unsharded levels with a coarser level and an aggregation transfer that run the fused passes (V(1,1), option "fuse").  MGS_ERR_INVALID: NULL
+ * argument (xin and range excepted), level out of range, vectors shorter than the level / its aggregates, a range that leaves the level;
+ * MGS_ERR_STATE: before mgs_hier_finalize, a general P, a sharded or value-coded level, a level that does not run the fused passes.
+ * Enqueued on the context's stream; the host waits for the block bounds behind the launch ([6]), the caller synchronizes before reading x. */
+int mgs_hier_post_pass(mgs_hier *h, int level, const mgs_vec *bvec, const mgs_vec *xin, const mgs_vec *ec, mgs_vec *x, const int range[4], int64_t info[8]);
 /* hipGraph state of the cycle (diagnostics): out[0] captured cycles cached, out[1] = 1 on the native RCCL transport, out[2] = 1 if
  * capturing the native cycle failed (eager launches since), out[3] eager native cycles run before the first capture.
  * Option "native_graph" (default 1): capture the row-sharded cycle including its RCCL exchanges (two eager cycles first).

@@ -67,6 +67,7 @@ PROTOTYPES = {
     "mgs_hier_graph_info": (C.c_int, [C.c_void_p, c_i64_p]),
     "mgs_hier_group_info": (C.c_int, [C.c_void_p, C.c_int, c_i64_p]),
     "mgs_hier_pre_pass": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "mgs_hier_post_pass": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
     "mgs_csr_update_values": (C.c_int, [C.c_void_p, c_dbl_p, C.c_int64]),
     "mgs_csr_update_values_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "mgs_csr_from_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),

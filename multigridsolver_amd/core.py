@@ -508,6 +508,14 @@ class Hierarchy:
         nd = C.c_int(0); check(lib().mgs_hier_pre_pass(self.h, level, b.h, t.h, r.h, rc.h, C.byref(nd)), self.ctx.h)
         return bool(nd.value)
 
+    def post_pass(self, level, bvec, xin, ec, x, range=None):
+        """the fused post pass of one level alone (mgs_hier_post_pass): xin None = t-form (bvec holds t = b + r), else bvec = r and xin = b;
+        range = (blk_lo, blk_hi, gap_at, gap_len) or None for the whole level.  Returns what the launcher decided."""
+        rg = (C.c_int * 4)(*[int(v) for v in range]) if range is not None else None
+        out = (C.c_int64 * 8)()
+        check(lib().mgs_hier_post_pass(self.h, level, bvec.h, xin.h if xin is not None else None, ec.h, x.h, rg, out), self.ctx.h)
+        return dict(zip(["operand", "kernel", "U", "flags", "capv", "capi", "blocks_over_budget", "t_form"], [int(v) for v in out]))
+
     def graph_info(self):
         out = (C.c_int64 * 4)(); check(lib().mgs_hier_graph_info(self.h, out), self.ctx.h)
         return dict(zip(["captured_cycles", "native_transport", "native_capture_failed", "native_eager_runs"], [int(v) for v in out]))

@@ -1443,6 +1443,8 @@ static bool use_rowcode(const mgs_csr *A, const mgs_rowcode *c, bool any = false
   return c && A->ctx->opt_rowcode && A->blkptr && A->lds_cap > 0 && A->max_row_len <= 64 &&
          (any || (double)c->coded_blocks >= 0.5 * c->nblocks);
 }
+// flags word of the coded kernels (coded_block_body): bit 0 no row is longer than the gather width, bit 1 option stage_unroll, bit 2 option rowptr_scan
+#define KFLAGS_(UU) ((A->max_row_len <= (UU) ? 1 : 0) | (ctx->opt_stage_unroll ? 2 : 0) | (ctx->opt_rowptr_scan ? 4 : 0))
 // LDS sizing of the float forms: capv a multiple of 4 (the integer region behind the values stays 16-byte aligned for the int4 stores of
 // the uncoded blocks), whose index slice may reach capv + 6 entries (both ends of the slice aligned to 4)
 static inline int capv_f32(const mgs_csr *A) { return (A->lds_cap + 3) & ~3; }
@@ -1465,11 +1467,16 @@ static int launch_coded_f32(const mgs_csr *A, const mgs_rowcode *c, int op, cons
 #define F_(O, UU) hipLaunchKernelGGL((csr_rowblock_coded_kernel<O, UU, false, false, float>), grid, dim3(RB), lds, ctx->stream, A->rows, A->rowptr, idx, A->val32, \
                                      c ? c->pid : nullptr, c ? c->tptr : nullptr, c ? c->tab : nullptr, x, b, dinv, 0.0, xin, agg, out, capv, \
                                      (ctx->opt_nt_store > 0 && A->rows >= ctx->opt_nt_store) ? -capi : capi, bm, A->blkptr, nullptr, 0x7fffffff, nullptr, nullptr, \
-                                     nullptr, nullptr, (A->rows + RB - 1) / RB, (A->max_row_len <= UU ? 1 : 0) | (ctx->opt_stage_unroll ? 2 : 0) | (ctx->opt_rowptr_scan ? 4 : 0))
+                                     nullptr, nullptr, (A->rows + RB - 1) / RB, KFLAGS_(UU))
 #define FU_(O) do { if (u == 4) F_(O, 4); else if (u == 7) F_(O, 7); else F_(O, 8); } while (0)
+  const bool u5 = op == FUSE_POST_MAPPED && mean_len > 4.5 && mean_len <= 5.5 && A->max_row_len <= 10;
   if (op == MGS_OP_RESIDUAL) FU_(MGS_OP_RESIDUAL);
-  else if (mean_len > 4.5 && mean_len <= 5.5 && A->max_row_len <= 10) F_(FUSE_POST_MAPPED, 5);
+  else if (u5) F_(FUSE_POST_MAPPED, 5);
   else FU_(FUSE_POST_MAPPED);
+  if (ctx->report && op == FUSE_POST_MAPPED) {
+    const int uu = u5 ? 5 : u;
+    *ctx->report = {2, uu, KFLAGS_(uu), capv, capi};
+  }
 #undef FU_
 #undef F_
   MGS_HIP(ctx, hipGetLastError());
@@ -1492,7 +1499,7 @@ static int launch_coded(const mgs_csr *A, const mgs_rowcode *c, int op, const in
 #define C_(O, UU, H, V) hipLaunchKernelGGL((csr_rowblock_coded_kernel<O, UU, H, V>), grid, dim3(RB), lds, ctx->stream, A->rows, A->rowptr, idx, A->val, \
                                            c->pid, c->tptr, c->tab, x, b, dinv, (O == FUSE_POST_MAPPED && A->dpos) ? A->dpos_omega : omega, xin, agg, out, capv, \
                                            (ctx->opt_nt_store > 0 && A->rows >= ctx->opt_nt_store) ? -capi : capi, bm, A->blkptr, hv, split, c->vtab, O == FUSE_POST_MAPPED ? A->dpos : nullptr, \
-                                           O == MGS_OP_SPMV ? A->dot_w1 : nullptr, O == MGS_OP_SPMV ? A->dot_part : nullptr, (A->rows + RB - 1) / RB, (A->max_row_len <= UU ? 1 : 0) | (ctx->opt_stage_unroll ? 2 : 0) | (ctx->opt_rowptr_scan ? 4 : 0))
+                                           O == MGS_OP_SPMV ? A->dot_w1 : nullptr, O == MGS_OP_SPMV ? A->dot_part : nullptr, (A->rows + RB - 1) / RB, KFLAGS_(UU))
   // group sweep (views with A->sweep set; plain index codes, no halo): one workgroup per row-block group of the grouped pre pass
   BlockMap gbm; dim3 ggrid(1);
   const bool sweep = A->sweep && !hv && !c->vtab && op == FUSE_POST_MAPPED;
@@ -1500,18 +1507,23 @@ static int launch_coded(const mgs_csr *A, const mgs_rowcode *c, int op, const in
 #define CG_(O, UU) hipLaunchKernelGGL((csr_rowblock_coded_group_kernel<O, UU, false, false>), ggrid, dim3(RB), lds, ctx->stream, A->rows, A->rowptr, idx, A->val, \
                                       c->pid, c->tptr, c->tab, x, b, dinv, (O == FUSE_POST_MAPPED && A->dpos) ? A->dpos_omega : omega, xin, agg, out, capv, \
                                       (ctx->opt_nt_store > 0 && A->rows >= ctx->opt_nt_store) ? -capi : capi, gbm, A->blkptr, hv, split, c->vtab, O == FUSE_POST_MAPPED ? A->dpos : nullptr, \
-                                      nullptr, nullptr, (A->rows + RB - 1) / RB, (A->max_row_len <= UU ? 1 : 0) | (ctx->opt_stage_unroll ? 2 : 0) | (ctx->opt_rowptr_scan ? 4 : 0), A->sweep->gdesc)
+                                      nullptr, nullptr, (A->rows + RB - 1) / RB, KFLAGS_(UU), A->sweep->gdesc)
 #define CH_(O, UU) do { if (sweep && O == FUSE_POST_MAPPED) CG_(FUSE_POST_MAPPED, UU); \
                         else if (hv) { if (c->vtab) C_(O, UU, true, true); else C_(O, UU, true, false); } \
                         else { if (c->vtab) C_(O, UU, false, true); else C_(O, UU, false, false); } } while (0)
 #define CU_(O) do { if (u == 4) CH_(O, 4); else if (u == 7) CH_(O, 7); else CH_(O, 8); } while (0)
+  const bool u5 = mean_len > 4.5 && mean_len <= 5.5 && A->max_row_len <= 10;      // post pass only
   switch (op) {
     case MGS_OP_SPMV: CU_(MGS_OP_SPMV); break;
     case MGS_OP_RESIDUAL: CU_(MGS_OP_RESIDUAL); break;
     case MGS_OP_JACOBI: CU_(MGS_OP_JACOBI); break;
     default:
       // A·P of a 7-point operator with aggregates of four has 5 entries per row: one unrolled step of 5 instead of 7
-      if (mean_len > 4.5 && mean_len <= 5.5 && A->max_row_len <= 10) CH_(FUSE_POST_MAPPED, 5); else CU_(FUSE_POST_MAPPED);
+      if (u5) CH_(FUSE_POST_MAPPED, 5); else CU_(FUSE_POST_MAPPED);
+      if (ctx->report) {
+        const int uu = u5 ? 5 : u;
+        *ctx->report = {sweep ? 3 : 1, uu, KFLAGS_(uu), capv, capi};
+      }
       break;
   }
 #undef CU_
@@ -1836,6 +1848,7 @@ int mgs_launch_fused_range(const mgs_csr *A, int which, const double *wd, const 
   }
   if (which == FUSE_POST_MAPPED && use_rowcode(A, A->code))      // A is the view whose col/code are the aggregate-mapped ones
     return launch_coded(A, A->code, FUSE_POST_MAPPED, A->col, ec, bvec, wd, 0.0, xin, agg, out, grid, bm);
+  if (ctx->report && which != FUSE_PRE) *ctx->report = {0, 8, 0, cap, cap + 2};      // the gather kernel: steps of 8, index slice beside the values
   if (which == FUSE_POST_MAPPED) hipLaunchKernelGGL((csr_rowblock_fused_kernel<FUSE_POST_MAPPED>), grid, dim3(RB), lds, ctx->stream, A->rows, A->rowptr, A->col, A->val, wd, bvec, xin, agg, ec, out, out2, cap, bm, hv, A->ctx->opt_blkptr ? A->blkptr : nullptr);
   else if (which == FUSE_PRE) hipLaunchKernelGGL((csr_rowblock_fused_kernel<FUSE_PRE>), grid, dim3(RB), lds, ctx->stream, A->rows, A->rowptr, A->col, A->val, wd, bvec, xin, agg, ec, out, out2, cap, bm, hv, A->ctx->opt_blkptr ? A->blkptr : nullptr);
   else hipLaunchKernelGGL((csr_rowblock_fused_kernel<FUSE_POST>), grid, dim3(RB), lds, ctx->stream, A->rows, A->rowptr, A->col, A->val, wd, bvec, xin, agg, ec, out, out2, cap, bm, hv, A->ctx->opt_blkptr ? A->blkptr : nullptr);

@@ -651,6 +651,37 @@ static int level_refresh_f32(mgs_hier *h, mgs_level &L, bool vals_changed) {
   return MGS_OK;
 }
 
+// The operands of level l's two fused passes under the options as they stand — the ONE place that chooses them (cycle_level and
+// mgs_hier_post_pass both ask here).  Setup-time operands: Â = A·diag(wd) makes the pre pass the plain residual kernel with x = b (one
+// gather per entry); A·P (or col_agg = the coarse column of every entry) lets the post pass gather e_c directly.  On a shard the halo
+// columns of Â read the payload buffer (the pattern-coded kernel knows that split); those of A·P read e_c's own halo.
+struct fused_operands {
+  mgs_csr Ahat, Amap;      // views: the pre pass's operand; the post pass's (meaningful only where `operands` holds)
+  bool f32 = false;        // both passes read the FP32 copies of the stored values (float forms of the same kernels), or neither does
+  bool operands = false;   // the passes run on the setup-time operands (false: the gather forms on A itself)
+  int post_form = 0;       // post pass on: 0 A with the column-to-aggregate map (gather form), 1 aggregate-mapped A, 2 merged A·P
+  bool grouped = false;    // the level qualifies for the grouped pre pass, whose post pass is the t-form (a row shard adds conditions of its own)
+  const mgs_groups *sweep = nullptr;   // option group_sweep: the grouped level's post pass sweeps these row-block groups
+};
+static void level_fused_operands(const mgs_hier *h, int l, bool halo, fused_operands &o) {
+  const mgs_ctx *ctx = h->ctx;
+  const mgs_level &L = h->lev[l];
+  mgs_csr &Ahat = o.Ahat, &Amap = o.Amap;
+  // Â's code: its own when the tuples carry values or halo tags, A's index-only code otherwise
+  Ahat = *L.A; Ahat.val = L.val_wd; Ahat.owns = false;
+  Ahat.code = halo ? L.code_pre : ((L.A->code && L.A->code->vtab) || L.code_hat ? L.code_hat : L.A->code);
+  Amap = *L.A; Amap.val = L.A->val; Amap.col = L.col_agg; Amap.code = L.code_agg; Amap.owns = false;
+  if (ctx->opt_diag_from_values && L.dpos) { Amap.dpos = L.dpos; Amap.dpos_omega = h->omega; }   // t-form post pass: ω/a_ii from the streamed values
+  const bool merged = ctx->opt_merge_ap && L.AP;
+  if (merged) { Amap = *L.AP; Amap.code = L.code_ap; Amap.owns = false; }      // A·P, merged: fewer entries, wd read per row
+  o.f32 = level_runs_f32(h, l) && !halo;
+  if (o.f32) { Ahat.val32 = L.val_wd32; Amap.val32 = L.ap_val32; }
+  o.operands = ctx->opt_fuse_operands && L.val_wd && (L.col_agg || merged) && (!halo || mgs_rowcode_usable(&Ahat, true));
+  o.post_form = !o.operands ? 0 : (merged ? 2 : 1);
+  o.grouped = ctx->opt_fuse_restrict && o.operands && L.grp && !(Ahat.code && Ahat.code->vtab);
+  o.sweep = (o.grouped && (ctx->opt_group_sweep & 1)) ? L.grp : nullptr;
+}
+
 extern "C" {
 
 int mgs_hier_create(mgs_ctx *ctx, const mgs_csr *A, double omega, int nu1, int nu2, mgs_hier **out) {
@@ -1095,12 +1126,60 @@ int mgs_hier_pre_pass(mgs_hier *h, int level, const mgs_vec *b, mgs_vec *t, mgs_
   const bool plain = L.A->cols == L.A->rows && !L.nx && !(L.A->code && L.A->code->vtab) && !L.code_hat;
   MGS_CHECK(ctx, ctx->opt_fuse_restrict && L.grp && L.val_wd && plain, MGS_ERR_STATE, "mgs_hier_pre_pass: level %d does not run the grouped pre pass (see mgs_hier_group_info), or is sharded / value-coded", level);
   MGS_CHECK(ctx, b->n >= L.n && t->n >= L.n && r->n >= L.n && rc->n >= L.T->n_coarse, MGS_ERR_INVALID, "mgs_hier_pre_pass: vectors shorter than the level (%d rows, %d aggregates)", L.n, L.T->n_coarse);
-  mgs_csr Ahat = *L.A; Ahat.val = L.val_wd; Ahat.owns = false;
-  const bool f32 = level_runs_f32(h, level);
-  if (f32) Ahat.val32 = L.val_wd32;
-  const bool nd = level_pre_nodiag(h, L, false, f32);
+  fused_operands ops;
+  level_fused_operands(h, level, false, ops);
+  const bool nd = level_pre_nodiag(h, L, false, ops.f32);
   if (nodiag) *nodiag = nd ? 1 : 0;
-  return mgs_launch_group_pre(&Ahat, L.grp, L.T, b->d, b->d, t->d, r->d, rc->d, nullptr, L.A->rows, nd ? L.val_nd : nullptr, L.nd_code, L.nd_omega);
+  return mgs_launch_group_pre(&ops.Ahat, L.grp, L.T, b->d, b->d, t->d, r->d, rc->d, nullptr, L.A->rows, nd ? L.val_nd : nullptr, L.nd_code, L.nd_omega);
+}
+int mgs_hier_post_pass(mgs_hier *h, int level, const mgs_vec *bvec, const mgs_vec *xin, const mgs_vec *ec, mgs_vec *x, const int range[4], int64_t info[8]) {
+  MGS_CHECK(nullptr, h && bvec && ec && x && info, MGS_ERR_INVALID, "mgs_hier_post_pass: NULL argument");
+  mgs_ctx *ctx = h->ctx;
+  MGS_CHECK(ctx, h->finalized, MGS_ERR_STATE, "mgs_hier_post_pass: call mgs_hier_finalize first");
+  MGS_CHECK(ctx, level >= 0 && level + 1 < (int)h->lev.size(), MGS_ERR_INVALID, "mgs_hier_post_pass: level %d has no coarser level", level);
+  MGS_TRY(prepare_fused(h));
+  mgs_level &L = h->lev[level];
+  const mgs_level &C = h->lev[level + 1];
+  MGS_CHECK(ctx, L.T && L.T->aggregation, MGS_ERR_STATE, "mgs_hier_post_pass: level %d has a general P (the fused post pass serves aggregation transfers only)", level);
+  const bool plain = L.A->cols == L.A->rows && C.A->cols == C.A->rows && !L.nx && !L.cmap_ext && !ctx->opt_valcode && !(L.A->code && L.A->code->vtab) && !L.code_hat &&
+                     !(L.code_agg && L.code_agg->vtab) && !(L.code_ap && L.code_ap->vtab);
+  MGS_CHECK(ctx, plain, MGS_ERR_STATE, "mgs_hier_post_pass: level %d is sharded or value-coded", level);
+  // what cycle_level asks before it takes the fused branch
+  MGS_CHECK(ctx, ctx->opt_fuse && !h->additive && h->nu1 == 1 && h->nu2 == 1 && L.wd && L.wd_omega == h->omega && L.A->lds_cap > 0, MGS_ERR_STATE,
+            "mgs_hier_post_pass: level %d does not run the fused passes (option fuse, V(1,1), multiplicative)", level);
+  MGS_CHECK(ctx, bvec->n >= L.n && (!xin || xin->n >= L.n) && x->n >= L.n && ec->n >= L.T->n_coarse, MGS_ERR_INVALID,
+            "mgs_hier_post_pass: vectors shorter than the level (%d rows, %d aggregates)", L.n, L.T->n_coarse);
+  const int nb = (L.A->rows + 255) / 256;
+  int b0 = 0, b1 = nb, ga = 0x7fffffff, gl = 0;
+  if (range) {
+    b0 = range[0]; b1 = range[1]; ga = range[2]; gl = range[3];
+    const long long last = (long long)b1 - 1 + (b1 - 1 >= ga ? gl : 0);      // the highest row block the launch maps to
+    MGS_CHECK(ctx, b0 >= 0 && b1 >= b0 && ga >= 0 && gl >= 0 && last < nb, MGS_ERR_INVALID, "mgs_hier_post_pass: row-block range {%d, %d, %d, %d} leaves the level's %d row blocks", b0, b1, ga, gl, nb);
+  }
+  fused_operands ops;
+  level_fused_operands(h, level, false, ops);
+  if (!range) ops.Amap.sweep = ops.sweep;      // the group sweep launches whole levels only
+  const mgs_csr *op = ops.operands ? &ops.Amap : L.A;
+  mgs_launch_report rep;
+  ctx->report = &rep;
+  const int rc = ops.operands
+      ? mgs_launch_fused_range(&ops.Amap, FUSE_POST_MAPPED, L.wd->d, bvec->d, xin ? xin->d : nullptr, L.T->agg, ec->d, x->d, nullptr, nullptr, b0, b1, ga, gl)
+      : mgs_launch_fused_range(L.A, FUSE_POST, L.wd->d, bvec->d, xin ? xin->d : nullptr, L.T->agg, ec->d, x->d, nullptr, nullptr, b0, b1, ga, gl);
+  ctx->report = nullptr;
+  MGS_TRY(rc);
+  info[0] = ops.post_form; info[1] = rep.kernel; info[2] = rep.u; info[3] = rep.flags; info[4] = rep.capv; info[5] = rep.capi;
+  // row blocks the kernel walks from global memory: entry counts from the operand's block bounds (a copy behind the launch; the host
+  // waits for the copy, the caller still synchronizes before it reads x)
+  int64_t over = -1;
+  if (op->blkptr && rep.kernel >= 0) {
+    std::vector<int> bp((size_t)nb + 1);
+    MGS_HIP(ctx, hipMemcpyAsync(bp.data(), op->blkptr, sizeof(int) * bp.size(), hipMemcpyDeviceToHost, ctx->stream));
+    MGS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    over = 0;
+    for (int q = 0; q < nb; ++q) over += bp[q + 1] - bp[q] > rep.capv;
+  }
+  info[6] = over; info[7] = ops.grouped ? 1 : 0;
+  return MGS_OK;
 }
 int mgs_hier_graph_info(const mgs_hier *h, int64_t out[4]) {
   int n = 0; for (auto &g : h->graphs) n += g.exec != nullptr;
@@ -1345,20 +1424,11 @@ static int cycle_level(mgs_hier *h, int l, const double *b, double *x, bool zero
       if (!rc) rc = h->halo_fused(h->halo_user, q, 2, src, nullptr, dst, 1);
       return rc ? mgs_fail(ctx, MGS_ERR_STATE, "halo exchange of the fused passes failed at level %d (%d)", q, rc) : MGS_OK;
     };
-    // Setup-time operands: Â = A·diag(wd) makes the pre pass the plain residual kernel with x = b (one gather per
-    // entry); A·P (or col_agg = the coarse column of every entry) lets the post pass gather e_c directly.  On a shard the
-    // halo columns of Â read the payload buffer (the pattern-coded kernel knows that split); those of A·P read e_c's own halo.
-    // Â's code: its own when the tuples carry values or halo tags, A's index-only code otherwise
-    mgs_csr Ahat = *L.A; Ahat.val = L.val_wd; Ahat.owns = false;
-    Ahat.code = halo ? L.code_pre : ((L.A->code && L.A->code->vtab) || L.code_hat ? L.code_hat : L.A->code);
-    mgs_csr Amap = *L.A; Amap.val = L.A->val; Amap.col = L.col_agg; Amap.code = L.code_agg; Amap.owns = false;
-    if (ctx->opt_diag_from_values && L.dpos) { Amap.dpos = L.dpos; Amap.dpos_omega = h->omega; }   // t-form post pass: ω/a_ii from the streamed values
-    if (ctx->opt_merge_ap && L.AP) { Amap = *L.AP; Amap.code = L.code_ap; Amap.owns = false; }      // A·P, merged: fewer entries, wd read per row
-    // operand precision: both passes of this level read the FP32 copies of the stored values (float forms of the same kernels), or neither does
-    const bool f32 = level_runs_f32(h, l) && !halo;
-    if (f32) { Ahat.val32 = L.val_wd32; Amap.val32 = L.ap_val32; }
-    const bool operands = ctx->opt_fuse_operands && L.val_wd && (L.col_agg || (ctx->opt_merge_ap && L.AP)) &&
-                          (!halo || mgs_rowcode_usable(&Ahat, true));
+    // setup-time operands of the two passes (level_fused_operands)
+    fused_operands ops;
+    level_fused_operands(h, l, halo, ops);
+    mgs_csr &Ahat = ops.Ahat, &Amap = ops.Amap;
+    const bool f32 = ops.f32, operands = ops.operands;
     const int *cmap = L.cmap_ext ? L.cmap_ext : L.T->agg;        // gather forms: coarse column of every local column
     double *ec = C.x->d, *ec_halo = C.x->d + C.n;
     // e_c's halo: one exchange on the coarse level's plan — unless that level is the replicated tail's, whose solution already holds the
@@ -1372,15 +1442,14 @@ static int cycle_level(mgs_hier *h, int l, const double *b, double *x, bool zero
     // Grouped form: pre pass + restriction in one kernel (r stays in LDS; L.r receives t = b + r, L.tmp the residuals of the
     // few rows whose aggregate leaves its row-block group), post pass in its t-form.
     // On a row shard the right-hand side of the halo rows is exchanged first (no interior/boundary split in this form).
-    const bool grouped = ctx->opt_fuse_restrict && operands && L.grp && !(Ahat.code && Ahat.code->vtab) &&
-                         (!halo || L.nx || !split || (h->capturing));
+    const bool grouped = ops.grouped && (!halo || L.nx || !split || (h->capturing));
     if (grouped) {
       if (halo) MGS_TRY(exchange_now(l, b, L.hbuf->d));
       // option pre_nodiag: an eligible FP64 level streams Â's diagonal as a byte per row (the same bits as from val_wd)
       const bool nodiag = level_pre_nodiag(h, L, halo, f32);
       MGS_TRY(mgs_launch_group_pre(&Ahat, L.grp, L.T, b, b, L.r->d, L.tmp->d, C.b->d, hv, L.A->rows, nodiag ? L.val_nd : nullptr, L.nd_code, L.nd_omega));
       MGS_TRY(coarse_solve(h, l + 1, C.b->d, C.x->d));
-      if (ctx->opt_group_sweep & 1) Amap.sweep = L.grp;
+      Amap.sweep = ops.sweep;
       return post_operand(L.r->d, nullptr);
     }
     // small level (a dispatch costs what it costs, whatever it does): pre pass and restriction in one aggregate-parallel kernel

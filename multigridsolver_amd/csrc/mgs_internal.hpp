@@ -12,6 +12,12 @@
 
 #include "../../include/mgs.h"
 
+// what the launcher of a fused post pass decided (mgs_hier_post_pass hands it to its caller): filled in by the launch path itself while
+// mgs_ctx::report points at one, so a test can tell which arm of the kernels its case ran
+struct mgs_launch_report {
+  int kernel = -1;   // 0 gather kernel (csr_rowblock_fused_kernel), 1 coded kernel FP64, 2 coded kernel FP32, 3 coded kernel swept group by group
+  int u = 0, flags = 0, capv = 0, capi = 0;   // gather width, the kernel's flags word, LDS budgets (values / ints) of a row block
+};
 constexpr int MGS_RED_VALS = 32;   // results one reduction can hand to the host (mgs_ctx::red_host)
 struct mgs_ctx {
   int device = 0;
@@ -79,6 +85,7 @@ struct mgs_ctx {
   struct mgs_comm *ncomm = nullptr;   // native RCCL all-reduce of the inner products (takes precedence over the callback)
   mgs_allreduce_fn allreduce = nullptr;
   void *allreduce_user = nullptr;
+  mgs_launch_report *report = nullptr;   // diagnostics (mgs_hier_post_pass): the next post-pass launch describes itself here; NULL in every cycle
 };
 
 // pattern code of a CSR-shaped index array (kernels_spmv.hip): one byte per row + a small table per row block
