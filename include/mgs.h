@@ -146,6 +146,26 @@ int mgs_csr_update_values_coo_dev(mgs_csr *A, const void *val_dev, int64_t ntrip
 /* diagnostics (no reference counterpart): out[0] triples the matrix was assembled from (0: not from COO / no map kept), out[1]
  * entries, out[2] most triples in one row (0: not from COO), out[3] bytes the kept map occupies.  MGS_ERR_INVALID: NULL argument. */
 int mgs_csr_coo_info(const mgs_csr *A, int64_t out[4]);
+/* ---- declared null space (pure-Neumann Poisson problems, graph Laplacians) ----
+ * MGS_NULLSPACE_CONSTANT asserts A·1 = 0 and 1ᵀ·A = 0: a symmetric A with zero row sums, or a nonsymmetric one with zero row and column
+ * sums.  Nearest reference line: none — the reference's SparseLU (bicg.cpp:35-36) fails on such a matrix.  Like symmetry in mgs_pcg the
+ * assertion is the caller's responsibility and is NOT verified (no threshold for "zero to rounding" can be derived for matrices somebody
+ * else assembled); mgs_csr_nullspace_defect is the net.  What acts on the declaration:
+ *   - mgs_hier_finalize / mgs_hier_refresh of a hierarchy whose fine operator carries it invert A_c + (s/n_c)·1·1ᵀ, s = max|a_ij| of the
+ *     coarsest operator A_c (n_c rows), instead of A_c: for a symmetric semidefinite A_c with null vector 1 that inverse is
+ *     A_c⁺ + (1/s)·1·1ᵀ/n_c — exactly A_c⁺·b on a right-hand side orthogonal to 1.  The singularity rule itself is unchanged.
+ *   - mgs_pcg, mgs_bicgstab and mgs_fgcr solve A·x = Πb, Π = I − 1·1ᵀ/n, and return the solution of zero mean (see mgs_pcg).
+ * Setting the kind on a matrix that a finalized hierarchy already uses takes effect at the next mgs_hier_finalize or mgs_hier_refresh.
+ * Without the declaration every call takes exactly the path it took before these entry points existed.
+ * mgs_csr_set_nullspace — MGS_ERR_INVALID: A NULL, unknown kind, matrix not square, matrix with halo columns (cols > rows: a row shard).
+ * mgs_csr_nullspace_defect: out[0] = ‖A·1‖∞ / ‖|A|·1‖∞, out[1] the same quantity for Aᵀ (0 where the denominator is 0) — mgs_spmv on a ones
+ * vector, mgs_csr_transpose and a max-abs reduction; it allocates two private copies of the matrix and synchronises: a diagnostic, never
+ * called implicitly. */
+#define MGS_NULLSPACE_NONE 0
+#define MGS_NULLSPACE_CONSTANT 1
+int mgs_csr_set_nullspace(mgs_csr *A, int kind);
+int mgs_csr_nullspace(const mgs_csr *A, int *kind);
+int mgs_csr_nullspace_defect(const mgs_csr *A, double out[2]);
 /* Synthetic operator generated on device: 7-point 3-D Poisson on an
  * N^3 grid, 3-D extension of src/common/poisson.cpp:11-33 (diag 6, off-diagonals −1,
  * row e=(i*N+j)*N+k, ascending columns).  Rows of planes [plane_lo, plane_hi) only
@@ -212,6 +232,13 @@ int mgs_axpby(double a, const mgs_vec *x, double b, mgs_vec *y); /* y = a x + b 
 int mgs_axpbypcz(double a, const mgs_vec *x, double b, const mgs_vec *y, double c,
                  mgs_vec *z);                                    /* z = a x + b y + c z */
 
+/* v ← v − mean(v): the projection Π = I − 1·1ᵀ/n the Krylov solvers apply for MGS_NULLSPACE_CONSTANT, on a vector of the caller's (tests and
+ * diagnostics; no reference counterpart).  Two streaming launches beside the fold — a sum pass with a fixed partial layout; one workgroup
+ * (behind a chunk stage above about two million entries) that folds the partials in index order and stores m = sum/n on the device; a
+ * shift pass — so the result is bit-reproducible from run to run; 16-byte accesses when v is 16-byte aligned.  mean (may be NULL): the m that was subtracted, read back; nrm2 (may be NULL): ‖v − m‖₂ from the shift pass.  Synchronises when
+ * either is asked for.  MGS_ERR_INVALID: v NULL. */
+int mgs_vec_project_const(mgs_vec *v, double *mean, double *nrm2);
+
 /* ------------------------------------------- L3 preconditioner: multilevel V-cycle (★) */
 /* MultiGridPrecond(A, P) — bicg.cpp:19-62.  A is borrowed (must outlive the hierarchy).
  * Level l cycle: ν1 damped-Jacobi sweeps, r = b − Ax, r_c = Pᵀr, recurse from 0,
@@ -240,7 +267,13 @@ int mgs_hier_coarsen(mgs_hier *h, double ktg, int npass, double tou, int coarse_
  * greater than 8·n·DBL_EPSILON·max|a_ij| (n its rows, a_ij its entries) — or holds a NaN or Inf.
  * A one-level hierarchy (no mgs_hier_push_P / mgs_hier_coarsen) is this dense solve alone and
  * is never smoothed: its operator may have zero or missing diagonal entries.  They are refused
- * with MGS_ERR_NUMERIC as soon as a level is pushed below it or it is smoothed itself.      */
+ * with MGS_ERR_NUMERIC as soon as a level is pushed below it or it is smoothed itself.
+ * Fine operator declared MGS_NULLSPACE_CONSTANT (mgs_csr_set_nullspace): the dense solve inverts A_c + (s/n_c)·1·1ᵀ, which is valid only
+ * if every level inherits the null space (P·1_c = 1).  MGS_ERR_INVALID, with a message naming the level, when some level's transfer is a
+ * general P, when a transfer leaves a row outside every aggregate, or when the hierarchy is row-sharded (halo columns, halo callbacks,
+ * native plans or tail) — structural checks without a tolerance, made before anything is launched.  A one-level hierarchy is the
+ * regularised dense solve alone; the smoothed coarsest form needs no change.  mgs_vcycle itself is not projected: its output on such a
+ * hierarchy may carry a constant component, which the Krylov solvers remove.                                                 */
 int mgs_hier_finalize(mgs_hier *h);
 int mgs_hier_set_smoother(mgs_hier *h, double omega, int nu1, int nu2);
 /* Values changed, pattern did not (time stepping, Picard / Newton iterations, parameter sweeps): recomputes everything in h
@@ -358,7 +391,16 @@ int mgs_fgcr(const mgs_csr *A, mgs_vec *x, const mgs_vec *b, mgs_hier *h, int re
  * to FP32 rounding: flexible = 1 is recommended there.
  * flexible = 1: β = z·(r − r_prev)/ρ_prev, computed as −α·(z·q)/ρ_prev from the vectors already held — accepts a preconditioner
  * that changes from call to call (K-cycle) or is not symmetric (V(2,1)); one more stream in the dots pass (88 instead of 80 B per
- * row beside cycle and SpMV). */
+ * row beside cycle and SpMV).
+ * A declared MGS_NULLSPACE_CONSTANT (all three Krylov solvers): the system solved is A·x = Πb with Π = I − 1·1ᵀ/n, and x comes back with
+ * zero mean.  Every true residual is Π(b − A·x); the caller's b is only read.  *tol is then relative to ‖Πb‖ (1 if that is zero).  mgs_pcg
+ * projects z after every preconditioner application (h = NULL included), so the preconditioner it sees is ΠMΠ, symmetric when M is;
+ * mgs_bicgstab projects both preconditioned vectors of an iteration, mgs_fgcr every direction c_k before v_k = A·c_k; x is projected after
+ * its last update, before the true residual that decides the return (mgs_pcg and mgs_fgcr: before every true residual that may decide
+ * one — when the recursion says converged or the iterations are used up; an ordinary restart of mgs_fgcr does not project x).  Two
+ * streaming launches beside a one-workgroup fold and 24 B per row for every projection.  MGS_ERR_INVALID: A is declared and is a row shard; h is
+ * given and its fine operator carries another kind than A (a hierarchy built for a regular twin of A).  Without the declaration no
+ * projection is launched. */
 int mgs_pcg(const mgs_csr *A, mgs_vec *x, const mgs_vec *b, mgs_hier *h, int flexible,
             int *max_iter, double *tol, int *status);
 

@@ -102,6 +102,7 @@ def write_mtx(path, rows, cols, rowptr, col, val):
     check(lib().mgs_mtx_write(path.encode(), rows, cols, len(col), _ip(rowptr), _ip(col), _dp(val)))
 
 
+_NULLSPACE = {None: 0, "constant": 1}      # MGS_NULLSPACE_NONE / MGS_NULLSPACE_CONSTANT
 _INDEX_BITS = {"int32": 32, "int64": 64, "<i4": 32, "<i8": 64}
 _FLOAT64 = ("float64", "<f8")
 
@@ -277,6 +278,24 @@ class Csr:
             check(lib().mgs_csr_update_values(self.h, _dp(a), a.size), self.ctx.h)
         return self
 
+    def set_nullspace(self, kind):
+        """declare the null space: "constant" (A·1 = 0 and 1ᵀ·A = 0: pure-Neumann operators, graph Laplacians) or None; not verified —
+        nullspace_defect() is the net.  Hierarchies act on it at their next finalize() / refresh(), the Krylov solvers at their next
+        call (mgs_csr_set_nullspace); returns self"""
+        if kind not in _NULLSPACE:
+            raise ValueError(f"set_nullspace: {kind!r}, expected one of {list(_NULLSPACE)}")
+        check(lib().mgs_csr_set_nullspace(self.h, _NULLSPACE[kind]), self.ctx.h); return self
+
+    def nullspace(self):
+        """what set_nullspace declared: "constant" or None"""
+        k = C.c_int(); check(lib().mgs_csr_nullspace(self.h, C.byref(k)), self.ctx.h)
+        return {v: n for n, v in _NULLSPACE.items()}[k.value]
+
+    def nullspace_defect(self):
+        """(‖A·1‖∞ / ‖|A|·1‖∞, the same for Aᵀ): how far the matrix is from the "constant" declaration; a diagnostic, synchronises"""
+        out = (C.c_double * 2)(); check(lib().mgs_csr_nullspace_defect(self.h, out), self.ctx.h)
+        return float(out[0]), float(out[1])
+
     def download(self):
         rows, _ = self.shape; nnz = self.nnz
         rp = np.empty(rows + 1, dtype=np.int32); ci = np.empty(max(nnz, 1), dtype=np.int32); v = np.empty(max(nnz, 1))
@@ -359,6 +378,13 @@ class Vec:
 
     def nrm2(self):
         out = C.c_double(); check(lib().mgs_nrm2(self.h, C.byref(out)), self.ctx.h); return out.value
+
+    def project_const(self, nrm2=False):
+        """self ← self − mean(self) on the device (mgs_vec_project_const) → the mean that was subtracted, read back; nrm2=True:
+        (mean, ‖self − mean‖₂ from the same pass)"""
+        m, s = C.c_double(), C.c_double()
+        check(lib().mgs_vec_project_const(self.h, C.byref(m), C.byref(s) if nrm2 else None), self.ctx.h)
+        return (m.value, s.value) if nrm2 else m.value
 
     def axpby(self, a, x, b):
         """self = a·x + b·self"""

@@ -151,6 +151,11 @@ class DeviceMatrix {
   int rows() const { return rows_; }
   int cols() const { return cols_; }
   mgs_csr *handle() const { return a_.get(); }
+  // Declares A·1 = 0 and 1ᵀ·A = 0 (pure-Neumann operators, graph Laplacians; mgs.h: mgs_csr_set_nullspace) — or takes the declaration
+  // back.  Set it before MultiGridPrecond is built on this matrix: its coarsest solve is then regularised, and BiCGSTABiml / CGiml
+  // solve A·x = Πb and return the x of zero mean.  Copies of a DeviceMatrix share the device matrix and with it the declaration.
+  void setNullspaceConstant(bool on) { check(mgs_csr_set_nullspace(a_.get(), on ? MGS_NULLSPACE_CONSTANT : MGS_NULLSPACE_NONE), context()); }
+  bool nullspaceConstant() const { int k = 0; check(mgs_csr_nullspace(a_.get(), &k), context()); return k == MGS_NULLSPACE_CONSTANT; }
   // New values, same pattern, in place (mgs.h: mgs_csr_update_values; the reference would upload a new matrix).  The pattern of A is
   // compared with the device copy's on the host: a different rowptr / col throws Error(MGS_ERR_INVALID).
   void update_values(const SMatrix &A) {

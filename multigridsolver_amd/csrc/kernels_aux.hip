@@ -490,6 +490,89 @@ __global__ __launch_bounds__(TB) void dot_block_vec_kernel(int64_t n, const doub
   }
 }
 
+// ------------------------------------------------------------------ constant null space: v ← v − mean(v) (k_project_const)
+// Two launches beside the fold, the scalar stays on the device.  Sum pass: one partial per workgroup in a fixed layout ([2][gridDim.x], the
+// second sum zero so that dot2_mid_kernel / k_dot2_finish serve), folded in index order by one workgroup whose last step stores m = sum/n —
+// the order does not depend on scheduling, so m and with it every shifted entry is bit-reproducible from run to run.  Shift pass:
+// v_i ← v_i − m with m loaded once per lane; NRM adds ‖v − m‖² (partial pair per workgroup); STORE = false leaves v as it is (‖Πb‖ of the
+// caller's const right-hand side).  24 B per row for the pair (read, read, write).
+__global__ __launch_bounds__(TB) void sum_partial_kernel(int64_t n, const double *__restrict__ v, double *__restrict__ part) {
+  __shared__ double sh[TB / 64];
+  double s = 0.0;
+  int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * TB;
+  for (; i < n; i += stride) s += v[i];
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) { double t = 0.0; for (int w = 0; w < TB / 64; ++w) t += sh[w]; part[blockIdx.x] = t; part[gridDim.x + blockIdx.x] = 0.0; }
+}
+// 16-byte form (lane t adds its pair x then y, a fixed order)
+__global__ __launch_bounds__(TB) void sum_partial_vec_kernel(int64_t n, const double *__restrict__ v, double *__restrict__ part) {
+  __shared__ double sh[TB / 64];
+  const int64_t n2 = n >> 1;
+  const vd2 *__restrict__ vv = reinterpret_cast<const vd2 *>(v);
+  double s = 0.0;
+  const int64_t stride = (int64_t)gridDim.x * TB;
+  for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < n2; i += stride) { const vd2 p = vv[i]; s += p.x; s += p.y; }
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) s += v[n - 1];
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) { double t = 0.0; for (int w = 0; w < TB / 64; ++w) t += sh[w]; part[blockIdx.x] = t; part[gridDim.x + blockIdx.x] = 0.0; }
+}
+__global__ __launch_bounds__(TB) void mean_final_kernel(int nb, const double *__restrict__ part, double n, double *__restrict__ mean) {
+  __shared__ double sh[TB];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < nb; i += TB) s += part[i];
+  sh[threadIdx.x] = s;
+  __syncthreads();
+  for (int w = TB / 2; w > 0; w >>= 1) { if (threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w]; __syncthreads(); }
+  if (threadIdx.x == 0) mean[0] = sh[0] / n;
+}
+template <bool STORE, bool NRM>
+__global__ __launch_bounds__(TB) void shift_const_kernel(int64_t n, double *__restrict__ v, const double *__restrict__ mean, double *__restrict__ part) {
+  __shared__ double sh[TB / 64];
+  const double m = mean[0];
+  double s0 = 0.0;
+  int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * TB;
+  for (; i < n; i += stride) { const double o = v[i] - m; if (STORE) v[i] = o; if (NRM) s0 += o * o; }
+  if (!NRM) return;
+  for (int off = 32; off > 0; off >>= 1) s0 += __shfl_down(s0, off);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s0;
+  __syncthreads();
+  if (threadIdx.x == 0) { double t0 = 0.0; for (int w = 0; w < TB / 64; ++w) t0 += sh[w]; part[blockIdx.x] = t0; part[gridDim.x + blockIdx.x] = 0.0; }
+}
+// 16-byte form (same per-element expression: same bits)
+template <bool STORE, bool NRM>
+__global__ __launch_bounds__(TB) void shift_const_vec_kernel(int64_t n, double *__restrict__ v, const double *__restrict__ mean, double *__restrict__ part, int nts) {
+  __shared__ double sh[TB / 64];
+  const double m = mean[0];
+  const int64_t n2 = n >> 1;
+  vd2 *__restrict__ vv = reinterpret_cast<vd2 *>(v);
+  double s0 = 0.0;
+  const int64_t stride = (int64_t)gridDim.x * TB;
+  for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < n2; i += stride) {
+    const vd2 p = vv[i]; vd2 o;
+    o.x = p.x - m; o.y = p.y - m;
+    if (STORE) st2(vv + i, o, nts != 0);
+    if (NRM) { s0 += o.x * o.x; s0 += o.y * o.y; }
+  }
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) { const double o = v[n - 1] - m; if (STORE) v[n - 1] = o; if (NRM) s0 += o * o; }
+  if (!NRM) return;
+  for (int off = 32; off > 0; off >>= 1) s0 += __shfl_down(s0, off);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s0;
+  __syncthreads();
+  if (threadIdx.x == 0) { double t0 = 0.0; for (int w = 0; w < TB / 64; ++w) t0 += sh[w]; part[blockIdx.x] = t0; part[gridDim.x + blockIdx.x] = 0.0; }
+}
+// |v_i| in place (mgs_csr_nullspace_defect: |A| of a private copy)
+__global__ void abs_vals_kernel(int64_t n, double *__restrict__ v) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (; i < n; i += stride) v[i] = fabs(v[i]);
+}
+
 // ------------------------------------------------------------------ several inner products against one vector, one pass
 // s_k = Σ a_i·b_k[i], k < K ≤ MDOT_MAX: `a` is read once.  Partials [K][gridDim.x] in a fixed order (no atomics), folded by
 // mdot_final_kernel — the K-cycle's (ρ1, α1) and the flexible Krylov methods' orthogonalisation coefficients.
@@ -678,6 +761,13 @@ __global__ __launch_bounds__(TB) void dense_absmax_kernel(int64_t nnz, const dou
   }
   for (int off = 32; off > 0; off >>= 1) { const unsigned long long o = __shfl_down(m, off); m = o > m ? o : m; }
   if ((threadIdx.x & 63) == 0) atomicMax(amax_bits, m);      // one atomic per wavefront
+}
+// Constant null space (mgs_csr_set_nullspace): A_c + (s/n)·1·1ᵀ with s = max|a_ij| as dense_absmax_kernel left it on the device — added to the left
+// half of W between the scatter and the elimination.  For a symmetric semidefinite A_c with null vector 1 the inverse is A_c⁺ + (1/s)·1·1ᵀ/n.
+__global__ void dense_reg_const_kernel(int n, double *__restrict__ W, const unsigned long long *__restrict__ amax_bits) {
+  int j = blockIdx.x * blockDim.x + threadIdx.x;
+  int i = blockIdx.y;
+  if (j < n) W[(size_t)i * 2 * n + j] += __longlong_as_double((long long)amax_bits[0]) / (double)n;
 }
 // Singularity rule: the operator is refused (piv[1] = 1) when a pivot is not greater than GJ_SINGULAR_FACTOR·n·DBL_EPSILON·max|a_ij|.
 // Written as !(|pivot| > threshold) so that a NaN pivot and a NaN or Inf scale are refused as well.  Basis of the constant (NumPy model
@@ -1163,6 +1253,59 @@ int k_pcg_residual(mgs_ctx *ctx, int64_t n, double a, double *r, const double *q
   MGS_HIP(ctx, hipGetLastError());
   return k_dot2_finish(ctx, nb, ctx->red_dev, out_host2);
 }
+// ---- constant null space: v ← v − mean(v)
+// The mean stays on the device, behind the folded results of the reductions (red_dev[DOT_BLOCKS + MGS_RED_VALS]).
+constexpr int MEAN_SLOT = DOT_BLOCKS + MGS_RED_VALS;
+static_assert(DOT_BLOCKS == MGS_DOT_BLOCKS && MEAN_SLOT < MGS_RED_CAP, "the mean slot lies behind the folded results, inside mgs_ctx::red_dev");
+// store: v is shifted in place (else only read); nrm2_host != NULL: nrm2_host[0] = ‖v − m‖² reaches the host (k_dot2_finish), nrm2_host[1] = 0
+static int project_const_impl(mgs_ctx *ctx, int64_t n, double *v, bool store, double *nrm2_host) {
+  if (n <= 0) { if (nrm2_host) nrm2_host[0] = nrm2_host[1] = 0.0; return MGS_OK; }
+  const bool vec = ctx->opt_blas1_vec && al16(v);
+  int nb = vec ? grid_vec((n + 1) / 2, ctx) : std::max(1, std::min(mgs_grid(n, TB), DOT_BLOCKS / 2));
+  double *part = ctx->red_dev, *mean = ctx->red_dev + MEAN_SLOT;
+  if (nb > DOT_BLOCKS / 2) { MGS_TRY(mgs_ensure_dot_part(ctx, 2 * (int64_t)nb)); part = ctx->dot_part; }
+  hipStream_t s = ctx->stream;
+  if (vec) hipLaunchKernelGGL(sum_partial_vec_kernel, dim3(nb), dim3(TB), 0, s, n, v, part);
+  else hipLaunchKernelGGL(sum_partial_kernel, dim3(nb), dim3(TB), 0, s, n, v, part);
+  const double *fold = part; int nf = nb;
+  if (nf > 4096) {          // long partial arrays: 256 chunk sums first (in red_dev), as k_dot2_finish does
+    const int groups = 256, chunk = (nf + groups - 1) / groups;
+    hipLaunchKernelGGL(dot2_mid_kernel, dim3(groups), dim3(TB), 0, s, nf, chunk, part, ctx->red_dev);
+    fold = ctx->red_dev; nf = groups;
+  }
+  hipLaunchKernelGGL(mean_final_kernel, dim3(1), dim3(TB), 0, s, nf, fold, (double)n, mean);
+  const int nts = ctx->opt_nt_store > 0 && n >= ctx->opt_nt_store;
+  const bool nrm = nrm2_host != nullptr;
+#define SHIFT_(ST, NR)                                                                                                              \
+  do {                                                                                                                              \
+    if (vec) hipLaunchKernelGGL((shift_const_vec_kernel<ST, NR>), dim3(nb), dim3(TB), 0, s, n, v, mean, part, nts);                  \
+    else hipLaunchKernelGGL((shift_const_kernel<ST, NR>), dim3(nb), dim3(TB), 0, s, n, v, mean, part);                               \
+  } while (0)
+  if (store && nrm) SHIFT_(true, true); else if (store) SHIFT_(true, false); else if (nrm) SHIFT_(false, true);
+#undef SHIFT_
+  MGS_HIP(ctx, hipGetLastError());
+  return nrm ? k_dot2_finish(ctx, nb, part, nrm2_host) : MGS_OK;
+}
+int k_project_const(mgs_ctx *ctx, int64_t n, double *v) { return project_const_impl(ctx, n, v, true, nullptr); }
+int k_project_const_nrm2(mgs_ctx *ctx, int64_t n, double *v, double *out_host2) { return project_const_impl(ctx, n, v, true, out_host2); }
+int k_const_dev_nrm2(mgs_ctx *ctx, int64_t n, const double *v, double *out_host2) { return project_const_impl(ctx, n, const_cast<double *>(v), false, out_host2); }
+// the mean the last projection on this context subtracted (diagnostics; synchronises)
+int k_project_const_mean(mgs_ctx *ctx, double *mean_host) {
+  MGS_HIP(ctx, hipMemcpyAsync(mean_host, ctx->red_dev + MEAN_SLOT, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  MGS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return MGS_OK;
+}
+int k_abs_inplace(mgs_ctx *ctx, int64_t n, double *v) {
+  if (n) hipLaunchKernelGGL(abs_vals_kernel, dim3(grid_cap(n, ctx->n_cu)), dim3(TB), 0, ctx->stream, n, v);
+  MGS_HIP(ctx, hipGetLastError());
+  return MGS_OK;
+}
+// max_i |v_i| as the bits of a non-negative double, folded into *amax_bits_dev (the caller zeroes it; a NaN wins): dense_absmax_kernel
+int k_absmax_dev(mgs_ctx *ctx, int64_t n, const double *v, unsigned long long *amax_bits_dev) {
+  if (n) hipLaunchKernelGGL(dense_absmax_kernel, dim3(grid_cap(n, ctx->n_cu)), dim3(TB), 0, ctx->stream, n, v, amax_bits_dev);
+  MGS_HIP(ctx, hipGetLastError());
+  return MGS_OK;
+}
 int k_dot_dev(mgs_ctx *ctx, int64_t n, const double *x, const double *y, double *out_dev) {
   int nb = (int)((n + TB - 1) / TB);
   if (nb > DOT_BLOCKS) nb = DOT_BLOCKS;
@@ -1255,8 +1398,8 @@ int k_dense_gemv(mgs_ctx *ctx, int n, const double *M, const double *b, double *
 // *inv_out == NULL: the n·n result is allocated here (and released again on failure); else it is written into the caller's buffer
 // (mgs_hier_refresh: the cached graphs hold that pointer), which stays the caller's whatever happens.  MGS_ERR_NUMERIC: a pivot not
 // greater than 8·n·DBL_EPSILON·max|a_ij| (see gj_pivot_kernel), which also refuses NaN and Inf among the values.  The work buffers are
-// released on every exit.
-int k_dense_inverse(mgs_ctx *ctx, const mgs_csr *A, double **inv_out) {
+// released on every exit.  reg_const != 0: A + (max|a_ij|/n)·1·1ᵀ is inverted (constant null space declared; dense_reg_const_kernel).
+int k_dense_inverse(mgs_ctx *ctx, const mgs_csr *A, double **inv_out, int reg_const) {
   const int n = A->rows;
   double *const into = *inv_out;
   MGS_CHECK(ctx, A->cols == n, MGS_ERR_INVALID, "coarsest operator is not square (%d x %d)", A->rows, A->cols);
@@ -1275,6 +1418,7 @@ int k_dense_inverse(mgs_ctx *ctx, const mgs_csr *A, double **inv_out) {
     MGS_HIP(ctx, hipMemsetAsync(amax, 0, sizeof(unsigned long long), s));
     if (A->nnz) hipLaunchKernelGGL(dense_absmax_kernel, dim3(grid_cap(A->nnz, ctx->n_cu)), dim3(TB), 0, s, (int64_t)A->nnz, A->val, amax);
     if (n) hipLaunchKernelGGL(dense_scatter_kernel, dim3(mgs_grid(n, TB)), dim3(TB), 0, s, n, A->rowptr, A->col, A->val, W);
+    if (n && reg_const) hipLaunchKernelGGL(dense_reg_const_kernel, dim3(mgs_grid(n, TB), n), dim3(TB), 0, s, n, W, amax);
     for (int k = 0; k < n; ++k) {
       hipLaunchKernelGGL(gj_pivot_kernel, dim3(1), dim3(TB), 0, s, n, k, W, piv, colk + n, amax);
       hipLaunchKernelGGL(gj_swap_scale_kernel, dim3(mgs_grid(2 * n, TB)), dim3(TB), 0, s, n, k, W, piv, colk + n);

@@ -187,7 +187,7 @@ int mgs_ctx_create(int device, void *stream, mgs_ctx **out) {
   else { e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking); if (e != hipSuccess) { delete c; return mgs_fail(nullptr, MGS_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e)); } c->own_stream = true; }
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->n_cu = prop.multiProcessorCount;
-  c->red_cap = 4096 + 64;    // DOT_BLOCKS partials + the folded results (kernels_aux.hip)
+  c->red_cap = MGS_RED_CAP;  // partials + the folded results + the device-only scalars (the projection's mean), see mgs_internal.hpp
   if (mgs_hip_malloc((void **)&c->red_dev, sizeof(double) * c->red_cap) != hipSuccess || hipHostMalloc((void **)&c->red_host, sizeof(double) * 2 * MGS_RED_VALS, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
     delete c; return mgs_fail(nullptr, MGS_ERR_ALLOC, "context scratch allocation failed");
   }
@@ -436,6 +436,57 @@ int mgs_csr_rowcode_info(const mgs_csr *A, int64_t out[4]) {
 int mgs_csr_poisson3d(mgs_ctx *ctx, int N, int plane_lo, int plane_hi, int local_cols, mgs_csr **out) { return k_poisson3d(ctx, N, plane_lo, plane_hi, local_cols, out); }
 int mgs_csr_poisson2d(mgs_ctx *ctx, int n, mgs_csr **out) { return k_poisson2d(ctx, n, out); }
 int mgs_csr_transpose(const mgs_csr *A, mgs_csr **out) { return k_transpose(A, out); }
+// declared null space: a word on the matrix that hierarchies (finalize / refresh) and the Krylov solvers read; nothing is verified here
+int mgs_csr_set_nullspace(mgs_csr *A, int kind) {
+  MGS_CHECK(nullptr, A, MGS_ERR_INVALID, "mgs_csr_set_nullspace: NULL matrix");
+  MGS_CHECK(A->ctx, kind == MGS_NULLSPACE_NONE || kind == MGS_NULLSPACE_CONSTANT, MGS_ERR_INVALID, "mgs_csr_set_nullspace: unknown kind %d", kind);
+  MGS_CHECK(A->ctx, A->rows == A->cols, MGS_ERR_INVALID, "mgs_csr_set_nullspace: the matrix is %d x %d (%s)", A->rows, A->cols,
+            A->cols > A->rows ? "halo columns: a row shard" : "not square");
+  A->nullspace = kind;
+  return MGS_OK;
+}
+int mgs_csr_nullspace(const mgs_csr *A, int *kind) {
+  MGS_CHECK(nullptr, A && kind, MGS_ERR_INVALID, "mgs_csr_nullspace: NULL argument");
+  *kind = A->nullspace;
+  return MGS_OK;
+}
+// out[0] = ‖A·1‖∞ / ‖|A|·1‖∞, out[1] the same for Aᵀ.  |Aᵀ| is the transpose's private copy with its values made absolute in place, |A| its
+// transpose; the four maxima are folded on the device (bits of non-negative doubles) and read once.
+int mgs_csr_nullspace_defect(const mgs_csr *A, double out[2]) {
+  MGS_CHECK(nullptr, A && out, MGS_ERR_INVALID, "mgs_csr_nullspace_defect: NULL argument");
+  mgs_ctx *ctx = A->ctx;
+  out[0] = out[1] = 0.0;
+  if (A->rows == 0 || A->cols == 0 || A->nnz == 0) return MGS_OK;
+  const int64_t nmax = A->rows > A->cols ? A->rows : A->cols;
+  mgs_vec *ones = nullptr, *y = nullptr; mgs_csr *At = nullptr, *Aa = nullptr; unsigned long long *mx = nullptr;
+  unsigned long long hm[4] = {0, 0, 0, 0};
+  auto run = [&]() -> int {
+    MGS_TRY(mgs_vec_create(ctx, nmax, &ones)); MGS_TRY(mgs_vec_create(ctx, nmax, &y));
+    MGS_TRY(mgs_dev_alloc(ctx, &mx, 4));
+    MGS_HIP(ctx, hipMemsetAsync(mx, 0, sizeof hm, ctx->stream));
+    MGS_TRY(mgs_vec_fill(ones, 1.0));
+    MGS_TRY(mgs_csr_transpose(A, &At));
+    MGS_TRY(mgs_spmv(A, ones, y));  MGS_TRY(k_absmax_dev(ctx, A->rows, y->d, mx + 0));      // ‖A·1‖∞
+    MGS_TRY(mgs_spmv(At, ones, y)); MGS_TRY(k_absmax_dev(ctx, At->rows, y->d, mx + 2));     // ‖Aᵀ·1‖∞
+    MGS_TRY(k_abs_inplace(ctx, At->nnz, At->val));
+    MGS_TRY(mgs_spmv(At, ones, y)); MGS_TRY(k_absmax_dev(ctx, At->rows, y->d, mx + 3));     // ‖|Aᵀ|·1‖∞
+    MGS_TRY(mgs_csr_transpose(At, &Aa));
+    MGS_TRY(mgs_spmv(Aa, ones, y)); MGS_TRY(k_absmax_dev(ctx, Aa->rows, y->d, mx + 1));     // ‖|A|·1‖∞
+    MGS_HIP(ctx, hipMemcpyAsync(hm, mx, sizeof hm, hipMemcpyDeviceToHost, ctx->stream));
+    MGS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return MGS_OK;
+  };
+  const int rc = run();
+  if (rc != MGS_OK) hipStreamSynchronize(ctx->stream);
+  mgs_vec_destroy(ones); mgs_vec_destroy(y); mgs_csr_destroy(At); mgs_csr_destroy(Aa);
+  if (mx) mgs_hip_free(mx);
+  if (rc != MGS_OK) return rc;
+  double v[4];
+  for (int q = 0; q < 4; ++q) memcpy(&v[q], &hm[q], sizeof(double));
+  out[0] = v[1] != 0.0 ? v[0] / v[1] : 0.0;
+  out[1] = v[3] != 0.0 ? v[2] / v[3] : 0.0;
+  return MGS_OK;
+}
 int mgs_csr_galerkin(const mgs_csr *A, const mgs_xfer *T, mgs_csr **out) {
   MGS_CHECK(A->ctx, T->n_fine == A->rows && A->rows == A->cols, MGS_ERR_INVALID, "galerkin: A is %d x %d, P has %d rows", A->rows, A->cols, T->n_fine);
   return T->aggregation ? k_galerkin_agg(A, T, out) : k_galerkin_general(A, T, out);
@@ -545,6 +596,14 @@ int mgs_axpby(double a, const mgs_vec *x, double b, mgs_vec *y) {
 int mgs_axpbypcz(double a, const mgs_vec *x, double b, const mgs_vec *y, double c, mgs_vec *z) {
   MGS_CHECK(x->ctx, x->n == y->n && x->n == z->n, MGS_ERR_INVALID, "mgs_axpbypcz: size mismatch");
   return k_axpbypcz(x->ctx, x->n, a, x->d, b, y->d, c, z->d);
+}
+int mgs_vec_project_const(mgs_vec *v, double *mean, double *nrm2) {
+  MGS_CHECK(nullptr, v, MGS_ERR_INVALID, "mgs_vec_project_const: NULL vector");
+  double d2[2] = {0.0, 0.0};
+  if (nrm2) { MGS_TRY(k_project_const_nrm2(v->ctx, v->n, v->d, d2)); *nrm2 = std::sqrt(d2[0]); }
+  else MGS_TRY(k_project_const(v->ctx, v->n, v->d));
+  if (mean) { *mean = 0.0; if (v->n > 0) MGS_TRY(k_project_const_mean(v->ctx, mean)); }
+  return MGS_OK;
 }
 int mgs_halo_pack(mgs_ctx *ctx, const mgs_vec *x, const int *send_idx_dev, int64_t n_send, double *send_buf_dev) {
   return k_gather(ctx, x->d, send_idx_dev, n_send, send_buf_dev);
@@ -1011,9 +1070,31 @@ int mgs_hier_coarsen(mgs_hier *h, double ktg, int npass, double tou, int coarse_
   return MGS_OK;
 }
 
+// Constant null space declared on the fine operator: the regularised coarsest solve is valid only if every level inherits the null
+// space, P·1_c = 1 — aggregation transfers that cover every row (T->nnz counts the rows inside an aggregate), no row shards.  Structural,
+// no tolerance, nothing launched.
+static bool hier_nullspace_const(const mgs_hier *h) { return h->lev[0].A->nullspace == MGS_NULLSPACE_CONSTANT; }
+static int nullspace_check(mgs_hier *h, const char *who) {
+  mgs_ctx *ctx = h->ctx;
+  const int nl = (int)h->lev.size();
+  MGS_CHECK(ctx, !(h->halo || h->halo_begin || h->halo_fused || h->native || h->ntail || h->coarse), MGS_ERR_INVALID,
+            "%s: constant null space declared on a row-sharded hierarchy (halo callbacks, native plans or tail)", who);
+  for (int l = 0; l < nl; ++l) {
+    const mgs_level &L = h->lev[l];
+    MGS_CHECK(ctx, L.A->cols == L.A->rows && !L.nx, MGS_ERR_INVALID, "%s: constant null space declared, level %d is a row shard (halo columns or a native plan)", who, l);
+    if (l + 1 >= nl) break;
+    MGS_CHECK(ctx, L.T && L.T->aggregation, MGS_ERR_INVALID, "%s: constant null space declared, the transfer of level %d is a general P, not an aggregation", who, l);
+    MGS_CHECK(ctx, L.T->nnz == (int64_t)L.T->n_fine, MGS_ERR_INVALID, "%s: constant null space declared, the transfer of level %d leaves %lld rows outside every aggregate", who, l,
+              (long long)(L.T->n_fine - L.T->nnz));
+  }
+  return MGS_OK;
+}
+
 int mgs_hier_finalize(mgs_hier *h) {
   mgs_ctx *ctx = h->ctx;
   const mgs_csr *Ac = h->lev.back().A;
+  const bool ns = hier_nullspace_const(h);
+  if (ns) MGS_TRY(nullspace_check(h, "mgs_hier_finalize"));
   MGS_CHECK(ctx, Ac->rows == Ac->cols, MGS_ERR_STATE, "coarsest operator is not square");
   if (h->inv) { mgs_hip_free(h->inv); h->inv = nullptr; }
   h->nc = Ac->rows;
@@ -1028,7 +1109,7 @@ int mgs_hier_finalize(mgs_hier *h) {
     h->finalized = true; drop_graph(h);
     return MGS_OK;
   }
-  MGS_TRY(k_dense_inverse(ctx, Ac, &h->inv));
+  MGS_TRY(k_dense_inverse(ctx, Ac, &h->inv, ns ? 1 : 0));
   h->finalized = true; drop_graph(h);
   return MGS_OK;
 }
@@ -1053,6 +1134,8 @@ int mgs_hier_refresh(mgs_hier *h) {
     MGS_CHECK(ctx, !(L.A->code && L.A->code->vtab) && !L.code_hat && !(L.code_ap && L.code_ap->vtab), MGS_ERR_INVALID,
               "mgs_hier_refresh: level %d carries a value-carrying pattern code (built under option valcode)", l);
   }
+  const bool ns = hier_nullspace_const(h);
+  if (ns) MGS_TRY(nullspace_check(h, "mgs_hier_refresh"));
   bool kept = true, nd_built = false;
   if (!h->refresh_flags) MGS_TRY(mgs_dev_alloc(ctx, &h->refresh_flags, 2));
   MGS_HIP(ctx, hipMemsetAsync(h->refresh_flags, 0, 2 * sizeof(int), ctx->stream));
@@ -1085,7 +1168,7 @@ int mgs_hier_refresh(mgs_hier *h) {
   }
   if (rc == MGS_OK && !h->coarse_sweeps) {      // coarsest dense inverse, into the buffer the cached graphs know
     if (!h->inv) { kept = false; drop_graph(h); }
-    rc = k_dense_inverse(ctx, h->lev.back().A, &h->inv);
+    rc = k_dense_inverse(ctx, h->lev.back().A, &h->inv, ns ? 1 : 0);
   }
   if (rc != MGS_OK) {      // half-refreshed state must not be replayed: no cycle until a later refresh (or finalize) succeeds
     h->finalized = false; h->refresh_failed = true; h->refresh_kept_graphs = 0; drop_graph(h);
@@ -1747,10 +1830,24 @@ static void ws_put(mgs_ctx *ctx, mgs_vec *v) {
   ctx->ws_free.push_back(v);
 }
 
+// A declared MGS_NULLSPACE_CONSTANT: the solvers below solve A·x = Πb, Π = I − 1·1ᵀ/n (k_project_const), and return the x of zero mean.
+// *ns_out = whether to project.  Refused: a declared row shard; a hierarchy whose fine operator carries another kind than A.
+static int krylov_nullspace(const mgs_csr *A, const mgs_hier *h, const char *who, bool *ns_out) {
+  mgs_ctx *ctx = A->ctx;
+  const bool ns = A->nullspace == MGS_NULLSPACE_CONSTANT;
+  MGS_CHECK(ctx, !ns || (A->cols == A->rows && !ctx->ncomm && !ctx->allreduce), MGS_ERR_INVALID, "%s: constant null space declared on a row shard", who);
+  MGS_CHECK(ctx, !h || h->lev[0].A->nullspace == A->nullspace, MGS_ERR_INVALID,
+            "%s: the hierarchy's fine operator carries null-space kind %d, A carries %d (a hierarchy built for a regular twin of A?)", who, h->lev[0].A->nullspace, A->nullspace);
+  *ns_out = ns;
+  return MGS_OK;
+}
+
 // BiCGSTABiml, reference src/common/bicg.cpp:74-136, statement by statement on device vectors.
 int mgs_bicgstab(const mgs_csr *A, mgs_vec *x, const mgs_vec *b, mgs_hier *h, int *max_iter, double *tol, int *status) {
   mgs_ctx *ctx = A->ctx;
   MGS_CHECK(ctx, max_iter && tol && status, MGS_ERR_INVALID, "mgs_bicgstab: NULL out parameter");
+  bool ns = false;
+  MGS_TRY(krylov_nullspace(A, h, "mgs_bicgstab", &ns));
   MGS_TRY(mgs_csr_optimize(const_cast<mgs_csr *>(A)));
   const int n = A->rows, next = A->cols > n ? A->cols : n;
   MGS_CHECK(ctx, x->n >= n && b->n >= n, MGS_ERR_INVALID, "mgs_bicgstab: vectors shorter than %d", n);
@@ -1769,22 +1866,26 @@ int mgs_bicgstab(const mgs_csr *A, mgs_vec *x, const mgs_vec *b, mgs_hier *h, in
     if (h->halo_begin) { int rc = h->halo_begin(h->halo_user, 0, w->d); return rc ? rc : h->halo_end(h->halo_user, 0, w->d); }
     return 0;
   };
-  auto precond = [&](const mgs_vec *in, mgs_vec *out) -> int {       // M.solve (bicg.cpp:106,116)
-    if (!h) { mgs_vec ov; view(out, ov); return mgs_vec_copy(in, &ov); }
-    return mgs_vcycle(h, in, out, 1);
+  auto precond = [&](const mgs_vec *in, mgs_vec *out) -> int {       // M.solve (bicg.cpp:106,116); constant null space: Π·M
+    if (!h) { mgs_vec ov; view(out, ov); MGS_TRY(mgs_vec_copy(in, &ov)); }
+    else MGS_TRY(mgs_vcycle(h, in, out, 1));
+    return ns ? k_project_const(ctx, n, out->d) : MGS_OK;
   };
+  auto fin = [&]() -> int { if (ns) MGS_TRY(k_project_const(ctx, n, xv.d)); return mgs_sync(ctx); };   // constant null space: x ← Πx after its last update
   double rho_1 = 0, rho_2 = 0, alpha = 0, beta = 0, omega = 0, resid = 0, normb = 0, tmp = 0;
-  MGS_TRY(mgs_nrm2(&bv, &normb));                                                     // :80
+  double d2[2];
+  if (ns) { MGS_TRY(k_const_dev_nrm2(ctx, n, bv.d, d2)); normb = std::sqrt(d2[0]); }  // ‖Πb‖, b only read
+  else MGS_TRY(mgs_nrm2(&bv, &normb));                                                // :80
   if (halo0(const_cast<mgs_vec *>(xin))) return mgs_fail(ctx, MGS_ERR_STATE, "halo exchange failed");
   MGS_TRY(mgs_residual(A, xin, &bv, r));                                              // :82
+  if (ns) MGS_TRY(k_project_const(ctx, n, r->d));                                     // r = Π(b − A·x)
   MGS_TRY(mgs_vec_copy(r, rt));                                                       // :83
   if (normb == 0.0) normb = 1;                                                        // :85-86
-  double d2[2];
   MGS_TRY(k_dot2(ctx, n, r->d, r->d, rt->d, r->d, d2));             // ‖r‖² and (r̃,r) in one pass / one round trip
-  if ((resid = std::sqrt(d2[0]) / normb) <= *tol) { *tol = resid; *max_iter = 0; *status = 0; return MGS_OK; }   // :88-92
+  if ((resid = std::sqrt(d2[0]) / normb) <= *tol) { *tol = resid; *max_iter = 0; *status = 0; return ns ? fin() : MGS_OK; }   // :88-92
   for (int i = 1; i <= *max_iter; ++i) {                                              // :94
     rho_1 = d2[1];                                                                    // :95 (computed with the last ‖r‖)
-    if (rho_1 == 0) { *tol = std::sqrt(d2[0]) / normb; *status = 2; return MGS_OK; }  // :96-99
+    if (rho_1 == 0) { *tol = std::sqrt(d2[0]) / normb; *status = 2; return ns ? fin() : MGS_OK; }  // :96-99
     if (i == 1) MGS_TRY(mgs_vec_copy(r, p));                                          // :100-101
     else {
       beta = (rho_1 / rho_2) * (alpha / omega);                                       // :103
@@ -1797,7 +1898,7 @@ int mgs_bicgstab(const mgs_csr *A, mgs_vec *x, const mgs_vec *b, mgs_hier *h, in
     tmp = std::sqrt(d2[0]);
     if ((resid = tmp / normb) < *tol) {                                               // :110-115
       MGS_TRY(mgs_axpby(alpha, &phv, 1.0, &xv));
-      *max_iter = i; *tol = resid; *status = 0; return mgs_sync(ctx);
+      *max_iter = i; *tol = resid; *status = 0; return fin();
     }
     MGS_TRY(precond(s, shat));                                                        // :116
     if (halo0(shat)) return mgs_fail(ctx, MGS_ERR_STATE, "halo exchange failed");
@@ -1805,11 +1906,11 @@ int mgs_bicgstab(const mgs_csr *A, mgs_vec *x, const mgs_vec *b, mgs_hier *h, in
     MGS_TRY(mgs_axpbypcz(alpha, &phv, omega, &shv, 1.0, &xv));                        // :119
     MGS_TRY(k_update_dot2(ctx, n, 1.0, s->d, -omega, t->d, r->d, rt->d, d2));       // :120 r = s − ωt with ‖r‖² (:123) and the next (r̃,r) (:95)
     rho_2 = rho_1;                                                                    // :122
-    if ((resid = std::sqrt(d2[0]) / normb) < *tol) { *tol = resid; *max_iter = i; *status = 0; return mgs_sync(ctx); }   // :123-127
-    if (omega == 0) { *tol = resid; *status = 3; return mgs_sync(ctx); }              // :128-131
+    if ((resid = std::sqrt(d2[0]) / normb) < *tol) { *tol = resid; *max_iter = i; *status = 0; return fin(); }   // :123-127
+    if (omega == 0) { *tol = resid; *status = 3; return fin(); }              // :128-131
   }
   *tol = resid; *status = 1;                                                          // :134-135
-  return mgs_sync(ctx);
+  return fin();
 }
 
 // Preconditioned conjugate gradients for symmetric positive definite A: the reference's Matlab driver, src/CPU_Matlab/solve.m:28-31
@@ -1830,6 +1931,8 @@ int mgs_pcg(const mgs_csr *A, mgs_vec *x, const mgs_vec *b, mgs_hier *h, int fle
   MGS_CHECK(ctx, max_iter && tol && status, MGS_ERR_INVALID, "mgs_pcg: NULL out parameter");
   MGS_CHECK(ctx, flexible || !h || (h->nu1 == h->nu2 && h->kcycle_levels <= 0 && !h->kcycle_entry), MGS_ERR_INVALID,
             "mgs_pcg: flexible = 0 needs a fixed symmetric preconditioner (nu1 == nu2, no K-cycle); pass flexible = 1");
+  bool ns = false;
+  MGS_TRY(krylov_nullspace(A, h, "mgs_pcg", &ns));
   MGS_TRY(mgs_csr_optimize(const_cast<mgs_csr *>(A)));
   const int n = A->rows, next = A->cols > n ? A->cols : n;
   MGS_CHECK(ctx, x->n >= n && b->n >= n, MGS_ERR_INVALID, "mgs_pcg: vectors shorter than %d", n);
@@ -1849,22 +1952,32 @@ int mgs_pcg(const mgs_csr *A, mgs_vec *x, const mgs_vec *b, mgs_hier *h, int fle
   };
   double normb = 0, resid = 0, rho = 0, rho_prev = 0, alpha = 0, beta = 0, d2[2] = {0, 0};
   bool pending = false;                                    // x is one step behind: x += alpha·p not applied yet
+  bool x_mean = ns;                                        // constant null space: x may carry a constant component (the guess's, or an update's rounding)
   auto flush = [&]() -> int {
     if (pending) { MGS_TRY(mgs_axpby(alpha, &pv, 1.0, &xv)); pending = false; }
     return MGS_OK;
   };
-  auto true_residual = [&]() -> int {                     // r = b − A·x (x flushed by the caller), resid = ‖r‖/‖b‖
+  auto project_x = [&]() -> int {                         // x ← Πx (x flushed by the caller): after the last update, before the final true residual
+    if (x_mean) { MGS_TRY(k_project_const(ctx, n, xv.d)); x_mean = false; }
+    return MGS_OK;
+  };
+  auto true_residual = [&]() -> int {                     // r = b − A·x (x flushed by the caller), resid = ‖r‖/‖b‖; constant null space: r = Π(b − A·x), ‖r‖/‖Πb‖
     mgs_vec *xin = x;
     if (xe) { MGS_TRY(mgs_vec_copy(&xv, xe)); xin = xe; }
     if (halo0(xin)) return mgs_fail(ctx, MGS_ERR_STATE, "halo exchange failed");
     MGS_TRY(mgs_residual(A, xin, &bv, r));
     double s = 0;
-    MGS_TRY(k_dot(ctx, n, r->d, r->d, &s));
+    if (ns) { double s2[2]; MGS_TRY(k_project_const_nrm2(ctx, n, r->d, s2)); s = s2[0]; }
+    else MGS_TRY(k_dot(ctx, n, r->d, r->d, &s));
     resid = std::sqrt(s) / normb;
     return MGS_OK;
   };
-  auto done = [&](int it, int st) -> int { int rc = flush(); *max_iter = it; *tol = resid; *status = st; return rc != MGS_OK ? rc : mgs_sync(ctx); };
-  MGS_TRY(mgs_nrm2(&bv, &normb));
+  auto done = [&](int it, int st) -> int {
+    int rc = flush(); if (rc == MGS_OK) rc = project_x();
+    *max_iter = it; *tol = resid; *status = st; return rc != MGS_OK ? rc : mgs_sync(ctx);
+  };
+  if (ns) { MGS_TRY(k_const_dev_nrm2(ctx, n, bv.d, d2)); normb = std::sqrt(d2[0]); }      // ‖Πb‖, b only read
+  else MGS_TRY(mgs_nrm2(&bv, &normb));
   if (normb == 0.0) normb = 1;
   MGS_TRY(true_residual());
   if (resid <= *tol) return done(0, 0);
@@ -1872,6 +1985,7 @@ int mgs_pcg(const mgs_csr *A, mgs_vec *x, const mgs_vec *b, mgs_hier *h, int fle
   bool restart = true;                                     // the next direction is p = z
   for (int i = 1; i <= maxit; ++i) {
     if (h) MGS_TRY(mgs_vcycle(h, r, z, 1)); else MGS_TRY(mgs_vec_copy(r, z));
+    if (ns) MGS_TRY(k_project_const(ctx, n, z->d));        // z ← Πz: the preconditioner seen is ΠMΠ
     if (flexible && !restart) { MGS_TRY(k_dot2(ctx, n, r->d, z->d, q->d, z->d, d2)); rho = d2[0]; }
     else MGS_TRY(k_dot(ctx, n, r->d, z->d, &rho));
     if (!(rho > 0)) return done(i, 2);                     // preconditioner not positive definite (or not a number)
@@ -1887,11 +2001,12 @@ int mgs_pcg(const mgs_csr *A, mgs_vec *x, const mgs_vec *b, mgs_hier *h, int fle
     if (halo0(p)) return mgs_fail(ctx, MGS_ERR_STATE, "halo exchange failed");
     MGS_TRY(mgs_spmv_dots(A, p->d, q->d, p->d, d2));      // q = A·p with p·q from the same pass
     if (!(d2[0] > 0)) return done(i, 3);                   // A not positive definite along p
-    alpha = rho / d2[0]; pending = true;
+    alpha = rho / d2[0]; pending = true; x_mean = ns;
     MGS_TRY(k_pcg_residual(ctx, n, alpha, r->d, q->d, d2));
     resid = std::sqrt(d2[0]) / normb; rho_prev = rho;
     if (resid < *tol) {                                    // the recursion says converged: the true residual decides
       MGS_TRY(flush());
+      MGS_TRY(project_x());
       MGS_TRY(true_residual());
       if (resid < *tol) return done(i, 0);
       restart = true;                                      // the recursion had drifted: r holds the true residual, start over from it
@@ -1917,6 +2032,8 @@ int mgs_fgcr(const mgs_csr *A, mgs_vec *x, const mgs_vec *b, mgs_hier *h, int re
   mgs_ctx *ctx = A->ctx;
   MGS_CHECK(ctx, max_iter && tol && status && restart >= 1 && restart <= 64, MGS_ERR_INVALID, "mgs_fgcr: bad arguments");
   MGS_CHECK(ctx, A->rows == A->cols && x->n >= A->rows && b->n >= A->rows, MGS_ERR_INVALID, "mgs_fgcr: square unsharded operator required");
+  bool ns = false;
+  MGS_TRY(krylov_nullspace(A, h, "mgs_fgcr", &ns));
   MGS_TRY(mgs_csr_optimize(const_cast<mgs_csr *>(A)));
   const int n = A->rows;
   constexpr int CH = 16;                             // vectors per multi-vector pass (kernels_aux.hip: MDOT_MAX)
@@ -1928,17 +2045,26 @@ int mgs_fgcr(const mgs_csr *A, mgs_vec *x, const mgs_vec *b, mgs_hier *h, int re
   mgs_vec xv; xv.ctx = ctx; xv.n = n; xv.d = x->d; xv.owns = false;
   mgs_vec bv; bv.ctx = ctx; bv.n = n; bv.d = b->d; bv.owns = false;
   double normb = 0, nr = 0;
-  MGS_TRY(mgs_nrm2(&bv, &normb));
+  if (ns) { double s2[2]; MGS_TRY(k_const_dev_nrm2(ctx, n, bv.d, s2)); normb = std::sqrt(s2[0]); }      // ‖Πb‖, b only read
+  else MGS_TRY(mgs_nrm2(&bv, &normb));
   if (normb == 0.0) normb = 1;
-  auto true_residual = [&](double *resid_out) -> int {      // r = b − A·x, ‖r‖/‖b‖
+  // r = b − A·x, ‖r‖/‖b‖.  Constant null space: r = Π(b − A·x), ‖r‖/‖Πb‖; with `last` (the call may decide a return: the recursion says
+  // converged, the iterations are used up, a breakdown) x ← Πx first.  An ordinary restart leaves x as it is (A·Πx = A·x); should its true
+  // residual end the solve all the same, fin() projects x behind it.
+  bool x_mean = ns;                                 // x may carry a constant component (the guess's, or a window's rounding)
+  auto true_residual = [&](double *resid_out, bool last) -> int {
+    if (last && x_mean) { MGS_TRY(k_project_const(ctx, n, xv.d)); x_mean = false; }
     MGS_TRY(mgs_residual(A, &xv, &bv, r));
-    MGS_TRY(mgs_nrm2(r, &nr));
+    if (ns) { double s2[2]; MGS_TRY(k_project_const_nrm2(ctx, n, r->d, s2)); nr = std::sqrt(s2[0]); }
+    else MGS_TRY(mgs_nrm2(r, &nr));
     *resid_out = nr / normb;
     return MGS_OK;
   };
   // x ← x + Σ_{j<m} y_j c_j, (I + U) y = α over the m directions of the open window
+  auto fin = [&]() -> int { if (x_mean) { MGS_TRY(k_project_const(ctx, n, xv.d)); x_mean = false; } return mgs_sync(ctx); };
   auto close_window = [&](int m) -> int {
     if (m <= 0) return MGS_OK;
+    x_mean = ns;
     for (int k = m - 1; k >= 0; --k) { double s = alpha[k]; for (int q = k + 1; q < m; ++q) s -= U[(size_t)k * restart + q] * y[q]; y[k] = s; }
     for (int c0 = 0; c0 < m; c0 += CH) {
       const int K = std::min(CH, m - c0);
@@ -1949,8 +2075,8 @@ int mgs_fgcr(const mgs_csr *A, mgs_vec *x, const mgs_vec *b, mgs_hier *h, int re
     return MGS_OK;
   };
   double resid = 0.0;
-  MGS_TRY(true_residual(&resid));
-  if (resid <= *tol) { *tol = resid; *max_iter = 0; *status = 0; return MGS_OK; }
+  MGS_TRY(true_residual(&resid, true));
+  if (resid <= *tol) { *tol = resid; *max_iter = 0; *status = 0; return ns ? mgs_sync(ctx) : MGS_OK; }
   int it = 0;
   while (it < *max_iter) {
     int m = 0;                                       // directions in the open window
@@ -1958,6 +2084,7 @@ int mgs_fgcr(const mgs_csr *A, mgs_vec *x, const mgs_vec *b, mgs_hier *h, int re
     for (int k = 0; k < restart && it < *max_iter && !restart_now; ++k) {
       if (!C[k]) { MGS_TRY(mk(&C[k])); MGS_TRY(mk(&V[k])); }
       if (h) MGS_TRY(mgs_vcycle(h, r, C[k], 1)); else MGS_TRY(mgs_vec_copy(r, C[k]));
+      if (ns) MGS_TRY(k_project_const(ctx, n, C[k]->d));      // c_k ← Πc_k before v_k = A·c_k
       MGS_TRY(mgs_spmv(A, C[k], V[k]));
       double d2[2];
       if (k == 0) {
@@ -1983,26 +2110,26 @@ int mgs_fgcr(const mgs_csr *A, mgs_vec *x, const mgs_vec *b, mgs_hier *h, int re
       if (rho[k] == 0.0) {                             // A·c_k lies in the span of the window: nothing more to gain from it
         alpha[k] = 0.0;
         MGS_TRY(close_window(m));
-        MGS_TRY(true_residual(&resid)); *status = resid < *tol ? 0 : 2; *tol = resid; *max_iter = it; return mgs_sync(ctx);
+        MGS_TRY(true_residual(&resid, true)); *status = resid < *tol ? 0 : 2; *tol = resid; *max_iter = it; return fin();
       }
       alpha[k] = d2[1] / rho[k];
       MGS_TRY(k_update_dot2(ctx, n, 1.0, r->d, -alpha[k], V[k]->d, r->d, nullptr, d2));   // r ← r − α v with ‖r‖²
       resid = std::sqrt(d2[0]) / normb;
       if (resid < *tol) {                         // the recursion says converged: the true residual decides
         MGS_TRY(close_window(m)); m = 0;
-        MGS_TRY(true_residual(&resid));
-        if (resid < *tol) { *tol = resid; *max_iter = it; *status = 0; return mgs_sync(ctx); }
+        MGS_TRY(true_residual(&resid, true));
+        if (resid < *tol) { *tol = resid; *max_iter = it; *status = 0; return fin(); }
         restart_now = true;                       // not yet: restart from the true residual (r holds it)
       }
     }
     if (m) {                                      // window full (or out of iterations): x catches up, r ← b − A·x
       MGS_TRY(close_window(m));
-      MGS_TRY(true_residual(&resid));
-      if (resid < *tol) { *tol = resid; *max_iter = it; *status = 0; return mgs_sync(ctx); }
+      MGS_TRY(true_residual(&resid, it >= *max_iter));
+      if (resid < *tol) { *tol = resid; *max_iter = it; *status = 0; return fin(); }
     }
   }
   *status = resid < *tol ? 0 : 1; *tol = resid; *max_iter = it;
-  return mgs_sync(ctx);
+  return fin();
 }
 
 // ------------------------------------------------------------------ instrumentation

@@ -19,6 +19,10 @@ struct mgs_launch_report {
   int u = 0, flags = 0, capv = 0, capi = 0;   // gather width, the kernel's flags word, LDS budgets (values / ints) of a row block
 };
 constexpr int MGS_RED_VALS = 32;   // results one reduction can hand to the host (mgs_ctx::red_host)
+// mgs_ctx::red_dev (kernels_aux.hip): MGS_DOT_BLOCKS partial slots, then MGS_RED_VALS folded results, then MGS_RED_VALS device-only scalars
+// (the first one: the mean of the last k_project_const)
+constexpr int MGS_DOT_BLOCKS = 4096;
+constexpr int MGS_RED_CAP = MGS_DOT_BLOCKS + 2 * MGS_RED_VALS;
 struct mgs_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -134,6 +138,7 @@ struct mgs_csr {
   int *coo_run = nullptr;   // nnz + 1: first sorted triple of every entry; entry e sums coo_src[coo_run[e] .. coo_run[e + 1])
   int64_t coo_ntrip = 0;
   int coo_max_row = 0;      // most triples one row received
+  int nullspace = MGS_NULLSPACE_NONE;   // mgs_csr_set_nullspace: what the caller declared (hierarchies and Krylov solvers act on it)
 };
 
 struct mgs_vec {
@@ -411,7 +416,15 @@ int k_maxpy_dot2(mgs_ctx *ctx, int64_t n, int K, const double *x, const double *
 int k_kc_update_r(mgs_ctx *ctx, int n, const double *scal, const double *r, const double *v1, double *rp);
 int k_kc_orth_dots(mgs_ctx *ctx, int n, bool energy, double *scal, const double *c1, const double *c2, const double *v1, const double *v2, const double *rp);
 int k_kc_combine(mgs_ctx *ctx, int n, const double *scal, const double *c1, const double *c2, double *x);
-int k_dense_inverse(mgs_ctx *ctx, const mgs_csr *A, double **inv_out);   // *inv_out != NULL on entry: written in place
+int k_dense_inverse(mgs_ctx *ctx, const mgs_csr *A, double **inv_out, int reg_const = 0);   // *inv_out != NULL on entry: written in place; reg_const: A + (max|a_ij|/n)·1·1ᵀ
+// constant null space (MGS_NULLSPACE_CONSTANT): v ← v − mean(v), two launches, the mean stays on the device; _nrm2: out_host2[0] = ‖v − mean‖² from the
+// shift pass; k_const_dev_nrm2: the same norm of a vector that is only read (‖Πb‖ of the caller's right-hand side)
+int k_project_const(mgs_ctx *ctx, int64_t n, double *v);
+int k_project_const_nrm2(mgs_ctx *ctx, int64_t n, double *v, double *out_host2);
+int k_const_dev_nrm2(mgs_ctx *ctx, int64_t n, const double *v, double *out_host2);
+int k_project_const_mean(mgs_ctx *ctx, double *mean_host);   // the mean the last projection subtracted (synchronises)
+int k_abs_inplace(mgs_ctx *ctx, int64_t n, double *v);
+int k_absmax_dev(mgs_ctx *ctx, int64_t n, const double *v, unsigned long long *amax_bits_dev);
 int k_poisson3d(mgs_ctx *ctx, int N, int plane_lo, int plane_hi, int local_cols, mgs_csr **out);
 int k_poisson2d(mgs_ctx *ctx, int n, mgs_csr **out);
 int k_gather(mgs_ctx *ctx, const double *x, const int *idx, int64_t n, double *out);

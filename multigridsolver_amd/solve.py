@@ -36,11 +36,16 @@ def main(argv=None):
     ap.add_argument("--tou", type=float, default=8.0)
     ap.add_argument("--operand-bits", type=int, choices=[64, 32], default=64,
                     help="stored precision of the cycle's matrix operands Â and A·P (32: values rounded to float, arithmetic stays FP64; single GPU only)")
+    ap.add_argument("--nullspace", choices=["none", "constant"], default="none",
+                    help="constant: A·1 = 0 and 1ᵀ·A = 0 (pure-Neumann operators, graph Laplacians) — regularised coarsest solve, projected Krylov method, "
+                         "zero-mean solution; single GPU only")
     ap.add_argument("--dump-x", default=None, help="write the solution (rank order, raw little-endian f64)")
     args = ap.parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1")); rank = int(os.environ.get("RANK", "0"))
     if world > 1 and args.operand_bits != 64:
         raise SystemExit("multi-GPU: FP64 operands only (--operand-bits 32 is a single-GPU option)")
+    if world > 1 and args.nullspace != "none":
+        raise SystemExit("multi-GPU: --nullspace is a single-GPU option (row shards carry no null-space declaration)")
     if world > 1:
         import torch  # noqa: F401  — before libmgs.so: both link a HIP runtime, the first one loaded serves the process
     import multigridsolver_amd as mg
@@ -53,6 +58,10 @@ def main(argv=None):
         if args.kcycle_energy:
             ctx.set_option("kcycle_energy", 1)
         A = ctx.csr(rows, cols, rp, ci, v)
+        defect = None
+        if args.nullspace == "constant":      # before the hierarchy is built: finalize() regularises the coarsest solve
+            A.set_nullspace("constant")
+            defect = A.nullspace_defect()
         h = mg.Hierarchy(A, args.omega, args.nu1, args.nu2)
         if args.P:
             h.push_P(mg.Csr.from_mtx(ctx, args.P))
@@ -67,6 +76,8 @@ def main(argv=None):
             st, it, tol = (mg.bicgstab if args.solver == "bicgstab" else lambda *a: mg.fgcr(a[0], a[1], a[2], a[3], 10, a[4], a[5]))(A, x, b, h, args.max_iter, args.tol)
         ctx.sync(); dt = time.perf_counter() - t0
         xs = x.numpy()
+        if defect is not None:
+            print("    \033[32m\033[1m[info] \033[00m%-42s : %g (rows), %g (columns)." % ("Null-space defect |A.1|/||A|.1| ", defect[0], defect[1]))
     else:
         import torch
         import torch.distributed as dist

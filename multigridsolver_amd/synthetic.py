@@ -1,6 +1,8 @@
 """Host-side generators of synthetic operators for tests and bench.py (numpy/scipy only; the Poisson operator of BASELINE.json
 configs[4] is generated on the device by `mgs_csr_poisson3d`).
 
+`neumann3d(N)`: the 7-point Laplacian with natural boundary rows — singular, constant null space (Csr.set_nullspace("constant")).
+
 `convdiff3d(N)`: a labelled STAND-IN for the reference's `matvf3dSky*` / `CSky3d*` problem class (the paper's nonsymmetric
 convection-diffusion with "skyscraper" coefficient jumps, docs/AGMG_For_Convection_Diffusion.pdf §5; matrices/CSky3d30.mtx is the 30^3
 member bundled with the reference, the 80^3 one is absent — /root/reference/.MISSING_LARGE_BLOBS).  It is NOT one of those matrices:
@@ -92,6 +94,29 @@ def convdiff3d(N, jump=1e3, vel_scale=200.0, chunk_planes=None, workers=None):
     np.cumsum(counts, out=rowptr[1:])
     assert rowptr[-1] < 2 ** 31
     return rowptr.astype(np.int32), np.concatenate(cols_out), np.concatenate(vals_out)
+
+
+def neumann3d(N):
+    """7-point Laplacian on an N^3 grid with natural (Neumann) boundary rows: off-diagonals −1 towards every neighbour inside the grid,
+    diagonal = number of neighbours, so every row and column sums to zero (A·1 = 0: the constant null space of
+    Csr.set_nullspace("constant")).  Rows e = (i*N + j)*N + k, sorted columns.  Returns (rowptr i32, col i32, val f64)."""
+    n = N ** 3
+    ax = np.arange(N, dtype=np.int64)
+    idx = (ax[:, None, None] * N + ax[None, :, None]) * N + ax[None, None, :]
+    coord = np.broadcast_arrays(ax[:, None, None], ax[None, :, None], ax[None, None, :])
+    cand_col = np.empty((N, N, N, 7), dtype=np.int64); cand_val = np.zeros((N, N, N, 7)); present = np.zeros((N, N, N, 7), dtype=bool)
+    stride = (N * N, N, 1)
+    slot = {(0, -1): 0, (1, -1): 1, (2, -1): 2, (2, 1): 4, (1, 1): 5, (0, 1): 6}
+    for d in range(3):
+        for sgn in (-1, 1):
+            inside = (coord[d] + sgn >= 0) & (coord[d] + sgn < N)
+            s_ = slot[(d, sgn)]
+            cand_col[..., s_] = idx + sgn * stride[d]; cand_val[..., s_] = -1.0; present[..., s_] = inside
+    cand_col[..., 3] = idx; cand_val[..., 3] = present.sum(axis=-1); present[..., 3] = True
+    rowptr = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(present.reshape(-1, 7).sum(axis=1), out=rowptr[1:])
+    assert rowptr[-1] < 2 ** 31
+    return rowptr.astype(np.int32), cand_col[present].astype(np.int32), cand_val[present]
 
 
 CSKY_ROWSUM_MARGIN = 2.86e-6      # the bundled CSky3d30's printed interior row sums, relative to the diagonal (median; 95 % of its interior rows)
