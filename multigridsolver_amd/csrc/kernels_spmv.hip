@@ -25,10 +25,11 @@
 #include "mgs_internal.hpp"
 
 #include <algorithm>
+#include <type_traits>
 
 namespace {
 
-constexpr int RB = 256;         // rows per row block == threads per workgroup
+constexpr int RB = MGS_RB;      // rows per row block == threads per workgroup
 constexpr int LDS_CAP_MAX = 5120;  // products (doubles) staged per block: 40 KiB → 4 blocks/CU
 
 template <bool NT, class T>
@@ -1258,6 +1259,92 @@ __global__ void plan_kernel(int n, const int *__restrict__ rowptr, const int *__
   if ((threadIdx.x & 63) == 0) { atomicMax(&out[0], mx); atomicMax(&out[1], mr); atomicMax(&out[2], far); }
 }
 
+// ------------------------------------------------------------------ launch layer: every launch decision is made in one function below
+// Template fan-out: a run-time value reaches a kernel's template argument through one of these helpers, which calls f with the value as a
+// std::integral_constant.  Each helper lists exactly the values its kernels are instantiated for.
+template <int V> using int_c = std::integral_constant<int, V>;
+template <class F> void with_bool(bool v, F f) { if (v) f(std::true_type{}); else f(std::false_type{}); }
+// gather widths (gather_width below); FIVE: and the post pass's 5 (post_gather_width)
+template <bool FIVE, class F> void with_width(int u, F f) {
+  if constexpr (FIVE) { if (u == 5) return f(int_c<5>{}); }
+  if (u == 4) f(int_c<4>{}); else if (u == 7) f(int_c<7>{}); else f(int_c<8>{});
+}
+// lanes per row of the long-row path
+template <class F> void with_lanes(int n, F f) {
+  if (n == 4) f(int_c<4>{}); else if (n == 8) f(int_c<8>{}); else if (n == 16) f(int_c<16>{}); else if (n == 32) f(int_c<32>{}); else f(int_c<64>{});
+}
+// the operator kernels' ops; false: op is none of them (f not called)
+template <class F> bool with_csr_op(int op, F f) {
+  if (op == MGS_OP_SPMV) f(int_c<MGS_OP_SPMV>{}); else if (op == MGS_OP_RESIDUAL) f(int_c<MGS_OP_RESIDUAL>{});
+  else if (op == MGS_OP_JACOBI) f(int_c<MGS_OP_JACOBI>{}); else return false;
+  return true;
+}
+// the gather kernel's passes
+template <class F> void with_fused_pass(int which, F f) {
+  if (which == FUSE_POST_MAPPED) f(int_c<FUSE_POST_MAPPED>{}); else if (which == FUSE_PRE) f(int_c<FUSE_PRE>{}); else f(int_c<FUSE_POST>{});
+}
+// value type of an operand's stored values from the pointer that carries them (A->val or A->val32)
+template <class P> using pointee_t = std::remove_cv_t<std::remove_pointer_t<P>>;
+
+inline double mean_row_len(const mgs_csr *A) { return A->rows ? (double)A->nnz / A->rows : 1.0; }
+// U = gathers per step of the row walk: the typical row length (7-point stencils: exactly one step)
+int gather_width(const mgs_csr *A) {
+  const double mean_len = mean_row_len(A);
+  return mean_len <= 4.5 ? 4 : (mean_len <= 7.5 && A->max_row_len <= 14 ? 7 : 8);
+}
+// post pass only: A·P of a 7-point operator with aggregates of four has 5 entries per row: one unrolled step of 5 instead of 7
+int post_gather_width(const mgs_csr *A) {
+  const double mean_len = mean_row_len(A);
+  return mean_len > 4.5 && mean_len <= 5.5 && A->max_row_len <= 10 ? 5 : gather_width(A);
+}
+// streaming stores of the output (option nt_store: operators with at least that many rows)
+bool nt_store_on(const mgs_csr *A) { return A->ctx->opt_nt_store > 0 && A->rows >= A->ctx->opt_nt_store; }
+// flags word of the row-block kernels.  bit 0 (`first`): the coded kernels (coded_block_body) — no row is longer than the gather width; the slice
+// kernel and the grouped pre pass — streaming stores (nt_store_on).  bit 1: option stage_unroll.  bit 2: option rowptr_scan (the kernels that
+// read a pattern code only: `coded`)
+int kernel_flags(const mgs_ctx *ctx, bool first, bool coded) {
+  return (first ? 1 : 0) | (ctx->opt_stage_unroll ? 2 : 0) | (coded && ctx->opt_rowptr_scan ? 4 : 0);
+}
+// row blocks of the slice kernel's launch take their bounds from the compact blkptr array (option blkptr; 0: from rowptr)
+const int *blkptr_opt(const mgs_csr *A) { return A->ctx->opt_blkptr ? A->blkptr : nullptr; }
+
+// strip-major sweep of period D (row blocks or groups) with strips of S: installs D, S, P and the multiply-high constants of
+// map_block_xi and returns the workgroups per XCD — or leaves the plain XCD-contiguous map (returns bm.chunk) where a quotient would
+// not be exact by multiply-high (idx·divisor ≥ 2³²: never at the sizes 288 GB hold, checked all the same)
+int strip_map(BlockMap &bm, int D, int S) {
+  const int P = (bm.chunk + D - 1) / D;
+  const int per_xcd = ((D + S - 1) / S) * P * S;
+  const unsigned long long ps = (unsigned long long)P * (unsigned long long)S;
+  // (S < 2: ⌊2³²/1⌋+1 does not fit 32 bits — the multiply-high quotient would be 0 instead of the dividend; a strip of one block is
+  // the plain plane-major order anyway, so the plain XCD-contiguous map serves)
+  if (D <= 0 || S < 2 || ps < 2 || ((unsigned long long)per_xcd + 1) * ps >= (1ull << 32) || ps * (unsigned long long)S >= (1ull << 32)) { bm.D = bm.S = bm.P = 0; return bm.chunk; }
+  bm.D = D; bm.S = S; bm.P = P;
+  bm.mps = (unsigned)((1ull << 32) / ps) + 1u;
+  bm.mS = (unsigned)((1ull << 32) / (unsigned long long)S) + 1u;
+  return per_xcd;
+}
+// The one planner of a workgroup → unit map (units: row blocks, row-block groups, super blocks): `units` of them from `base` on, XCD-contiguous
+// from 64 units up (option xcd_remap); returns the grid.  Strip-major sweep (option strip; strips of `strip` units) when three x planes
+// (3·far·8 B) overflow an XCD's L2 share — a far band `D` units away, D >= d_min — and the XCD's range holds at least two planes.
+// gap_at / gap_len stay as the caller set them.
+dim3 plan_map(const mgs_ctx *ctx, BlockMap &bm, int base, int units, int D, int d_min, int strip) {
+  bm.base = base; bm.nblocks = units;
+  bm.remap = ctx->opt_xcd_remap && bm.nblocks >= 64;
+  bm.chunk = (bm.nblocks + 7) / 8;
+  bm.D = 0; bm.S = 0; bm.P = 0;
+  int per_xcd = bm.chunk;
+  if (bm.remap && ctx->opt_strip != 0 && D >= d_min && bm.chunk >= 2 * D) per_xcd = strip_map(bm, D, strip);
+  return dim3(bm.remap ? per_xcd * 8 : bm.nblocks);
+}
+// workgroup → row-block map of a launch over the row blocks [blk_lo, blk_hi) with their gap (BlockMap): far band of at least 512 row blocks,
+// strips of 64 by default
+dim3 plan_block_map(const mgs_csr *A, int blk_lo, int blk_hi, int gap_at, int gap_len, BlockMap &bm) {
+  const mgs_ctx *ctx = A->ctx;
+  bm.gap_at = gap_at; bm.gap_len = gap_len;
+  return plan_map(ctx, bm, blk_lo, blk_hi - blk_lo, (A->far_band + RB - 1) / RB, 512, ctx->opt_strip > 0 ? ctx->opt_strip : 64);
+}
+
+// A/B-only launchers (variants 2–4 here, 6 and 7 below launch_slice): kept as they were, run by no test
 template <int OP, bool NT, int CHUNK>
 int launch_lanes(const mgs_csr *A, int lanes, dim3 grid, size_t lds, const double *x, const double *b,
                  const double *dinv, double omega, double *out, int cap, BlockMap bm) {
@@ -1275,28 +1362,18 @@ int launch_lanes(const mgs_csr *A, int lanes, dim3 grid, size_t lds, const doubl
 #undef L_
   return MGS_OK;
 }
+// the slice kernel (default path of operators without a usable pattern code; variant 1: cap < 0, every row block on the long-row path)
 template <int OP, bool NT>
 int launch_slice(const mgs_csr *A, int lanes, dim3 grid, const double *x, const double *b,
                  const double *dinv, double omega, double *out, int cap, BlockMap bm) {
-  hipStream_t s = A->ctx->stream;
   const size_t lds = (size_t)(cap > 0 ? cap + 2 : 2) * 12 + 16 + (size_t)A->ctx->opt_lds_pad;   // opt_lds_pad: occupancy experiments
-  // U = gathers per step of the row walk: the typical row length (7-point stencils: exactly one step)
-  const double mean_len = A->rows ? (double)A->nnz / A->rows : 1.0;
-  const int u = mean_len <= 4.5 ? 4 : (mean_len <= 7.5 && A->max_row_len <= 14 ? 7 : 8);
-#define L_(LN)                                                                                                 \
-  do {                                                                                                         \
-    if (u == 4) hipLaunchKernelGGL((csr_rowblock_slice_kernel<OP, NT, LN, 4>), grid, dim3(RB), lds, s, A->rows, A->rowptr, A->col, A->val, x, b, dinv, omega, out, cap, bm, A->max_row_len <= 64 ? 1 : 0, A->ctx->opt_blkptr ? A->blkptr : nullptr, ((A->ctx->opt_nt_store > 0 && A->rows >= A->ctx->opt_nt_store) ? 1 : 0) | (A->ctx->opt_stage_unroll ? 2 : 0)); \
-    else if (u == 7) hipLaunchKernelGGL((csr_rowblock_slice_kernel<OP, NT, LN, 7>), grid, dim3(RB), lds, s, A->rows, A->rowptr, A->col, A->val, x, b, dinv, omega, out, cap, bm, A->max_row_len <= 64 ? 1 : 0, A->ctx->opt_blkptr ? A->blkptr : nullptr, ((A->ctx->opt_nt_store > 0 && A->rows >= A->ctx->opt_nt_store) ? 1 : 0) | (A->ctx->opt_stage_unroll ? 2 : 0)); \
-    else hipLaunchKernelGGL((csr_rowblock_slice_kernel<OP, NT, LN, 8>), grid, dim3(RB), lds, s, A->rows, A->rowptr, A->col, A->val, x, b, dinv, omega, out, cap, bm, A->max_row_len <= 64 ? 1 : 0, A->ctx->opt_blkptr ? A->blkptr : nullptr, ((A->ctx->opt_nt_store > 0 && A->rows >= A->ctx->opt_nt_store) ? 1 : 0) | (A->ctx->opt_stage_unroll ? 2 : 0)); \
-  } while (0)
-  switch (lanes) {
-    case 4: L_(4); break;
-    case 8: L_(8); break;
-    case 16: L_(16); break;
-    case 32: L_(32); break;
-    default: L_(64); break;
-  }
-#undef L_
+  const int flags = kernel_flags(A->ctx, nt_store_on(A), false);
+  with_lanes(lanes, [&](auto LN) {
+    with_width<false>(gather_width(A), [&](auto U) {
+      hipLaunchKernelGGL((csr_rowblock_slice_kernel<OP, NT, decltype(LN)::value, decltype(U)::value>), grid, dim3(RB), lds, A->ctx->stream,
+                         A->rows, A->rowptr, A->col, A->val, x, b, dinv, omega, out, cap, bm, A->max_row_len <= 64 ? 1 : 0, blkptr_opt(A), flags);
+    });
+  });
   return MGS_OK;
 }
 template <int OP, bool NT>
@@ -1309,6 +1386,41 @@ int launch_chunk(const mgs_csr *A, int chunk_elems, int lanes, dim3 grid, size_t
     default: return launch_lanes<OP, NT, 4>(A, lanes, grid, lds, x, b, dinv, omega, out, cap, bm);
   }
 }
+// pipelined variant (6): G row blocks per workgroup; block map over super blocks
+int launch_pipe(const mgs_csr *A, int op, const double *x, const double *b, const double *dinv, double omega, double *out, int cap,
+                const BlockMap &bm) {
+  mgs_ctx *ctx = A->ctx;
+  constexpr int G = 4;
+  const int nrb = bm.nblocks;
+  BlockMap sm = bm;
+  // base stays in row-block units inside the kernel: bm.base + first + j
+  dim3 g = plan_map(ctx, sm, bm.base, (nrb + G - 1) / G, ((A->far_band + RB - 1) / RB + G - 1) / G, 64,
+                    ctx->opt_strip > 0 ? std::max(1, ctx->opt_strip / G) : 16);
+  const size_t lds = (size_t)(cap + 2) * 12 + 16;
+  hipStream_t st = ctx->stream;
+  const bool ntp = ctx->opt_nontemporal != 0;
+#define P_(O, NTV) hipLaunchKernelGGL((csr_rowblock_pipe_kernel<O, NTV, 4, G>), g, dim3(RB), lds, st, A->rows, A->rowptr, A->col, A->val, x, b, dinv, omega, out, cap, sm, nrb)
+  if (op == MGS_OP_SPMV) { if (ntp) P_(MGS_OP_SPMV, true); else P_(MGS_OP_SPMV, false); }
+  else if (op == MGS_OP_RESIDUAL) { if (ntp) P_(MGS_OP_RESIDUAL, true); else P_(MGS_OP_RESIDUAL, false); }
+  else { if (ntp) P_(MGS_OP_JACOBI, true); else P_(MGS_OP_JACOBI, false); }
+#undef P_
+  MGS_HIP(ctx, hipGetLastError());
+  return MGS_OK;
+}
+// wave variant (7): four workgroups of one wave per row block
+int launch_wave(const mgs_csr *A, int op, const double *x, const double *b, const double *dinv, double omega, double *out, dim3 grid,
+                const BlockMap &bm) {
+  mgs_ctx *ctx = A->ctx;
+  const int capw = A->max_wave_nnz;
+  dim3 g(grid.x * 4);
+  const size_t ldsw = (size_t)(capw + 2) * 12 + 16;
+  hipStream_t st = ctx->stream;
+#define W_(O) hipLaunchKernelGGL((csr_wave_slice_kernel<O>), g, dim3(64), ldsw, st, A->rows, A->rowptr, A->col, A->val, x, b, dinv, omega, out, capw, bm)
+  if (op == MGS_OP_SPMV) W_(MGS_OP_SPMV); else if (op == MGS_OP_RESIDUAL) W_(MGS_OP_RESIDUAL); else W_(MGS_OP_JACOBI);
+#undef W_
+  MGS_HIP(ctx, hipGetLastError());
+  return MGS_OK;
+}
 
 }  // namespace
 
@@ -1317,7 +1429,7 @@ int mgs_plan_csr(mgs_csr *A) {
   A->max_row_len = 0;
   A->lds_cap = 0;
   if (A->rows == 0) return MGS_OK;
-  int nblocks = (A->rows + RB - 1) / RB;
+  int nblocks = mgs_row_blocks(A);
   if (A->blkptr) { mgs_hip_free(A->blkptr); A->blkptr = nullptr; }
   MGS_TRY(mgs_dev_alloc(ctx, &A->blkptr, (size_t)nblocks + 1));
   hipLaunchKernelGGL(blkptr_kernel, dim3((nblocks + 256) / 256), dim3(256), 0, ctx->stream, A->rows, A->rowptr, nblocks, A->blkptr);
@@ -1443,131 +1555,99 @@ static bool use_rowcode(const mgs_csr *A, const mgs_rowcode *c, bool any = false
   return c && A->ctx->opt_rowcode && A->blkptr && A->lds_cap > 0 && A->max_row_len <= 64 &&
          (any || (double)c->coded_blocks >= 0.5 * c->nblocks);
 }
-// flags word of the coded kernels (coded_block_body): bit 0 no row is longer than the gather width, bit 1 option stage_unroll, bit 2 option rowptr_scan
-#define KFLAGS_(UU) ((A->max_row_len <= (UU) ? 1 : 0) | (ctx->opt_stage_unroll ? 2 : 0) | (ctx->opt_rowptr_scan ? 4 : 0))
-// LDS sizing of the float forms: capv a multiple of 4 (the integer region behind the values stays 16-byte aligned for the int4 stores of
-// the uncoded blocks), whose index slice may reach capv + 6 entries (both ends of the slice aligned to 4)
-static inline int capv_f32(const mgs_csr *A) { return (A->lds_cap + 3) & ~3; }
-static inline int capi_f32(const mgs_rowcode *c, int capv) {
+// LDS budget of one row block of the coded kernels (c may be NULL: nothing coded): capv values, capi ints, and the bytes of the two regions
+struct coded_lds {
+  int capv, capi;
+  size_t val_bytes, int_bytes, pad_bytes;      // pad_bytes: what every launch adds behind the regions (alignment slack + option lds_pad)
+};
+static coded_lds coded_budget(const mgs_csr *A, const mgs_rowcode *c, bool f32) {
+  coded_lds l;
+  // float values: capv a multiple of 4 (the integer region behind the values stays 16-byte aligned for the int4 stores of the uncoded
+  // blocks), whose index slice may reach capv + 6 entries (both ends of the slice aligned to 4)
+  l.capv = f32 ? (A->lds_cap + 3) & ~3 : A->lds_cap;
+  // nearly everything coded: LDS holds values + tables only (8 B per entry → more workgroups per CU); otherwise
+  // the integer region must also fit the index slice of the uncoded blocks
   const bool lean = c && (double)c->coded_blocks >= 0.985 * c->nblocks;
-  return lean ? std::max(c->tab_cap, 64) : std::max(c ? c->tab_cap : 0, capv + 8);
+  l.capi = lean ? std::max(c->tab_cap, 64) : std::max(c ? c->tab_cap : 0, l.capv + (f32 ? 8 : 2));
+  l.val_bytes = (size_t)(f32 ? val_region<float>(l.capv) : val_region<double>(l.capv)) * 8;
+  l.int_bytes = (size_t)l.capi * 4;
+  l.pad_bytes = 16 + (size_t)A->ctx->opt_lds_pad;      // opt_lds_pad: occupancy experiments
+  return l;
 }
-// The pre pass (RESIDUAL on Â) and the post pass (FUSE_POST_MAPPED on A·P) of an FP32 level: the same coded kernel instantiated for float
-// values (A->val32).  Serves any unsharded operator with short rows — c may be NULL or code only a few blocks: the uncoded blocks stage
-// their index slice — so a level switched to FP32 never falls back to a kernel that reads the FP64 values.
-static int launch_coded_f32(const mgs_csr *A, const mgs_rowcode *c, int op, const int *idx, const double *x, const double *b, const double *dinv,
-                            const double *xin, const int *agg, double *out, dim3 grid, BlockMap bm) {
-  mgs_ctx *ctx = A->ctx;
-  if (op != MGS_OP_RESIDUAL && op != FUSE_POST_MAPPED) return mgs_fail(ctx, MGS_ERR_INVALID, "FP32 operand values: op %d has no float form", op);
-  if (c && c->vtab) c = nullptr;      // value tuples are FP64: not this path (the setter refuses option valcode)
-  const int capv = capv_f32(A), capi = capi_f32(c, capv);
-  const size_t lds = (size_t)val_region<float>(capv) * 8 + (size_t)capi * 4 + 16 + (size_t)ctx->opt_lds_pad;
-  const double mean_len = A->rows ? (double)A->nnz / A->rows : 1.0;
-  const int u = mean_len <= 4.5 ? 4 : (mean_len <= 7.5 && A->max_row_len <= 14 ? 7 : 8);
-#define F_(O, UU) hipLaunchKernelGGL((csr_rowblock_coded_kernel<O, UU, false, false, float>), grid, dim3(RB), lds, ctx->stream, A->rows, A->rowptr, idx, A->val32, \
-                                     c ? c->pid : nullptr, c ? c->tptr : nullptr, c ? c->tab : nullptr, x, b, dinv, 0.0, xin, agg, out, capv, \
-                                     (ctx->opt_nt_store > 0 && A->rows >= ctx->opt_nt_store) ? -capi : capi, bm, A->blkptr, nullptr, 0x7fffffff, nullptr, nullptr, \
-                                     nullptr, nullptr, (A->rows + RB - 1) / RB, KFLAGS_(UU))
-#define FU_(O) do { if (u == 4) F_(O, 4); else if (u == 7) F_(O, 7); else F_(O, 8); } while (0)
-  const bool u5 = op == FUSE_POST_MAPPED && mean_len > 4.5 && mean_len <= 5.5 && A->max_row_len <= 10;
-  if (op == MGS_OP_RESIDUAL) FU_(MGS_OP_RESIDUAL);
-  else if (u5) F_(FUSE_POST_MAPPED, 5);
-  else FU_(FUSE_POST_MAPPED);
-  if (ctx->report && op == FUSE_POST_MAPPED) {
-    const int uu = u5 ? 5 : u;
-    *ctx->report = {2, uu, KFLAGS_(uu), capv, capi};
-  }
-#undef FU_
-#undef F_
-  MGS_HIP(ctx, hipGetLastError());
-  return MGS_OK;
+// the one statement that fills mgs_launch_report: what a post-pass launcher launched (NULL in every cycle: nothing written)
+static void report_launch(const mgs_ctx *ctx, int kernel, int u, int flags, int capv, int capi) {
+  if (ctx->report) *ctx->report = {kernel, u, flags, capv, capi};
 }
-// op ∈ {SPMV, RESIDUAL, JACOBI, FUSE_POST_MAPPED}; for the post pass: x = e_c, b = r, dinv = wd, xin = b, idx = agg[col]
-static dim3 plan_group_map(const mgs_csr *A, const mgs_groups *G, BlockMap &bm);
+// workgroup → group map: XCD-contiguous, strip-major for far bands (distances in groups instead of row blocks)
+static dim3 plan_group_map(const mgs_csr *A, const mgs_groups *G, BlockMap &bm) {
+  const mgs_ctx *ctx = A->ctx;
+  const int Db = (A->far_band + RB - 1) / RB;
+  const int D = Db >= 512 ? G->plane_groups : 0;          // groups from one far-band period to the next (setup: first blocks Db apart)
+  // strip of 128 groups by default: 512³, same-process sweep 5.51 / 5.46 / 5.42 / 5.40 / 5.40 / 5.51 ms per cycle for 2 / 16 / 32 / 64 / 128 / 512 groups
+  const int strip = ctx->opt_group_strip > 0 ? ctx->opt_group_strip : (ctx->opt_strip > 0 ? std::max(1, ctx->opt_strip / 2) : 128);
+  return plan_map(ctx, bm, 0, G->ngroups, D, 64, strip);
+}
+
+// The coded kernel on the view A (idx = its coded index array, c its code).  op ∈ {SPMV, RESIDUAL, JACOBI, FUSE_POST_MAPPED}; for the post
+// pass: x = e_c, b = r, dinv = wd, xin = b, idx = agg[col].  hv/split: halo payload of a row shard.
+// The value type follows A->val32 — the pre pass (RESIDUAL on Â) and the post pass (FUSE_POST_MAPPED on A·P) of an FP32 level run the same
+// kernel instantiated for float values.  That form serves any unsharded operator with short rows — c may be NULL or code only a few blocks:
+// the uncoded blocks stage their index slice — so a level switched to FP32 never falls back to a kernel that reads the FP64 values.
 static int launch_coded(const mgs_csr *A, const mgs_rowcode *c, int op, const int *idx, const double *x, const double *b, const double *dinv,
                         double omega, const double *xin, const int *agg, double *out, dim3 grid, BlockMap bm,
                         const double *hv = nullptr, int split = 0x7fffffff) {
   mgs_ctx *ctx = A->ctx;
-  const int capv = A->lds_cap;
-  // nearly everything coded: LDS holds values + tables only (8 B per entry → more workgroups per CU); otherwise
-  // the integer region must also fit the index slice of the uncoded blocks
-  const bool lean = (double)c->coded_blocks >= 0.985 * c->nblocks;
-  const int capi = lean ? std::max(c->tab_cap, 64) : std::max(c->tab_cap, capv + 2);
-  const size_t lds = (size_t)(capv + 2) * 8 + (size_t)capi * 4 + 16 + (size_t)ctx->opt_lds_pad;
-  const double mean_len = A->rows ? (double)A->nnz / A->rows : 1.0;
-  const int u = mean_len <= 4.5 ? 4 : (mean_len <= 7.5 && A->max_row_len <= 14 ? 7 : 8);
-#define C_(O, UU, H, V) hipLaunchKernelGGL((csr_rowblock_coded_kernel<O, UU, H, V>), grid, dim3(RB), lds, ctx->stream, A->rows, A->rowptr, idx, A->val, \
-                                           c->pid, c->tptr, c->tab, x, b, dinv, (O == FUSE_POST_MAPPED && A->dpos) ? A->dpos_omega : omega, xin, agg, out, capv, \
-                                           (ctx->opt_nt_store > 0 && A->rows >= ctx->opt_nt_store) ? -capi : capi, bm, A->blkptr, hv, split, c->vtab, O == FUSE_POST_MAPPED ? A->dpos : nullptr, \
-                                           O == MGS_OP_SPMV ? A->dot_w1 : nullptr, O == MGS_OP_SPMV ? A->dot_part : nullptr, (A->rows + RB - 1) / RB, KFLAGS_(UU))
-  // group sweep (views with A->sweep set; plain index codes, no halo): one workgroup per row-block group of the grouped pre pass
-  BlockMap gbm; dim3 ggrid(1);
-  const bool sweep = A->sweep && !hv && !c->vtab && op == FUSE_POST_MAPPED;
-  if (sweep) ggrid = plan_group_map(A, A->sweep, gbm);
-#define CG_(O, UU) hipLaunchKernelGGL((csr_rowblock_coded_group_kernel<O, UU, false, false>), ggrid, dim3(RB), lds, ctx->stream, A->rows, A->rowptr, idx, A->val, \
-                                      c->pid, c->tptr, c->tab, x, b, dinv, (O == FUSE_POST_MAPPED && A->dpos) ? A->dpos_omega : omega, xin, agg, out, capv, \
-                                      (ctx->opt_nt_store > 0 && A->rows >= ctx->opt_nt_store) ? -capi : capi, gbm, A->blkptr, hv, split, c->vtab, O == FUSE_POST_MAPPED ? A->dpos : nullptr, \
-                                      nullptr, nullptr, (A->rows + RB - 1) / RB, KFLAGS_(UU), A->sweep->gdesc)
-#define CH_(O, UU) do { if (sweep && O == FUSE_POST_MAPPED) CG_(FUSE_POST_MAPPED, UU); \
-                        else if (hv) { if (c->vtab) C_(O, UU, true, true); else C_(O, UU, true, false); } \
-                        else { if (c->vtab) C_(O, UU, false, true); else C_(O, UU, false, false); } } while (0)
-#define CU_(O) do { if (u == 4) CH_(O, 4); else if (u == 7) CH_(O, 7); else CH_(O, 8); } while (0)
-  const bool u5 = mean_len > 4.5 && mean_len <= 5.5 && A->max_row_len <= 10;      // post pass only
-  switch (op) {
-    case MGS_OP_SPMV: CU_(MGS_OP_SPMV); break;
-    case MGS_OP_RESIDUAL: CU_(MGS_OP_RESIDUAL); break;
-    case MGS_OP_JACOBI: CU_(MGS_OP_JACOBI); break;
-    default:
-      // A·P of a 7-point operator with aggregates of four has 5 entries per row: one unrolled step of 5 instead of 7
-      if (u5) CH_(FUSE_POST_MAPPED, 5); else CU_(FUSE_POST_MAPPED);
-      if (ctx->report) {
-        const int uu = u5 ? 5 : u;
-        *ctx->report = {sweep ? 3 : 1, uu, KFLAGS_(uu), capv, capi};
-      }
-      break;
+  const bool f32 = A->val32 != nullptr;
+  const bool post = op != MGS_OP_SPMV && op != MGS_OP_RESIDUAL && op != MGS_OP_JACOBI;
+  if (f32) {
+    if (op != MGS_OP_RESIDUAL && op != FUSE_POST_MAPPED) return mgs_fail(ctx, MGS_ERR_INVALID, "FP32 operand values: op %d has no float form", op);
+    if (hv) return mgs_fail(ctx, MGS_ERR_INVALID, "FP32 operand values: the coded kernel has no float form on a row shard");
+    if (c && c->vtab) c = nullptr;      // value tuples are FP64: not this path (the setter refuses option valcode)
   }
-#undef CU_
-#undef CH_
-#undef CG_
-#undef C_
+  const coded_lds l = coded_budget(A, c, f32);
+  const size_t lds = l.val_bytes + l.int_bytes + l.pad_bytes;
+  const int u = post ? post_gather_width(A) : gather_width(A);
+  const int flags = kernel_flags(ctx, A->max_row_len <= u, true);
+  const double *vtab = c ? c->vtab : nullptr;
+  const unsigned char *dpos = post && !f32 ? A->dpos : nullptr;      // t-form post pass (FP64 values): ω/a_ii from the streamed values
+  if (dpos) omega = A->dpos_omega;
+  // group sweep (views with A->sweep set; FP64 values, plain index codes, no halo): one workgroup per row-block group of the grouped pre pass
+  const bool sweep = A->sweep && !f32 && !hv && !vtab && op == FUSE_POST_MAPPED;
+  BlockMap gbm; dim3 ggrid(1);
+  if (sweep) ggrid = plan_group_map(A, A->sweep, gbm);
+  // the two wrappers share CODED_PARAMS; `more`: what the group wrapper takes behind them
+  auto launch = [&](auto kernel, auto vals, dim3 g, const BlockMap &m, auto... more) {
+    hipLaunchKernelGGL(kernel, g, dim3(RB), lds, ctx->stream, A->rows, A->rowptr, idx, vals, c ? c->pid : nullptr, c ? c->tptr : nullptr,
+                       c ? c->tab : nullptr, x, b, dinv, omega, xin, agg, out, l.capv, nt_store_on(A) ? -l.capi : l.capi, m, A->blkptr, hv, split,
+                       vtab, dpos, op == MGS_OP_SPMV ? A->dot_w1 : nullptr, op == MGS_OP_SPMV ? A->dot_part : nullptr, mgs_row_blocks(A), flags,
+                       more...);
+  };
+  auto form = [&](auto O, auto H, auto V, auto vals) {
+    constexpr int OP = decltype(O)::value;
+    constexpr bool HALO = decltype(H)::value, VAL = decltype(V)::value;
+    using VT = pointee_t<decltype(vals)>;
+    with_width<OP == FUSE_POST_MAPPED>(u, [&](auto U) {
+      constexpr int UU = decltype(U)::value;
+      if constexpr (OP == FUSE_POST_MAPPED && !HALO && !VAL && std::is_same_v<VT, double>) {
+        if (sweep) return launch(csr_rowblock_coded_group_kernel<OP, UU, false, false>, vals, ggrid, gbm, A->sweep->gdesc);
+      }
+      launch(csr_rowblock_coded_kernel<OP, UU, HALO, VAL, VT>, vals, grid, bm);
+    });
+  };
+  const std::false_type no{};
+  if (f32) {      // the float forms: RESIDUAL and the post pass, never the halo or value-tuple forms
+    if (post) form(int_c<FUSE_POST_MAPPED>{}, no, no, A->val32); else form(int_c<MGS_OP_RESIDUAL>{}, no, no, A->val32);
+  } else {
+    const double *val = A->val;
+    with_bool(hv != nullptr, [&](auto H) {
+      with_bool(vtab != nullptr, [&](auto V) {
+        if (!with_csr_op(op, [&](auto O) { form(O, H, V, val); })) form(int_c<FUSE_POST_MAPPED>{}, H, V, val);
+      });
+    });
+  }
+  if (post) report_launch(ctx, f32 ? 2 : (sweep ? 3 : 1), u, flags, l.capv, l.capi);
   MGS_HIP(ctx, hipGetLastError());
   return MGS_OK;
-}
-
-
-// strip-major sweep of period D (row blocks or groups) with strips of S: installs D, S, P and the multiply-high constants of
-// map_block_xi and returns the workgroups per XCD — or leaves the plain XCD-contiguous map (returns bm.chunk) where a quotient would
-// not be exact by multiply-high (idx·divisor ≥ 2³²: never at the sizes 288 GB hold, checked all the same)
-static int strip_map(BlockMap &bm, int D, int S) {
-  const int P = (bm.chunk + D - 1) / D;
-  const int per_xcd = ((D + S - 1) / S) * P * S;
-  const unsigned long long ps = (unsigned long long)P * (unsigned long long)S;
-  // (S < 2: ⌊2³²/1⌋+1 does not fit 32 bits — the multiply-high quotient would be 0 instead of the dividend; a strip of one block is
-  // the plain plane-major order anyway, so the plain XCD-contiguous map serves)
-  if (D <= 0 || S < 2 || ps < 2 || ((unsigned long long)per_xcd + 1) * ps >= (1ull << 32) || ps * (unsigned long long)S >= (1ull << 32)) { bm.D = bm.S = bm.P = 0; return bm.chunk; }
-  bm.D = D; bm.S = S; bm.P = P;
-  bm.mps = (unsigned)((1ull << 32) / ps) + 1u;
-  bm.mS = (unsigned)((1ull << 32) / (unsigned long long)S) + 1u;
-  return per_xcd;
-}
-// workgroup → group map: XCD-contiguous, strip-major for far bands (distances in groups instead of row blocks)
-static dim3 plan_group_map(const mgs_csr *A, const mgs_groups *G, BlockMap &bm) {
-  mgs_ctx *ctx = A->ctx;
-  bm.base = 0; bm.nblocks = G->ngroups;
-  bm.remap = ctx->opt_xcd_remap && bm.nblocks >= 64;
-  bm.chunk = (bm.nblocks + 7) / 8;
-  bm.D = 0; bm.S = 0; bm.P = 0;
-  int per_xcd = bm.chunk;
-  if (bm.remap && ctx->opt_strip != 0) {
-    const int Db = (A->far_band + RB - 1) / RB;
-    const int D = G->plane_groups;          // groups from one far-band period to the next (setup: first blocks Db apart)
-    if (Db >= 512 && D >= 64 && bm.chunk >= 2 * D) {
-      per_xcd = strip_map(bm, D, ctx->opt_group_strip > 0 ? ctx->opt_group_strip : (ctx->opt_strip > 0 ? std::max(1, ctx->opt_strip / 2) : 128));
-      // strip of 128 groups by default: 512³, same-process sweep 5.51 / 5.46 / 5.42 / 5.40 / 5.40 / 5.51 ms per cycle for 2 / 16 / 32 / 64 / 128 / 512 groups
-    }
-  }
-  const dim3 grid(bm.remap ? per_xcd * 8 : bm.nblocks);
-  return grid;
 }
 
 void mgs_free_groups(mgs_groups *g) {
@@ -1582,7 +1662,7 @@ int mgs_build_groups(mgs_ctx *ctx, const mgs_csr *A, const mgs_xfer *T, mgs_grou
   *out = nullptr;
   const int n = A->rows, nc = T ? T->n_coarse : 0;
   if (!T || !T->aggregation || n <= 0 || nc <= 0 || A->max_row_len > 64 || !A->blkptr || A->lds_cap <= 0) return MGS_OK;
-  const int nblocks = (n + RB - 1) / RB;
+  const int nblocks = mgs_row_blocks(A);
   if (nblocks < ctx->opt_group_min_blocks) return MGS_OK;      // small levels: too few workgroups once blocks are grouped
   hipStream_t st = ctx->stream;
   mgs_groups *G = new mgs_groups();
@@ -1724,37 +1804,37 @@ int mgs_launch_group_pre(const mgs_csr *A, const mgs_groups *G, const mgs_xfer *
   const bool f32 = A->val32 != nullptr;      // FP32 level: the float form (unsharded levels only, the caller sees to that)
   if (f32 && hv) return mgs_fail(ctx, MGS_ERR_INVALID, "grouped pre pass: FP32 operand values on a row shard");
   if (val_nd && (f32 || hv || !nd_code)) return mgs_fail(ctx, MGS_ERR_INVALID, "grouped pre pass: the operand without diagonal serves unsharded FP64 levels only");
-  const int capv = f32 ? capv_f32(A) : A->lds_cap;
-  const bool lean = c && (double)c->coded_blocks >= 0.985 * c->nblocks;
-  const int capi = f32 ? capi_f32(c, capv) : (lean ? std::max(c->tab_cap, 64) : std::max(c ? c->tab_cap : 0, capv + 2));
-  const size_t lds = (size_t)(f32 ? val_region<float>(capv) : capv + 2) * 8 + (size_t)((capi + 1) / 2) * 8 + (size_t)G->max_blocks * RB * 8 + 16 + (size_t)ctx->opt_lds_pad;
+  if (f32) { nd_code = nullptr; omega = 0.0; }      // the float form knows no operand without diagonal
+  // LDS: the coded kernels' two regions (the integer one rounded up to 8 bytes) and, behind them, the residuals of the group's row blocks
+  const coded_lds l = coded_budget(A, c, f32);
+  const size_t regions = l.val_bytes + ((l.int_bytes + 7) & ~(size_t)7);
   BlockMap bm;
   dim3 grid = plan_group_map(A, G, bm);
-  const double mean_len = A->rows ? (double)A->nnz / A->rows : 1.0;
-  const int u = mean_len <= 4.5 ? 4 : (mean_len <= 7.5 && A->max_row_len <= 14 ? 7 : 8);
   const bool pairs = G->max_blocks <= 2 && ctx->opt_group_concurrent && !f32;     // 512 threads, both blocks of a pair at once (FP64 values only)
   const bool ordered = !pairs && G->gorder && ctx->opt_group_order > 0 && ctx->opt_xcd_remap;
   if (ordered) grid = dim3(8 * G->gorder_per_xcd);
-  const size_t lds2 = (size_t)2 * ((size_t)(capv + 2) * 8 + (size_t)((capi + 1) / 2) * 8) + (size_t)2 * RB * 8 + 16 + (size_t)ctx->opt_lds_pad;
-#define G2_(UU, H) hipLaunchKernelGGL((csr_group2_pre_kernel<UU, H>), grid, dim3(2 * RB), lds2, ctx->stream, A->rows, A->rowptr, A->col, A->val, \
-                                      c ? c->pid : nullptr, c ? c->tptr : nullptr, c ? c->tab : nullptr, x, b, t_out, r_out, rc_out, G->gdesc, \
-                                      G->acode, G->wmask, capv, capi, bm, hv, hv ? split : 0x7fffffff)
-#define G_(UU, H, N) hipLaunchKernelGGL((csr_group_pre_kernel<UU, H, double, N>), grid, dim3(RB), lds, ctx->stream, A->rows, A->rowptr, A->col, A->val, \
-                                     c ? c->pid : nullptr, c ? c->tptr : nullptr, c ? c->tab : nullptr, x, b, t_out, r_out, rc_out, G->gdesc, \
-                                     G->acode, G->wmask, capv, capi, bm, hv, hv ? split : 0x7fffffff, ((ctx->opt_nt_store > 0 && A->rows >= ctx->opt_nt_store) ? 1 : 0) | (ctx->opt_stage_unroll ? 2 : 0) | (ctx->opt_rowptr_scan ? 4 : 0), \
-                                     ordered ? G->gorder : nullptr, G->gorder_per_xcd, val_nd, nd_code, omega)
-#define GF_(UU) hipLaunchKernelGGL((csr_group_pre_kernel<UU, false, float>), grid, dim3(RB), lds, ctx->stream, A->rows, A->rowptr, A->col, A->val32, \
-                                   c ? c->pid : nullptr, c ? c->tptr : nullptr, c ? c->tab : nullptr, x, b, t_out, r_out, rc_out, G->gdesc, \
-                                   G->acode, G->wmask, capv, capi, bm, nullptr, 0x7fffffff, ((ctx->opt_nt_store > 0 && A->rows >= ctx->opt_nt_store) ? 1 : 0) | (ctx->opt_stage_unroll ? 2 : 0) | (ctx->opt_rowptr_scan ? 4 : 0), \
-                                   ordered ? G->gorder : nullptr, G->gorder_per_xcd, nullptr, nullptr, 0.0)
-#define GU_(UU) do { if (f32) GF_(UU); \
-                     else if (pairs) { if (hv) G2_(UU, true); else G2_(UU, false); } \
-                     else { if (hv) G_(UU, true, false); else if (val_nd) G_(UU, false, true); else G_(UU, false, false); } } while (0)
-  if (u == 4) GU_(4); else if (u == 7) GU_(7); else GU_(8);
-#undef GU_
-#undef GF_
-#undef G_
-#undef G2_
+  // the pair kernel's parameters are the leading ones of the one-block kernel's; `more`: what the latter takes behind them
+  auto launch = [&](auto kernel, auto vals, int threads, size_t lds, auto... more) {
+    hipLaunchKernelGGL(kernel, grid, dim3(threads), lds + l.pad_bytes, ctx->stream, A->rows, A->rowptr, A->col, vals, c ? c->pid : nullptr,
+                       c ? c->tptr : nullptr, c ? c->tab : nullptr, x, b, t_out, r_out, rc_out, G->gdesc, G->acode, G->wmask, l.capv, l.capi, bm, hv,
+                       hv ? split : 0x7fffffff, more...);
+  };
+  with_width<false>(gather_width(A), [&](auto U) {
+    constexpr int UU = decltype(U)::value;
+    if (pairs) {
+      with_bool(hv != nullptr, [&](auto H) { launch(csr_group2_pre_kernel<UU, decltype(H)::value>, (const double *)A->val, 2 * RB, 2 * regions + 2 * RB * 8); });
+      return;
+    }
+    auto form = [&](auto H, auto ND, auto vals) {      // (HALO, ND) ∈ {(true, false), (false, true), (false, false)} for double, neither for float
+      launch(csr_group_pre_kernel<UU, decltype(H)::value, pointee_t<decltype(vals)>, decltype(ND)::value>, vals, RB,
+             regions + (size_t)G->max_blocks * RB * 8, kernel_flags(ctx, nt_store_on(A), true), ordered ? G->gorder : nullptr, G->gorder_per_xcd,
+             val_nd, nd_code, omega);
+    };
+    const std::false_type no{};
+    if (f32) form(no, no, A->val32);
+    else if (hv) form(std::true_type{}, no, (const double *)A->val);
+    else with_bool(val_nd != nullptr, [&](auto ND) { form(no, ND, (const double *)A->val); });
+  });
   MGS_HIP(ctx, hipGetLastError());
   if (G->nstray) {
     hipLaunchKernelGGL(restrict_stray_kernel, dim3((G->nstray + RB - 1) / RB), dim3(RB), 0, ctx->stream, G->nstray, G->stray, T->cptr, T->members, r_out, rc_out);
@@ -1765,7 +1845,7 @@ int mgs_launch_group_pre(const mgs_csr *A, const mgs_groups *G, const mgs_xfer *
 
 int mgs_spmv_dots(const mgs_csr *A, const double *x, double *y, const double *w1, double *out_host2) {
   mgs_ctx *ctx = A->ctx;
-  const int nb = (A->rows + RB - 1) / RB;
+  const int nb = mgs_row_blocks(A);
   const bool fused = ctx->opt_fuse_dots && A->rows > 0 && ctx->opt_spmv_variant == 0 && !ctx->opt_nontemporal && use_rowcode(A, A->code) && A->lds_cap >= 8;
   if (!fused) {
     MGS_TRY(mgs_launch_csr_op(A, MGS_OP_SPMV, x, nullptr, nullptr, 0.0, y));
@@ -1779,24 +1859,6 @@ int mgs_spmv_dots(const mgs_csr *A, const double *x, double *y, const double *w1
 
 bool mgs_rowcode_usable(const mgs_csr *A, bool any) { return use_rowcode(A, A->code, any); }
 
-// workgroup → row-block map of a launch over the row blocks [blk_lo, blk_hi) (XCD-contiguous, strip-major for far bands)
-static dim3 plan_block_map(const mgs_csr *A, int blk_lo, int blk_hi, BlockMap &bm) {
-  mgs_ctx *ctx = A->ctx;
-  bm.base = blk_lo; bm.nblocks = blk_hi - blk_lo;
-  bm.remap = ctx->opt_xcd_remap && bm.nblocks >= 64;
-  bm.chunk = (bm.nblocks + 7) / 8;
-  bm.D = 0; bm.S = 0; bm.P = 0;
-  int per_xcd = bm.chunk;
-  if (bm.remap && ctx->opt_strip != 0) {
-    const int D = (A->far_band + RB - 1) / RB;
-    if (D >= 512 && bm.chunk >= 2 * D) {
-      per_xcd = strip_map(bm, D, ctx->opt_strip > 0 ? ctx->opt_strip : 64);
-    }
-  }
-  const dim3 grid(bm.remap ? per_xcd * 8 : bm.nblocks);
-  return grid;
-}
-
 // The coded kernel on the row blocks [blk_lo, blk_hi) of the view A (A->col = the coded index array, A->code its
 // code); hv/split: halo payload of a row shard (nullptr / INT_MAX: none).  Caller checks mgs_rowcode_usable(A).
 int mgs_launch_coded_range(const mgs_csr *A, int op, const double *x, const double *b, const double *dinv, double omega,
@@ -1805,20 +1867,19 @@ int mgs_launch_coded_range(const mgs_csr *A, int op, const double *x, const doub
   if (A->rows == 0 || blk_hi <= blk_lo) return MGS_OK;
   if (!use_rowcode(A, A->code, hv != nullptr)) return MGS_ERR_STATE;
   BlockMap bm;
-  const dim3 grid = plan_block_map(A, blk_lo, blk_hi, bm);
-  bm.gap_at = gap_at; bm.gap_len = gap_len;
+  const dim3 grid = plan_block_map(A, blk_lo, blk_hi, gap_at, gap_len, bm);
   return launch_coded(A, A->code, op, A->col, x, b, dinv, omega, xin, agg, out, grid, bm, hv, hv ? split : 0x7fffffff);
 }
 
 int mgs_launch_csr_op(const mgs_csr *A, int op, const double *x, const double *b, const double *dinv,
                       double omega, double *out) {
-  return mgs_launch_csr_op_range(A, op, x, b, dinv, omega, out, 0, (A->rows + RB - 1) / RB);
+  return mgs_launch_csr_op_range(A, op, x, b, dinv, omega, out, 0, mgs_row_blocks(A));
 }
 
 // fused passes (see csr_rowblock_fused_kernel); returns MGS_ERR_STATE when the level cannot use them
 int mgs_launch_fused(const mgs_csr *A, int which, const double *wd, const double *bvec, const double *xin, const int *agg,
                      const double *ec, double *out, double *out2) {
-  return mgs_launch_fused_range(A, which, wd, bvec, xin, agg, ec, out, out2, nullptr, 0, (A->rows + RB - 1) / RB);
+  return mgs_launch_fused_range(A, which, wd, bvec, xin, agg, ec, out, out2, nullptr, 0, mgs_row_blocks(A));
 }
 // row blocks [blk_lo, blk_hi); hv = values of the halo columns (nullptr for a square operator)
 int mgs_launch_fused_range(const mgs_csr *A, int which, const double *wd, const double *bvec, const double *xin, const int *agg,
@@ -1827,31 +1888,18 @@ int mgs_launch_fused_range(const mgs_csr *A, int which, const double *wd, const 
   if (A->rows == 0 || blk_hi <= blk_lo) return MGS_OK;
   if (A->lds_cap <= 0 || (which == FUSE_PRE && A->rows != A->cols && !hv)) return MGS_ERR_STATE;   // (row shards: the pre pass reads its halo columns from the payload; the post passes gather e_c, halo room included)
   BlockMap bm;
-  bm.gap_at = gap_at; bm.gap_len = gap_len;
-  bm.base = blk_lo; bm.nblocks = blk_hi - blk_lo;
-  bm.remap = ctx->opt_xcd_remap && bm.nblocks >= 64;
-  bm.chunk = (bm.nblocks + 7) / 8;
-  bm.D = 0; bm.S = 0; bm.P = 0;
-  int per_xcd = bm.chunk;
-  if (bm.remap && ctx->opt_strip != 0) {
-    const int D = (A->far_band + RB - 1) / RB;
-    if (D >= 512 && bm.chunk >= 2 * D) {
-      per_xcd = strip_map(bm, D, ctx->opt_strip > 0 ? ctx->opt_strip : 64);
-    }
-  }
-  dim3 grid(bm.remap ? per_xcd * 8 : bm.nblocks);
+  const dim3 grid = plan_block_map(A, blk_lo, blk_hi, gap_at, gap_len, bm);
+  // FP32 level: post pass on the float copy of A·P's values (never the gather kernels, which read FP64 values)
+  if (A->val32 && (which != FUSE_POST_MAPPED || hv)) return mgs_fail(ctx, MGS_ERR_INVALID, "FP32 operand values: fused pass %d has no float form", which);
+  if (A->val32 || (which == FUSE_POST_MAPPED && use_rowcode(A, A->code)))      // A is the view whose col/code are the aggregate-mapped ones
+    return launch_coded(A, A->code, FUSE_POST_MAPPED, A->col, ec, bvec, wd, 0.0, xin, agg, out, grid, bm);
   const int cap = A->lds_cap;
   const size_t lds = (size_t)(cap + 2) * 12 + 16;
-  if (A->val32) {      // FP32 level: post pass on the float copy of A·P's values (never the gather kernels, which read FP64 values)
-    if (which != FUSE_POST_MAPPED || hv) return mgs_fail(ctx, MGS_ERR_INVALID, "FP32 operand values: fused pass %d has no float form", which);
-    return launch_coded_f32(A, A->code, FUSE_POST_MAPPED, A->col, ec, bvec, wd, xin, agg, out, grid, bm);
-  }
-  if (which == FUSE_POST_MAPPED && use_rowcode(A, A->code))      // A is the view whose col/code are the aggregate-mapped ones
-    return launch_coded(A, A->code, FUSE_POST_MAPPED, A->col, ec, bvec, wd, 0.0, xin, agg, out, grid, bm);
-  if (ctx->report && which != FUSE_PRE) *ctx->report = {0, 8, 0, cap, cap + 2};      // the gather kernel: steps of 8, index slice beside the values
-  if (which == FUSE_POST_MAPPED) hipLaunchKernelGGL((csr_rowblock_fused_kernel<FUSE_POST_MAPPED>), grid, dim3(RB), lds, ctx->stream, A->rows, A->rowptr, A->col, A->val, wd, bvec, xin, agg, ec, out, out2, cap, bm, hv, A->ctx->opt_blkptr ? A->blkptr : nullptr);
-  else if (which == FUSE_PRE) hipLaunchKernelGGL((csr_rowblock_fused_kernel<FUSE_PRE>), grid, dim3(RB), lds, ctx->stream, A->rows, A->rowptr, A->col, A->val, wd, bvec, xin, agg, ec, out, out2, cap, bm, hv, A->ctx->opt_blkptr ? A->blkptr : nullptr);
-  else hipLaunchKernelGGL((csr_rowblock_fused_kernel<FUSE_POST>), grid, dim3(RB), lds, ctx->stream, A->rows, A->rowptr, A->col, A->val, wd, bvec, xin, agg, ec, out, out2, cap, bm, hv, A->ctx->opt_blkptr ? A->blkptr : nullptr);
+  with_fused_pass(which, [&](auto W) {
+    hipLaunchKernelGGL((csr_rowblock_fused_kernel<decltype(W)::value>), grid, dim3(RB), lds, ctx->stream, A->rows, A->rowptr, A->col, A->val, wd, bvec,
+                       xin, agg, ec, out, out2, cap, bm, hv, blkptr_opt(A));
+  });
+  if (which != FUSE_PRE) report_launch(ctx, 0, 8, 0, cap, cap + 2);      // the gather kernel: steps of 8, index slice beside the values
   MGS_HIP(ctx, hipGetLastError());
   return MGS_OK;
 }
@@ -1866,88 +1914,28 @@ int mgs_launch_csr_op_range(const mgs_csr *A, int op, const double *x, const dou
     return mgs_launch_csr_op_range(A, op, x, b, dinv, omega, out, gap_at + gap_len, blk_hi + gap_len, 0x7fffffff, 0);
   }
   BlockMap bm;
-  bm.gap_at = gap_at; bm.gap_len = gap_len;
-  bm.base = blk_lo;
-  bm.nblocks = blk_hi - blk_lo;
-  bm.remap = ctx->opt_xcd_remap && bm.nblocks >= 64;
-  bm.chunk = (bm.nblocks + 7) / 8;
-  bm.D = 0; bm.S = 0; bm.P = 0;
-  int per_xcd = bm.chunk;
-  // strip-major sweep when three x planes (3·far·8 B) overflow an XCD's L2 share and the XCD's
-  // range holds at least two planes
-  if (bm.remap && ctx->opt_strip != 0) {
-    const int D = (A->far_band + RB - 1) / RB;
-    if (D >= 512 && bm.chunk >= 2 * D) {
-      per_xcd = strip_map(bm, D, ctx->opt_strip > 0 ? ctx->opt_strip : 64);
-    }
-  }
-  if (A->val32) {      // FP32 level: pre pass on the float copy of Â's values, whatever the SpMV variant options say
-    const dim3 grid32(bm.remap ? per_xcd * 8 : bm.nblocks);
-    return launch_coded_f32(A, A->code, op, A->col, x, b, dinv, nullptr, nullptr, out, grid32, bm);
-  }
-  int cap = ctx->opt_spmv_variant == 1 ? -1 : A->lds_cap;
-  if (ctx->opt_spmv_variant == 6 && A->max_block_nnz <= 2048 && A->max_block_nnz == A->lds_cap) {
-    // pipelined variant: G row blocks per workgroup; block map over super blocks
-    constexpr int G = 4;
-    const int nrb = bm.nblocks;
-    BlockMap sm = bm;
-    sm.nblocks = (nrb + G - 1) / G;
-    sm.remap = ctx->opt_xcd_remap && sm.nblocks >= 64;
-    sm.chunk = (sm.nblocks + 7) / 8;
-    sm.D = 0; sm.S = 0; sm.P = 0;
-    int per = sm.chunk;
-    if (sm.remap && ctx->opt_strip != 0) {
-      const int D = ((A->far_band + RB - 1) / RB + G - 1) / G;
-      if (D >= 64 && sm.chunk >= 2 * D) {
-        per = strip_map(sm, D, ctx->opt_strip > 0 ? std::max(1, ctx->opt_strip / G) : 16);
-      }
-    }
-    // base stays in row-block units inside the kernel: bm.base + first + j
-    dim3 g(sm.remap ? per * 8 : sm.nblocks);
-    const size_t lds = (size_t)(cap + 2) * 12 + 16;
-    hipStream_t st = ctx->stream;
-    const bool ntp = ctx->opt_nontemporal != 0;
-#define P_(O, NTV) hipLaunchKernelGGL((csr_rowblock_pipe_kernel<O, NTV, 4, G>), g, dim3(RB), lds, st, A->rows, A->rowptr, A->col, A->val, x, b, dinv, omega, out, cap, sm, nrb)
-    if (op == MGS_OP_SPMV) { if (ntp) P_(MGS_OP_SPMV, true); else P_(MGS_OP_SPMV, false); }
-    else if (op == MGS_OP_RESIDUAL) { if (ntp) P_(MGS_OP_RESIDUAL, true); else P_(MGS_OP_RESIDUAL, false); }
-    else { if (ntp) P_(MGS_OP_JACOBI, true); else P_(MGS_OP_JACOBI, false); }
-#undef P_
-    MGS_HIP(ctx, hipGetLastError());
-    return MGS_OK;
-  }
-  if (ctx->opt_spmv_variant == 7 && A->max_wave_nnz <= 4096) {
-    const int capw = A->max_wave_nnz;
-    dim3 g((bm.remap ? per_xcd * 8 : bm.nblocks) * 4);
-    const size_t ldsw = (size_t)(capw + 2) * 12 + 16;
-    hipStream_t st = ctx->stream;
-#define W_(O) hipLaunchKernelGGL((csr_wave_slice_kernel<O>), g, dim3(64), ldsw, st, A->rows, A->rowptr, A->col, A->val, x, b, dinv, omega, out, capw, bm)
-    if (op == MGS_OP_SPMV) W_(MGS_OP_SPMV); else if (op == MGS_OP_RESIDUAL) W_(MGS_OP_RESIDUAL); else W_(MGS_OP_JACOBI);
-#undef W_
-    MGS_HIP(ctx, hipGetLastError());
-    return MGS_OK;
-  }
-  dim3 grid(bm.remap ? per_xcd * 8 : bm.nblocks);
+  const dim3 grid = plan_block_map(A, blk_lo, blk_hi, gap_at, gap_len, bm);
+  // FP32 level: pre pass on the float copy of Â's values, whatever the SpMV variant options say (the float forms take no ω)
+  if (A->val32) return launch_coded(A, A->code, op, A->col, x, b, dinv, 0.0, nullptr, nullptr, out, grid, bm);
+  const int cap = ctx->opt_spmv_variant == 1 ? -1 : A->lds_cap;
+  if (ctx->opt_spmv_variant == 6 && A->max_block_nnz <= 2048 && A->max_block_nnz == A->lds_cap) return launch_pipe(A, op, x, b, dinv, omega, out, cap, bm);
+  if (ctx->opt_spmv_variant == 7 && A->max_wave_nnz <= 4096) return launch_wave(A, op, x, b, dinv, omega, out, grid, bm);
   if (ctx->opt_spmv_variant == 0 && !ctx->opt_nontemporal && use_rowcode(A, A->code))
     return launch_coded(A, A->code, op, A->col, x, b, dinv, omega, nullptr, nullptr, out, grid, bm);
-  size_t lds = sizeof(double) * (size_t)(cap > 0 ? cap : 1);
+  const size_t lds = sizeof(double) * (size_t)(cap > 0 ? cap : 1);
   // lanes per row of the long-row path: next power of two ≥ mean row length, in [4,64]
-  double mean = A->rows ? (double)A->nnz / A->rows : 1.0;
+  const double mean = mean_row_len(A);
   int lanes = 4;
   while (lanes < 64 && lanes < mean) lanes <<= 1;
-  const bool nt = ctx->opt_nontemporal > 0;
   // variants: 0 auto, 1 forced sub-wavefront rows, 2/3/4 = products-in-LDS with 1/2/4 entries per lane, 5 = slice-in-LDS
   int chunk_elems = 0;
   switch (ctx->opt_spmv_variant) { case 2: chunk_elems = 1; break; case 3: chunk_elems = 2; break; case 4: chunk_elems = 4; break; default: chunk_elems = 0; }
-#define OP_(O)                                                                                                   \
-  (nt ? launch_chunk<O, true>(A, chunk_elems, lanes, grid, lds, x, b, dinv, omega, out, cap, bm)                 \
-      : launch_chunk<O, false>(A, chunk_elems, lanes, grid, lds, x, b, dinv, omega, out, cap, bm))
-  switch (op) {
-    case MGS_OP_SPMV: OP_(MGS_OP_SPMV); break;
-    case MGS_OP_RESIDUAL: OP_(MGS_OP_RESIDUAL); break;
-    case MGS_OP_JACOBI: OP_(MGS_OP_JACOBI); break;
-    default: return mgs_fail(ctx, MGS_ERR_INVALID, "unknown csr op %d", op);
-  }
-#undef OP_
+  const bool known = with_csr_op(op, [&](auto O) {
+    with_bool(ctx->opt_nontemporal > 0, [&](auto NT) {
+      launch_chunk<decltype(O)::value, decltype(NT)::value>(A, chunk_elems, lanes, grid, lds, x, b, dinv, omega, out, cap, bm);
+    });
+  });
+  if (!known) return mgs_fail(ctx, MGS_ERR_INVALID, "unknown csr op %d", op);
   MGS_HIP(ctx, hipGetLastError());
   return MGS_OK;
 }

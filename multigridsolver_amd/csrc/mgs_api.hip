@@ -429,7 +429,7 @@ int mgs_csr_optimize(mgs_csr *A) {
   return mgs_build_rowcode(A->ctx, A->rows, A->rowptr, A->col, nullptr, 0x7fffffff, &A->code, A->ctx->opt_valcode ? A->val : nullptr);
 }
 int mgs_csr_rowcode_info(const mgs_csr *A, int64_t out[4]) {
-  out[0] = A->code ? A->code->coded_blocks : 0; out[1] = A->code ? A->code->nblocks : (A->rows + 255) / 256;
+  out[0] = A->code ? A->code->coded_blocks : 0; out[1] = A->code ? A->code->nblocks : mgs_row_blocks(A);
   out[2] = A->code ? A->code->tab_total : 0; out[3] = A->code ? A->code->tab_cap : 0;
   return MGS_OK;
 }
@@ -1188,7 +1188,7 @@ int mgs_hier_fused_info(const mgs_hier *h, int level, int64_t out[6]) {
   MGS_CHECK(h->ctx, level >= 0 && level < (int)h->lev.size(), MGS_ERR_INVALID, "mgs_hier_fused_info: level %d out of range", level);
   const mgs_level &L = h->lev[level];
   auto coded = [](const mgs_rowcode *c) -> int64_t { return c ? c->coded_blocks : 0; };
-  out[0] = (L.A->rows + 255) / 256; out[1] = L.val_wd != nullptr; out[2] = L.col_agg != nullptr || L.AP != nullptr;
+  out[0] = mgs_row_blocks(L.A); out[1] = L.val_wd != nullptr; out[2] = L.col_agg != nullptr || L.AP != nullptr;
   out[3] = coded(L.A->code); out[4] = coded(L.code_pre); out[5] = coded(L.AP ? L.code_ap : L.code_agg);
   return MGS_OK;
 }
@@ -1196,7 +1196,7 @@ int mgs_hier_fused_info(const mgs_hier *h, int level, int64_t out[6]) {
 int mgs_hier_group_info(const mgs_hier *h, int level, int64_t out[4]) {
   MGS_CHECK(h->ctx, level >= 0 && level < (int)h->lev.size(), MGS_ERR_INVALID, "mgs_hier_group_info: level %d out of range", level);
   const mgs_groups *G = h->lev[level].grp;
-  out[0] = G ? G->ngroups : 0; out[1] = G ? G->nblocks - G->ngroups : 0;   /* blocks merged into another block's group */ out[2] = G ? G->nstray : 0; out[3] = (h->lev[level].A->rows + 255) / 256;
+  out[0] = G ? G->ngroups : 0; out[1] = G ? G->nblocks - G->ngroups : 0;   /* blocks merged into another block's group */ out[2] = G ? G->nstray : 0; out[3] = mgs_row_blocks(h->lev[level].A);
   return MGS_OK;
 }
 int mgs_hier_pre_pass(mgs_hier *h, int level, const mgs_vec *b, mgs_vec *t, mgs_vec *r, mgs_vec *rc, int *nodiag) {
@@ -1232,7 +1232,7 @@ int mgs_hier_post_pass(mgs_hier *h, int level, const mgs_vec *bvec, const mgs_ve
             "mgs_hier_post_pass: level %d does not run the fused passes (option fuse, V(1,1), multiplicative)", level);
   MGS_CHECK(ctx, bvec->n >= L.n && (!xin || xin->n >= L.n) && x->n >= L.n && ec->n >= L.T->n_coarse, MGS_ERR_INVALID,
             "mgs_hier_post_pass: vectors shorter than the level (%d rows, %d aggregates)", L.n, L.T->n_coarse);
-  const int nb = (L.A->rows + 255) / 256;
+  const int nb = mgs_row_blocks(L.A);
   int b0 = 0, b1 = nb, ga = 0x7fffffff, gl = 0;
   if (range) {
     b0 = range[0]; b1 = range[1]; ga = range[2]; gl = range[3];
@@ -1325,7 +1325,7 @@ static int sharded_op(mgs_hier *h, int l, const mgs_csr *A, int op, double *x, c
   }
   if (!h->halo && !h->halo_begin) return mgs_launch_csr_op(A, op, x, b, dinv, omega, out);
   if (h->halo_begin && A->halo_split_ok && A->rows >= h->ctx->opt_split_min_rows) {
-    const int nb = (A->rows + 255) / 256, lo = A->halo_lo_blocks, hi = nb - A->halo_hi_blocks;
+    const int nb = mgs_row_blocks(A), lo = A->halo_lo_blocks, hi = nb - A->halo_hi_blocks;
     int rc = h->halo_begin(h->halo_user, l, x);
     if (rc) return mgs_fail(h->ctx, MGS_ERR_STATE, "halo exchange (begin) failed at level %d (%d)", l, rc);
     MGS_TRY(mgs_launch_csr_op_range(A, op, x, b, dinv, omega, out, lo, hi));
@@ -1476,7 +1476,7 @@ static int cycle_level(mgs_hier *h, int l, const double *b, double *x, bool zero
                         L.T->aggregation && L.A->lds_cap > 0 && transport_ok;
   if (can_fuse) {
     const double *hv = halo ? L.hbuf->d : nullptr;
-    const int nb = (L.A->rows + 255) / 256;
+    const int nb = mgs_row_blocks(L.A);
     // interior row blocks run while the halo values are in flight
     const bool split = halo && L.A->halo_split_ok && L.A->rows >= h->ctx->opt_split_min_rows;
     const int lo = split ? L.A->halo_lo_blocks : 0, hi = split ? nb - L.A->halo_hi_blocks : nb;

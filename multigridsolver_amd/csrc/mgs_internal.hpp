@@ -140,6 +140,8 @@ struct mgs_csr {
   int coo_max_row = 0;      // most triples one row received
   int nullspace = MGS_NULLSPACE_NONE;   // mgs_csr_set_nullspace: what the caller declared (hierarchies and Krylov solvers act on it)
 };
+constexpr int MGS_RB = 256;   // rows per row block of the row-block kernels (kernels_spmv.hip) == their threads per workgroup
+static inline int mgs_row_blocks(const mgs_csr *A) { return (A->rows + MGS_RB - 1) / MGS_RB; }
 
 struct mgs_vec {
   mgs_ctx *ctx = nullptr;

@@ -1541,3 +1541,31 @@ def test_kcycle_split_launch_same_bits(ctx, mg):
         assert v0 is not None
     finally:
         ctx.set_option("graph", 1); ctx.set_option("graph_split_rows", 1 << 20); ctx.set_option("kcycle_energy", 0)
+
+
+def test_launch_options_same_bits(ctx, mg):
+    """Launch options that change no operand, no product and no order of a sum: row-block bounds from rowptr instead of blkptr, non-temporal
+    loads, extra LDS per workgroup, streaming stores from the first row on, the looped staging, the plain workgroup map.  Each must give the
+    bits of the defaults — for SpMV, residual, Jacobi and one zero-guess V(1,1) cycle.  poisson3d(26): 17 576 rows = 69 row blocks, the smallest
+    cube with the 64 blocks that turn the XCD-contiguous map on; its last block is partial (168 rows)."""
+    N = 26; n = N ** 3
+    A = ctx.poisson3d(N)
+    assert (n + 255) // 256 == 69 and n % 256 == 168
+    x = ctx.vec(n).rand(seed=11); b = ctx.vec(n).rand(seed=12)
+    dinv = A.diag_inv()
+    h = mg.Hierarchy(A, 0.6, 1, 1).coarsen(10.0, 2, 8.0, 60, 10).finalize()
+
+    def results():
+        return (A.spmv(x).numpy(), A.residual(x, b).numpy(), A.jacobi(dinv, 0.6, b, x).numpy(), h.vcycle(b).numpy())
+
+    ref = results()
+    assert all(np.all(np.isfinite(r)) and np.any(r != 0.0) for r in ref)
+    defaults = {"blkptr": 1, "nontemporal": 0, "lds_pad": 0, "nt_store": 1000000, "stage_unroll": 1, "xcd_remap": 1}
+    for opt, val in (("blkptr", 0), ("nontemporal", 1), ("lds_pad", 8192), ("nt_store", 1), ("stage_unroll", 0), ("xcd_remap", 0)):
+        ctx.set_option(opt, val)
+        try:
+            got = results()
+        finally:
+            ctx.set_option(opt, defaults[opt])
+        for what, r, g in zip(("spmv", "residual", "jacobi", "vcycle"), ref, got):
+            assert np.array_equal(r, g), (opt, val, what)
