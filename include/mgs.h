@@ -404,6 +404,58 @@ int mgs_fgcr(const mgs_csr *A, mgs_vec *x, const mgs_vec *b, mgs_hier *h, int re
 int mgs_pcg(const mgs_csr *A, mgs_vec *x, const mgs_vec *b, mgs_hier *h, int flexible,
             int *max_iter, double *tol, int *status);
 
+/* ------------------------------------- projected initial guesses for successive right-hand sides */
+/* Nearest reference line: none: the reference solves one right-hand side, bicg.cpp:159-166.  A caller who solves with the same operator again and
+ * again (time stepping, Picard / Newton, the pressure Poisson equation) gets a better start than its last solution by projecting the new
+ * right-hand side onto the span of the last few solutions (Fischer 1998; PETSc: KSPGuessFischer).  The guess holds size <= capacity pairs
+ * (x̃_k, ỹ_k = A·x̃_k), both n doubles, normalised so that <x̃_j, ỹ_k> = δ_jk (MGS_GUESS_ENERGY: A symmetric positive definite, x0 minimises
+ * ‖x − x0‖_A over the span) or <ỹ_j, ỹ_k> = δ_jk (MGS_GUESS_RESIDUAL: any nonsingular A, x0 minimises ‖b − A·x0‖₂ over the span); q_k names the
+ * vector that is dotted, x̃_k resp. ỹ_k.  Both kinds store pairs: one code path, and no operation but the update's own needs an SpMV.
+ * A is borrowed and must outlive the guess.  The 2·capacity vectors, the partial sums and the device scalars are allocated at create (inside
+ * the arena when one exists); the update's two scratch vectors come from the context's work-vector pool (mgs_ctx_trim releases them).
+ *   apply:  α_k = <q_k, b> in one pass over b and the q_k, then x0 = Σ_k α_k·x̃_k; α stays in device memory between the two launches.  Without
+ *     rel_resid the call makes no host round trip and is enqueued on the context's stream.  With rel_resid the second pass also forms
+ *     r0 = b − Σ α_k·ỹ_k (not stored), *rel_resid = ‖r0‖/‖b‖ and the call synchronises.  An empty basis gives x0 = 0 and *rel_resid = 1.
+ *   update(x): x is a solution the caller just computed (its right-hand side is not needed).  w = A·x (mgs_spmv); c¹_k = <q_k, w> and
+ *     ν0² = <x, w> (ENERGY) or <w, w> (RESIDUAL) in one pass; the pair pass x' = x − Σ c¹_k·x̃_k, w' = w − Σ c¹_k·ỹ_k (into the free slot), which also accumulates
+ *     c²_k = <q_k, w'> and ν1²; the pair pass again with c², giving x'', w'' and ν2² (classical Gram-Schmidt, twice); one workgroup decides on
+ *     the device; a store pass predicated on that decision writes x̃ = s·x'', ỹ = s·w'', s = 1/√ν2², into slot `size` — the only copy out of
+ *     scratch.  The host reads one flag at the end.  Accepted (DGKS, η = 1/√2): ν2² finite and positive, ν2² >= ν1²/2, ν0² > 0 and ν2 > 32·2⁻⁵²·ν0 (what the first pass
+ *     leaves of a candidate inside the span is rounding noise, which the second pass barely shortens: the floor, PETSc's drop tolerance, refuses it).  A candidate
+ *     whose norm falls further in the second pass lies numerically inside the span; an ENERGY candidate with ν0² <= 0 means A is not positive
+ *     along x: neither is added, *added = 0 (added may be NULL) and the "refused" counter goes up.  size == capacity: the basis restarts from
+ *     the candidate alone (Fischer's restart: nothing is orthogonalised, ν1² = ν2² = ν0², slot 0 takes the normalised (x, w), size = 1, the
+ *     restart counter goes up) — measured better than dropping the oldest pair, which carries the bulk of the solution.
+ *   rebase: A's values changed (mgs_csr_update_values*): reset followed by update(x̃_k) from the oldest to the newest, in place; every ỹ is
+ *     recomputed with the current values.   reset: size = 0; the counters stay.
+ *   A declared MGS_NULLSPACE_CONSTANT: update works on a zero-mean copy of x, so every x̃_k and with them x0 have zero mean; a constant
+ *     candidate whose mean is exact (e.g. all ones) has ν0² = 0 and is refused.
+ *   Arithmetic: every elementwise result is a sum of products in ascending k starting from the first product (x' = x − (c_0·x̃_0 + c_1·x̃_1 + …)),
+ *     one rounding per product and per sum, so a host restatement given the coefficient bits reproduces x0, x', w' and the stored pairs bit
+ *     for bit; partial sums have a fixed layout and a fixed-order fold, no atomics: two identical calls give identical bits.  16-byte accesses
+ *     where the caller's vectors are 16-byte aligned, 8-byte ones otherwise — the same bits.
+ *   info: out = size, capacity, kind, restarts, candidates refused, device bytes held.
+ *   coef (tests and diagnostics; synchronises): after an apply α_0..α_{K−1}; after an update c¹_0..c¹_{K−1}, c²_0..c²_{K−1}, ν0², ν1², ν2², s,
+ *     the accept flag (K = the pairs the call ran against); entries beyond that are 0.
+ *   gram (tests and diagnostics; synchronises): host[j·size + k] = <q_j, ỹ_k>.
+ *   pair (tests and diagnostics; enqueued): copies of x̃_k and ỹ_k, 0 <= k < size.  k = size < capacity reads the free slot, which the first
+ *     Gram-Schmidt pass uses as its output: after a refused update that orthogonalised it holds that candidate's x' and w'.
+ * MGS_ERR_INVALID, with a message: a NULL argument (rel_resid, added excepted); an unknown kind; a capacity outside 1..16; A not square or with
+ * halo columns (cols > rows: a row shard); vectors shorter than A's rows; x0 aliasing b. */
+typedef struct mgs_guess mgs_guess;
+#define MGS_GUESS_ENERGY 0
+#define MGS_GUESS_RESIDUAL 1
+int mgs_guess_create(const mgs_csr *A, int kind, int capacity, mgs_guess **out);
+int mgs_guess_destroy(mgs_guess *g);
+int mgs_guess_apply(mgs_guess *g, const mgs_vec *b, mgs_vec *x0, double *rel_resid);
+int mgs_guess_update(mgs_guess *g, const mgs_vec *x, int *added);
+int mgs_guess_rebase(mgs_guess *g);
+int mgs_guess_reset(mgs_guess *g);
+int mgs_guess_info(const mgs_guess *g, int64_t out[6]);
+int mgs_guess_coef(const mgs_guess *g, double *host, int n);
+int mgs_guess_gram(mgs_guess *g, double *host);
+int mgs_guess_pair(const mgs_guess *g, int k, mgs_vec *x, mgs_vec *y);
+
 /* ------------------------------------------------------------- multi-GPU row shards   */
 /* Halo plan of a row-range shard whose CSR uses LOCAL column numbering: columns
  * [0,n_loc) are owned rows, columns n_loc+k are halo slot k.  send_idx lists the owned

@@ -130,6 +130,16 @@ PROTOTYPES = {
     "mgs_bicgstab": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_int_p, c_dbl_p, c_int_p]),
     "mgs_fgcr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, c_int_p, c_dbl_p, c_int_p]),
     "mgs_pcg": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, c_int_p, c_dbl_p, c_int_p]),
+    "mgs_guess_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "mgs_guess_destroy": (C.c_int, [C.c_void_p]),
+    "mgs_guess_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_dbl_p]),
+    "mgs_guess_update": (C.c_int, [C.c_void_p, C.c_void_p, c_int_p]),
+    "mgs_guess_rebase": (C.c_int, [C.c_void_p]),
+    "mgs_guess_reset": (C.c_int, [C.c_void_p]),
+    "mgs_guess_info": (C.c_int, [C.c_void_p, c_i64_p]),
+    "mgs_guess_coef": (C.c_int, [C.c_void_p, c_dbl_p, C.c_int]),
+    "mgs_guess_gram": (C.c_int, [C.c_void_p, c_dbl_p]),
+    "mgs_guess_pair": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "mgs_halo_pack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "mgs_hier_set_halo_exchange": (C.c_int, [C.c_void_p, HALO_FN, C.c_void_p]),
     "mgs_aggregate_shard": (C.c_int, [C.c_void_p, C.c_double, C.c_int, C.c_double, C.POINTER(C.c_void_p)]),

@@ -582,6 +582,66 @@ class Hierarchy:
         check(lib().mgs_hier_set_halo_exchange(self.h, self._cb, None), self.ctx.h)
 
 
+_GUESS_KIND = {"energy": 0, "residual": 1}      # MGS_GUESS_ENERGY / MGS_GUESS_RESIDUAL
+
+
+class Guess:
+    """Projected initial guesses for successive right-hand sides of one operator (mgs_guess, include/mgs.h): the span of the last
+    `capacity` solutions, kept as A-orthonormal ("energy", SPD A) or AᵀA-orthonormal ("residual", any nonsingular A) pairs (x̃, A·x̃).
+    A must outlive the guess (it is kept referenced here)."""
+
+    def __init__(self, A, kind="energy", capacity=8):
+        if kind not in _GUESS_KIND:
+            raise ValueError(f"Guess: kind {kind!r}, expected one of {list(_GUESS_KIND)}")
+        self.ctx, self.A, self.kind = A.ctx, A, kind
+        h = C.c_void_p(); check(lib().mgs_guess_create(A.h, _GUESS_KIND[kind], int(capacity), C.byref(h)), A.ctx.h)
+        self.h = h
+
+    def __del__(self):
+        try:
+            if self.h and self.ctx.h:
+                lib().mgs_guess_destroy(self.h)
+        except Exception:  # noqa: BLE001
+            pass
+
+    def apply(self, b, x0=None, rel_resid=False):
+        """x0 = the projection of b's solution onto the stored span, enqueued; rel_resid=True → (x0, ‖b − A·x0‖/‖b‖) and synchronises"""
+        x0 = x0 if x0 is not None else Vec(self.ctx, len(b))
+        r = C.c_double()
+        check(lib().mgs_guess_apply(self.h, b.h, x0.h, C.byref(r) if rel_resid else None), self.ctx.h)
+        return (x0, r.value) if rel_resid else x0
+
+    def update(self, x):
+        """offer the solution x to the basis → True if it was added (False: numerically inside the span, or A not positive along it)"""
+        a = C.c_int(); check(lib().mgs_guess_update(self.h, x.h, C.byref(a)), self.ctx.h); return bool(a.value)
+
+    def rebase(self):
+        """A's values changed (Csr.update_values): recompute every A·x̃ and re-orthonormalise, in place"""
+        check(lib().mgs_guess_rebase(self.h), self.ctx.h); return self
+
+    def reset(self):
+        check(lib().mgs_guess_reset(self.h), self.ctx.h); return self
+
+    def info(self):
+        out = (C.c_int64 * 6)(); check(lib().mgs_guess_info(self.h, out), self.ctx.h)
+        return dict(zip(["size", "capacity", "kind", "restarts", "refused", "bytes"], [int(v) for v in out]))
+
+    def coef(self, n=36):
+        """α of the last apply, or c¹, c², ν0², ν1², ν2², s, flag of the last update (see mgs_guess_coef); zero padded to n"""
+        out = np.zeros(max(int(n), 1)); check(lib().mgs_guess_coef(self.h, _dp(out), int(n)), self.ctx.h); return out[: int(n)]
+
+    def pair(self, k):
+        """copies (x̃_k, A·x̃_k) of stored pair k; k = size reads the free slot (x', w' of a refused update, see mgs_guess_pair)"""
+        n = self.A.shape[0]
+        x, y = Vec(self.ctx, n), Vec(self.ctx, n)
+        check(lib().mgs_guess_pair(self.h, int(k), x.h, y.h), self.ctx.h); return x, y
+
+    def gram(self):
+        """size × size matrix <q_j, A·x̃_k>: the identity to rounding"""
+        k = self.info()["size"]
+        out = np.zeros(max(k * k, 1)); check(lib().mgs_guess_gram(self.h, _dp(out)), self.ctx.h); return out[: k * k].reshape(k, k)
+
+
 def bicgstab(A, x, b, hier=None, max_iter=10000, tol=1e-6):
     """BiCGSTABiml (reference bicg.cpp:74-136) → (status, iterations, achieved_tol)"""
     mi, t, st = C.c_int(max_iter), C.c_double(tol), C.c_int(-1)

@@ -334,6 +334,35 @@ inline int CGiml(const SMatrix &, Vector &x, const Vector &b, const MultiGridPre
   return CGiml(M.matrix(), x, b, M, max_iter, tol);
 }
 
+// ---------------------------------------------------------------- projected initial guesses (mgs.h: mgs_guess)
+// No reference counterpart: the reference solves one right-hand side (bicg.cpp:159-166).  For a caller who solves with the same operator
+// again and again:   SolutionGuess guess(A, MGS_GUESS_ENERGY);   per step:  guess.apply(b, x);  CGiml(A, x, b, M, it, tol);  guess.update(x);
+// The guess keeps the DeviceMatrix (and with it the device matrix) alive.  MGS_GUESS_RESIDUAL serves any nonsingular A (BiCGSTABiml).
+class SolutionGuess {
+  DeviceMatrix A_;
+  std::shared_ptr<mgs_guess> g_;
+  int64_t info(int i) const { int64_t o[6]; check(mgs_guess_info(g_.get(), o), context()); return o[i]; }
+ public:
+  SolutionGuess(const DeviceMatrix &A, int kind = MGS_GUESS_ENERGY, int capacity = 8) : A_(A) {
+    mgs_guess *p = nullptr;
+    check(mgs_guess_create(A.handle(), kind, capacity, &p), context());
+    g_ = std::shared_ptr<mgs_guess>(p, [](mgs_guess *q) { mgs_guess_destroy(q); });
+  }
+  // x0 = projection onto the stored span, enqueued; no host round trip
+  void applyAsync(const Vector &b, Vector &x0) { check(mgs_guess_apply(g_.get(), b.handle(), x0.out(), nullptr), context()); }
+  // ... and ‖b − A·x0‖/‖b‖ (1 with an empty basis); synchronises
+  double apply(const Vector &b, Vector &x0) { double r = 0.0; check(mgs_guess_apply(g_.get(), b.handle(), x0.out(), &r), context()); return r; }
+  // offer a solution just computed; false: it lies numerically inside the span (or A is not positive along it) and was not added
+  bool update(const Vector &x) { int added = 0; check(mgs_guess_update(g_.get(), x.handle(), &added), context()); return added != 0; }
+  void rebase() { check(mgs_guess_rebase(g_.get()), context()); }      // after DeviceMatrix::update_values
+  void reset() { check(mgs_guess_reset(g_.get()), context()); }
+  int size() const { return (int)info(0); }
+  int capacity() const { return (int)info(1); }
+  int64_t restarts() const { return info(3); }
+  int64_t refused() const { return info(4); }
+  mgs_guess *handle() const { return g_.get(); }
+};
+
 // ---------------------------------------------------------------- TicToc.cpp:18-53
 class TicToc {
   std::chrono::time_point<std::chrono::system_clock> start;

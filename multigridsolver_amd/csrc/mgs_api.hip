@@ -1829,6 +1829,10 @@ static void ws_put(mgs_ctx *ctx, mgs_vec *v) {
   if (ctx->ws_free.size() >= 24) { mgs_vec *old = ctx->ws_free.front(); ctx->ws_free.erase(ctx->ws_free.begin()); mgs_vec_destroy(old); }
   ctx->ws_free.push_back(v);
 }
+extern "C++" {   // internal (mgs_internal.hpp): the pool for the other translation units
+int mgs_ws_get(mgs_ctx *ctx, int64_t n, int64_t owned, mgs_vec **out) { return ws_get(ctx, n, owned, out); }
+void mgs_ws_put(mgs_ctx *ctx, mgs_vec *v) { ws_put(ctx, v); }
+}
 
 // A declared MGS_NULLSPACE_CONSTANT: the solvers below solve A·x = Πb, Π = I − 1·1ᵀ/n (k_project_const), and return the x of zero mean.
 // *ns_out = whether to project.  Refused: a declared row shard; a hierarchy whose fine operator carries another kind than A.

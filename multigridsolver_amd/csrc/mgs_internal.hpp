@@ -450,6 +450,10 @@ int k_csr_update_values_coo(mgs_csr *A, const void *val_dev);
 
 // helpers (mgs_api.hip)
 int mgs_csr_alloc(mgs_ctx *ctx, int rows, int cols, int64_t nnz, mgs_csr **out);
+// the context's pool of work vectors (the Krylov solvers' ws_get / ws_put) for the other translation units: a vector of n entries, written before
+// it is read by whoever takes it; mgs_ws_put(NULL) does nothing
+int mgs_ws_get(mgs_ctx *ctx, int64_t n, int64_t owned, mgs_vec **out);
+void mgs_ws_put(mgs_ctx *ctx, mgs_vec *v);
 template <class T>
 static inline int mgs_dev_alloc(mgs_ctx *ctx, T **p, size_t count) {
   *p = nullptr;

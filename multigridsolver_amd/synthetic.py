@@ -232,3 +232,29 @@ def csky3d(N, velocity=1000.0, workers=None, digits=6, rowsum_floor=None):
     np.cumsum(counts, out=rowptr[1:])
     assert rowptr[-1] < 2 ** 31
     return rowptr.astype(np.int32), np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
+
+
+def moving_blob_rhs(N, step, dim=3, dt=0.05):
+    """Right-hand side number `step` of a slowly varying sequence (successive right-hand sides of one operator: Guess, tools/ab_guess.py): a
+    Gaussian blob (σ = 0.1) moving on a circle of radius 1/4 around the centre of the unit square / cube, plus six sine modes whose
+    amplitudes vary in time; t = step·dt; nodes (i + 1/2)/N, rows e = (i*N + j)*N + k as the Poisson and csky3d operators order them."""
+    import math
+    t = step * dt
+    ax = (np.arange(N) + 0.5) / N
+    shape = [1] * dim
+    g = []
+    for d in range(dim):
+        sh = list(shape); sh[d] = N
+        g.append(ax.reshape(sh))
+    x, y = g[0], g[1]
+    cx, cy = 0.5 + 0.25 * math.cos(t), 0.5 + 0.25 * math.sin(t)
+    d2 = (x - cx) ** 2 + (y - cy) ** 2
+    if dim == 3:
+        d2 = d2 + (g[2] - 0.5) ** 2
+    b = np.exp(-d2 / (2 * 0.1 ** 2))
+    for m in range(1, 7):
+        mode = np.sin(m * math.pi * x) * np.sin((m % 3 + 1) * math.pi * y)
+        if dim == 3:
+            mode = mode * np.sin((m % 2 + 1) * math.pi * g[2])
+        b = b + (math.cos(m * t + m) / m) * mode
+    return np.ascontiguousarray(b.reshape(-1))
