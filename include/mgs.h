@@ -404,6 +404,50 @@ int mgs_fgcr(const mgs_csr *A, mgs_vec *x, const mgs_vec *b, mgs_hier *h, int re
 int mgs_pcg(const mgs_csr *A, mgs_vec *x, const mgs_vec *b, mgs_hier *h, int flexible,
             int *max_iter, double *tol, int *status);
 
+/* ------------------------------------- PCG with device-resident scalars: enqueue-only solves, one host look per iteration */
+/* Nearest reference line: src/CPU_Matlab/solve.m:28-31 (pcg); the reference has no counterpart for the asynchronous form.  mgs_pcg computes ρ, α, β
+ * and the stopping test on the host: three host looks per iteration, each one draining the queue behind it, and the call cannot return before
+ * the solve is over.  A plan keeps those scalars in one state block in device memory (normb, rho, rho_prev, alpha, beta, pq, zq, rr, resid,
+ * true_resid; flags it, status, frozen, first, pending, wasted).  One-wave scalar-step kernels (INIT, RHO, PQ, RES, FINAL) turn the folded inner
+ * products into the next scalars with the operations the host uses in mgs_pcg, the direction, residual and flush passes read α and β from the
+ * state block, and everything else is the very launches mgs_pcg makes — so every bit of x agrees with mgs_pcg's.  An iteration is a fixed
+ * launch sequence: cycle (or copy), projection (declared null space), dots + fold, RHO, direction, SpMV with p·q + fold, PQ, residual + fold, RES.
+ * A solve that converges (by the recursion) or breaks down sets `frozen` on the device: later iterations change no vector the solve depends
+ * on (their scalar steps count into `wasted`, their vector passes return at once; cycle, SpMV and reductions still run).
+ *   create: borrows A and h (may be NULL); both must outlive the plan.  mgs_pcg's acceptance rules (flexible = 0 refuses nu1 != nu2 and the
+ *     K-cycle; the null-space kinds of A and h must agree); runs mgs_csr_optimize(A); allocates r, z, p, q and the state block (inside the arena
+ *     when one exists; not from the work-vector pool), a ring of posted results in mapped host memory, the partial-sum buffer, and runs one cycle
+ *     on r = 1 so that the hierarchy's operands exist and the cycle is captured: no later call allocates.  r and z never move, so the cycle replays
+ *     from one captured graph for the life of the plan.
+ *   solve: mgs_pcg's contract — statuses 0/1/2/3, the *max_iter / *tol write-back, x = initial guess, status 0 only on the TRUE residual,
+ *     restart from the true residual when the recursion had drifted — and mgs_pcg's bits, for every ahead >= 0.  The host looks once per
+ *     iteration (RES posts iteration, status, frozen, resid and a ticket into the ring) and looks BEHIND the queue: iteration k is not enqueued
+ *     before the outcome of iteration k − 1 − ahead has been seen, and never beyond *max_iter.  ahead = 0: a look per iteration, nothing
+ *     speculative; a large ahead: one look at the end, up to `ahead` wasted iterations (ahead is clamped to 1022, the ring's size).  On a posted
+ *     "recursion converged" the host flushes, projects, forms the true residual (a synchronising look) and either returns or clears `frozen`
+ *     on the stream and enqueues again from the next iteration.
+ *   enqueue: no host wait at all.  INIT, `iters` iterations, then FINAL: the predicated flush of x, the projection (declared null space),
+ *     r = b − A·x, its norm, and the status: 0 only if the recursion froze as converged AND the true residual is below tol; 2 or 3 as found;
+ *     else 1.  x and b must stay alive and untouched until the result is read or the stream is synchronised.  A second enqueue is ordered
+ *     behind the first on the stream.
+ *   result (synchronises): of the last enqueue: *iters_done = where the solve froze, or iters; *resid = the true relative residual; *status.
+ *     Status 1 with iters_done < iters: the recursion had drifted — enqueue again, which starts from the true residual as mgs_pcg's restart
+ *     does.  After a solve: what that solve returned.
+ *   info: out = device bytes held, solves + enqueues so far, iterations enqueued by the last call, of those the iterations that ran frozen
+ *     (cycle + SpMV wasted; known after solve / result), host waits the last call made, restarts from the true residual in the last call.
+ *   A declared MGS_NULLSPACE_CONSTANT is honoured as in mgs_pcg: z is projected after every preconditioner application, ‖Πb‖ is the norm, x is
+ *   projected before every true residual that may decide.
+ * MGS_ERR_INVALID, with a message: a NULL argument; a matrix without rows; a row shard (A->cols > A->rows, a context that sums over ranks, a hierarchy with halo
+ * columns, callbacks, native plans or a tail); h's fine operator carrying another null-space kind than A; vectors shorter than A's rows; x
+ * aliasing b; ahead < 0; iters < 0.  MGS_ERR_STATE: the context's stream is being captured (capturing a whole solve is not supported). */
+typedef struct mgs_pcg_plan mgs_pcg_plan;
+int mgs_pcg_plan_create(const mgs_csr *A, mgs_hier *h, int flexible, mgs_pcg_plan **out);
+int mgs_pcg_plan_destroy(mgs_pcg_plan *p);
+int mgs_pcg_plan_solve(mgs_pcg_plan *p, mgs_vec *x, const mgs_vec *b, int ahead, int *max_iter, double *tol, int *status);
+int mgs_pcg_plan_enqueue(mgs_pcg_plan *p, mgs_vec *x, const mgs_vec *b, int iters, double tol);
+int mgs_pcg_plan_result(mgs_pcg_plan *p, int *iters_done, double *resid, int *status);
+int mgs_pcg_plan_info(const mgs_pcg_plan *p, int64_t out[6]);
+
 /* ------------------------------------- projected initial guesses for successive right-hand sides */
 /* Nearest reference line: none: the reference solves one right-hand side, bicg.cpp:159-166.  A caller who solves with the same operator again and
  * again (time stepping, Picard / Newton, the pressure Poisson equation) gets a better start than its last solution by projecting the new

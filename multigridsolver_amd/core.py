@@ -642,6 +642,50 @@ class Guess:
         out = np.zeros(max(k * k, 1)); check(lib().mgs_guess_gram(self.h, _dp(out)), self.ctx.h); return out[: k * k].reshape(k, k)
 
 
+class PcgPlan:
+    """Preconditioned CG with device-resident scalars (mgs_pcg_plan, include/mgs.h): mgs_pcg's arithmetic and bits, with one host look per
+    iteration `ahead` iterations behind the queue (solve), or none at all (enqueue, then result).  A and hier must outlive the plan (they are
+    kept referenced here)."""
+
+    def __init__(self, A, hier=None, flexible=False):
+        self.ctx, self.A, self.hier = A.ctx, A, hier
+        h = C.c_void_p()
+        check(lib().mgs_pcg_plan_create(A.h, hier.h if hier else None, int(bool(flexible)), C.byref(h)), A.ctx.h)
+        self.h = h
+        self._keep = None
+
+    def __del__(self):
+        try:
+            if self.h and self.ctx.h:
+                lib().mgs_pcg_plan_destroy(self.h)
+        except Exception:  # noqa: BLE001
+            pass
+
+    def solve(self, x, b, max_iter=10000, tol=1e-6, ahead=1):
+        """mgs_pcg's contract → (status, iterations, achieved_tol)"""
+        mi, t, st = C.c_int(max_iter), C.c_double(tol), C.c_int(-1)
+        check(lib().mgs_pcg_plan_solve(self.h, x.h, b.h, int(ahead), C.byref(mi), C.byref(t), C.byref(st)), self.ctx.h)
+        return st.value, mi.value, t.value
+
+    def enqueue(self, x, b, iters, tol):
+        """INIT, `iters` iterations and the final true residual on the context's stream; no host wait.  x and b are kept referenced until result()"""
+        check(lib().mgs_pcg_plan_enqueue(self.h, x.h, b.h, int(iters), float(tol)), self.ctx.h)
+        self._keep = (self._keep, x, b)
+        return self
+
+    def result(self):
+        """of the last enqueue (synchronises) → (status, iterations done, true relative residual)"""
+        it, r, st = C.c_int(), C.c_double(), C.c_int(-1)
+        check(lib().mgs_pcg_plan_result(self.h, C.byref(it), C.byref(r), C.byref(st)), self.ctx.h)
+        self._keep = None
+        return st.value, it.value, r.value
+
+    def info(self):
+        """[0] device bytes, [1] solves + enqueues, [2] iterations enqueued by the last call, [3] of those run frozen, [4] host waits, [5] restarts"""
+        out = (C.c_int64 * 6)(); check(lib().mgs_pcg_plan_info(self.h, out), self.ctx.h)
+        return [int(v) for v in out]
+
+
 def bicgstab(A, x, b, hier=None, max_iter=10000, tol=1e-6):
     """BiCGSTABiml (reference bicg.cpp:74-136) → (status, iterations, achieved_tol)"""
     mi, t, st = C.c_int(max_iter), C.c_double(tol), C.c_int(-1)

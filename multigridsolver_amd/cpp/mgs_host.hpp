@@ -363,6 +363,39 @@ class SolutionGuess {
   mgs_guess *handle() const { return g_.get(); }
 };
 
+// ---------------------------------------------------------------- PCG with device-resident scalars (mgs.h: mgs_pcg_plan)
+// No reference counterpart for the asynchronous form.  CGiml's arithmetic and bits with one host look per iteration (solve), or none at all
+// (enqueue + result).  With SolutionGuess, a time step that never holds the host thread:
+//   guess.applyAsync(b, x);  plan.enqueue(x, b, iters, tol);  /* ... other host work ... */  plan.result(it, resid);  guess.update(x);
+// The plan keeps the DeviceMatrix and the preconditioner alive.  x and b must stay alive until result() (or a synchronisation).
+class PcgPlan {
+  DeviceMatrix A_;
+  MultiGridPrecond M_;
+  std::shared_ptr<mgs_pcg_plan> p_;
+ public:
+  PcgPlan(const DeviceMatrix &A, const MultiGridPrecond &M) : A_(A), M_(M) {
+    mgs_pcg_plan *p = nullptr;
+    check(mgs_pcg_plan_create(A.handle(), M.use_preconditioner() ? M.handle() : nullptr, M.symmetric() ? 0 : 1, &p), context());
+    p_ = std::shared_ptr<mgs_pcg_plan>(p, [](mgs_pcg_plan *q) { mgs_pcg_plan_destroy(q); });
+  }
+  // CGiml's contract: returns the status, max_iter and tol are written back; `ahead` iterations stay enqueued beyond the last outcome seen
+  int solve(Vector &x, const Vector &b, int &max_iter, double &tol, int ahead = 1) {
+    int status = -1;
+    check(mgs_pcg_plan_solve(p_.get(), x.out(), b.handle(), ahead, &max_iter, &tol, &status), context());
+    return status;
+  }
+  // INIT, `iters` iterations and the final true residual, enqueued; no host wait
+  void enqueue(Vector &x, const Vector &b, int iters, double tol) { check(mgs_pcg_plan_enqueue(p_.get(), x.out(), b.handle(), iters, tol), context()); }
+  // of the last enqueue (synchronises): returns the status; iterations done and the true relative residual
+  int result(int &iters_done, double &resid) {
+    int status = -1;
+    check(mgs_pcg_plan_result(p_.get(), &iters_done, &resid, &status), context());
+    return status;
+  }
+  int64_t info(int i) const { int64_t o[6]; check(mgs_pcg_plan_info(p_.get(), o), context()); return o[i]; }
+  mgs_pcg_plan *handle() const { return p_.get(); }
+};
+
 // ---------------------------------------------------------------- TicToc.cpp:18-53
 class TicToc {
   std::chrono::time_point<std::chrono::system_clock> start;

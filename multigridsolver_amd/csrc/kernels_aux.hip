@@ -1130,6 +1130,18 @@ static int fetch_results(mgs_ctx *ctx, int cnt, double *out_host, const Post &pa
   return MGS_OK;
 }
 
+// "Enqueue and fold" without "fetch" (mgs_pcg_plan, pcg_plan.hip): a reduction called with a NULL host pointer launches exactly what it
+// launches otherwise, posts nothing and returns as soon as the fold is enqueued; the folded values stay in red_dev[DOT_BLOCKS ..], where the
+// next kernel on the stream finds them.  With a host pointer nothing changes.
+static const Post NO_POST = {nullptr, nullptr, 0ull};
+static int fetch_or_leave(mgs_ctx *ctx, int cnt, double *out_host, const Post &pa) {
+  if (out_host) return fetch_results(ctx, cnt, out_host, pa);
+  MGS_HIP(ctx, hipGetLastError());
+  return MGS_OK;
+}
+int mgs_blas1_grid(const mgs_ctx *ctx, int64_t n2) { return grid_vec(n2, ctx); }
+int mgs_blas1_grid_capped(const mgs_ctx *ctx, int64_t n) { return grid_cap(n, ctx->n_cu); }
+
 int k_dot(mgs_ctx *ctx, int64_t n, const double *x, const double *y, double *out_host) {
   if (ctx->opt_blas1_vec && n >= 2 && al16(x) && al16(y)) {       // one-shot workgroups, staged fold (as the fused update kernels)
     const int nbv = grid_vec(n / 2, ctx);
@@ -1137,6 +1149,7 @@ int k_dot(mgs_ctx *ctx, int64_t n, const double *x, const double *y, double *out
     if (nbv > DOT_BLOCKS / 2) { MGS_TRY(mgs_ensure_dot_part(ctx, 2 * (int64_t)nbv)); part = ctx->dot_part; }
     hipLaunchKernelGGL(dot_block_vec_kernel<1>, dim3(nbv), dim3(TB), 0, ctx->stream, n, x, y, x, y, part);
     MGS_HIP(ctx, hipGetLastError());
+    if (!out_host) return k_dot2_finish(ctx, nbv, part, nullptr);
     double two[2] = {0.0, 0.0};
     MGS_TRY(k_dot2_finish(ctx, nbv, part, two));
     *out_host = two[0];
@@ -1146,10 +1159,10 @@ int k_dot(mgs_ctx *ctx, int64_t n, const double *x, const double *y, double *out
   if (nb > DOT_BLOCKS) nb = DOT_BLOCKS;
   if (nb < 1) nb = 1;
   hipLaunchKernelGGL(dot_partial_kernel, dim3(nb), dim3(TB), 0, ctx->stream, n, x, y, ctx->red_dev);
-  const Post pa = begin_post(ctx);
+  const Post pa = out_host ? begin_post(ctx) : NO_POST;
   hipLaunchKernelGGL(dot_final_kernel, dim3(1), dim3(TB), 0, ctx->stream, nb, ctx->red_dev, ctx->red_dev + DOT_BLOCKS, pa);
   if (ctx->ncomm) MGS_TRY(mgs_comm_allreduce_sum(ctx->ncomm, ctx->red_dev + DOT_BLOCKS, 1));   // sum over the row shards, on this stream
-  return fetch_results(ctx, 1, out_host, pa);
+  return fetch_or_leave(ctx, 1, out_host, pa);
 }
 
 // middle stage for long partial arrays (one pair per row block of a 512³ operator = 2 × 524 288): workgroup g sums the g-th
@@ -1174,11 +1187,11 @@ int k_dot2_finish(mgs_ctx *ctx, int nb, const double *part, double *out_host2) {
     hipLaunchKernelGGL(dot2_mid_kernel, dim3(groups), dim3(TB), 0, ctx->stream, nb, chunk, part, ctx->red_dev);
     part = ctx->red_dev; nb = groups;
   }
-  const Post pa = begin_post(ctx);
+  const Post pa = out_host2 ? begin_post(ctx) : NO_POST;
   hipLaunchKernelGGL(dot2_final_kernel, dim3(1), dim3(TB), 0, ctx->stream, nb, part, ctx->red_dev + DOT_BLOCKS, pa);
   MGS_HIP(ctx, hipGetLastError());
   if (ctx->ncomm) MGS_TRY(mgs_comm_allreduce_sum(ctx->ncomm, ctx->red_dev + DOT_BLOCKS, 2));
-  return fetch_results(ctx, 2, out_host2, pa);
+  return fetch_or_leave(ctx, 2, out_host2, pa);
 }
 int k_dot2(mgs_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w, double *out_host2) {
   if (ctx->opt_blas1_vec && n >= 2 && al16(x) && al16(y) && al16(z) && al16(w)) {
@@ -1193,10 +1206,10 @@ int k_dot2(mgs_ctx *ctx, int64_t n, const double *x, const double *y, const doub
   if (nb > DOT_BLOCKS / 2) nb = DOT_BLOCKS / 2;
   if (nb < 1) nb = 1;
   hipLaunchKernelGGL(dot2_partial_kernel, dim3(nb), dim3(TB), 0, ctx->stream, n, x, y, z, w, ctx->red_dev);
-  const Post pa = begin_post(ctx);
+  const Post pa = out_host2 ? begin_post(ctx) : NO_POST;
   hipLaunchKernelGGL(dot2_final_kernel, dim3(1), dim3(TB), 0, ctx->stream, nb, ctx->red_dev, ctx->red_dev + DOT_BLOCKS, pa);
   if (ctx->ncomm) MGS_TRY(mgs_comm_allreduce_sum(ctx->ncomm, ctx->red_dev + DOT_BLOCKS, 2));
-  return fetch_results(ctx, 2, out_host2, pa);
+  return fetch_or_leave(ctx, 2, out_host2, pa);
 }
 int k_update_dot2(mgs_ctx *ctx, int64_t n, double a, const double *x, double b, const double *y, double *z, const double *w, double *out_host2) {
   int nb = (int)((n + TB - 1) / TB);
@@ -1258,7 +1271,7 @@ int k_pcg_residual(mgs_ctx *ctx, int64_t n, double a, double *r, const double *q
 constexpr int MEAN_SLOT = DOT_BLOCKS + MGS_RED_VALS;
 static_assert(DOT_BLOCKS == MGS_DOT_BLOCKS && MEAN_SLOT < MGS_RED_CAP, "the mean slot lies behind the folded results, inside mgs_ctx::red_dev");
 // store: v is shifted in place (else only read); nrm2_host != NULL: nrm2_host[0] = ‖v − m‖² reaches the host (k_dot2_finish), nrm2_host[1] = 0
-static int project_const_impl(mgs_ctx *ctx, int64_t n, double *v, bool store, double *nrm2_host) {
+static int project_const_impl(mgs_ctx *ctx, int64_t n, double *v, bool store, double *nrm2_host, bool nrm2_fold = false) {
   if (n <= 0) { if (nrm2_host) nrm2_host[0] = nrm2_host[1] = 0.0; return MGS_OK; }
   const bool vec = ctx->opt_blas1_vec && al16(v);
   int nb = vec ? grid_vec((n + 1) / 2, ctx) : std::max(1, std::min(mgs_grid(n, TB), DOT_BLOCKS / 2));
@@ -1275,7 +1288,7 @@ static int project_const_impl(mgs_ctx *ctx, int64_t n, double *v, bool store, do
   }
   hipLaunchKernelGGL(mean_final_kernel, dim3(1), dim3(TB), 0, s, nf, fold, (double)n, mean);
   const int nts = ctx->opt_nt_store > 0 && n >= ctx->opt_nt_store;
-  const bool nrm = nrm2_host != nullptr;
+  const bool nrm = nrm2_host != nullptr || nrm2_fold;
 #define SHIFT_(ST, NR)                                                                                                              \
   do {                                                                                                                              \
     if (vec) hipLaunchKernelGGL((shift_const_vec_kernel<ST, NR>), dim3(nb), dim3(TB), 0, s, n, v, mean, part, nts);                  \
@@ -1290,6 +1303,9 @@ int k_project_const(mgs_ctx *ctx, int64_t n, double *v) { return project_const_i
 int k_project_const_nrm2(mgs_ctx *ctx, int64_t n, double *v, double *out_host2) { return project_const_impl(ctx, n, v, true, out_host2); }
 int k_const_dev_nrm2(mgs_ctx *ctx, int64_t n, const double *v, double *out_host2) { return project_const_impl(ctx, n, const_cast<double *>(v), false, out_host2); }
 // the mean the last projection on this context subtracted (diagnostics; synchronises)
+// the same two with the norm left on the device (red_dev[DOT_BLOCKS], see fetch_or_leave): no host round trip
+int k_project_const_nrm2_fold(mgs_ctx *ctx, int64_t n, double *v) { return project_const_impl(ctx, n, v, true, nullptr, true); }
+int k_const_dev_nrm2_fold(mgs_ctx *ctx, int64_t n, const double *v) { return project_const_impl(ctx, n, const_cast<double *>(v), false, nullptr, true); }
 int k_project_const_mean(mgs_ctx *ctx, double *mean_host) {
   MGS_HIP(ctx, hipMemcpyAsync(mean_host, ctx->red_dev + MEAN_SLOT, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   MGS_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -1846,6 +1846,10 @@ static int krylov_nullspace(const mgs_csr *A, const mgs_hier *h, const char *who
   return MGS_OK;
 }
 
+extern "C++" {
+int mgs_krylov_nullspace(const mgs_csr *A, const mgs_hier *h, const char *who, bool *ns_out) { return krylov_nullspace(A, h, who, ns_out); }
+}
+
 // BiCGSTABiml, reference src/common/bicg.cpp:74-136, statement by statement on device vectors.
 int mgs_bicgstab(const mgs_csr *A, mgs_vec *x, const mgs_vec *b, mgs_hier *h, int *max_iter, double *tol, int *status) {
   mgs_ctx *ctx = A->ctx;

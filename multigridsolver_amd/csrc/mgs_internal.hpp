@@ -408,6 +408,10 @@ int k_dot2(mgs_ctx *ctx, int64_t n, const double *x, const double *y, const doub
 // and the residual in place (r ← r − a·q, out_host2[0] = ‖r‖²)
 int k_pcg_direction(mgs_ctx *ctx, int64_t n, int first, double a, double beta, double *x, double *p, const double *z);
 int k_pcg_residual(mgs_ctx *ctx, int64_t n, double a, double *r, const double *q, double *out_host2);
+// Reductions that end in a host look (k_dot, k_dot2, k_dot2_finish, mgs_spmv_dots) take out_host = NULL as "enqueue and fold, do not fetch": the
+// same launches, nothing posted, the folded values left in red_dev[MGS_DOT_BLOCKS ..] for the next kernel on the stream (mgs_pcg_plan).
+int mgs_blas1_grid(const mgs_ctx *ctx, int64_t n2);          // workgroups of a 16-byte BLAS-1 launch over n2 pairs (grid_vec)
+int mgs_blas1_grid_capped(const mgs_ctx *ctx, int64_t n);   // ... of an 8-byte grid-stride launch over n entries (grid_cap)
 int mgs_ensure_dot_part(mgs_ctx *ctx, int64_t doubles);   // per-workgroup partial pairs of one-shot reduction launches
 int k_dot2_finish(mgs_ctx *ctx, int nb, const double *part /*[2][nb]*/, double *out_host2);   // second stage + rank reduction + host copy
 // y = A·x with (y·w1, y·y) from the same pass where the pattern-coded kernel serves A (else SpMV + k_dot2): BiCGSTAB's
@@ -424,6 +428,8 @@ int k_dense_inverse(mgs_ctx *ctx, const mgs_csr *A, double **inv_out, int reg_co
 int k_project_const(mgs_ctx *ctx, int64_t n, double *v);
 int k_project_const_nrm2(mgs_ctx *ctx, int64_t n, double *v, double *out_host2);
 int k_const_dev_nrm2(mgs_ctx *ctx, int64_t n, const double *v, double *out_host2);
+int k_project_const_nrm2_fold(mgs_ctx *ctx, int64_t n, double *v);         // ... the norm² stays in red_dev[MGS_DOT_BLOCKS]: enqueued only
+int k_const_dev_nrm2_fold(mgs_ctx *ctx, int64_t n, const double *v);
 int k_project_const_mean(mgs_ctx *ctx, double *mean_host);   // the mean the last projection subtracted (synchronises)
 int k_abs_inplace(mgs_ctx *ctx, int64_t n, double *v);
 int k_absmax_dev(mgs_ctx *ctx, int64_t n, const double *v, unsigned long long *amax_bits_dev);
@@ -452,6 +458,8 @@ int k_csr_update_values_coo(mgs_csr *A, const void *val_dev);
 int mgs_csr_alloc(mgs_ctx *ctx, int rows, int cols, int64_t nnz, mgs_csr **out);
 // the context's pool of work vectors (the Krylov solvers' ws_get / ws_put) for the other translation units: a vector of n entries, written before
 // it is read by whoever takes it; mgs_ws_put(NULL) does nothing
+// the Krylov solvers' null-space rule (krylov_nullspace) for the other translation units
+int mgs_krylov_nullspace(const mgs_csr *A, const mgs_hier *h, const char *who, bool *ns_out);
 int mgs_ws_get(mgs_ctx *ctx, int64_t n, int64_t owned, mgs_vec **out);
 void mgs_ws_put(mgs_ctx *ctx, mgs_vec *v);
 template <class T>
