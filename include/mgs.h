@@ -448,6 +448,65 @@ int mgs_pcg_plan_enqueue(mgs_pcg_plan *p, mgs_vec *x, const mgs_vec *b, int iter
 int mgs_pcg_plan_result(mgs_pcg_plan *p, int *iters_done, double *resid, int *status);
 int mgs_pcg_plan_info(const mgs_pcg_plan *p, int64_t out[6]);
 
+/* ------------------------------------- BiCGSTAB with device-resident scalars: enqueue-only solves, one host look per iteration */
+/* Reference: BiCGSTABiml, src/common/bicg.cpp:74-136; the reference has no counterpart for the asynchronous form.  mgs_bicgstab computes ρ, α, ω, β and
+ * three stopping tests on the host: four host looks per iteration (r̃·v, ‖s‖, (t·s, t·t), (‖r‖, r̃·r)), each one draining the queue behind it, and
+ * the call cannot return before the solve is over.  A plan keeps those scalars in one state block in device memory (normb, rho, rho_next,
+ * rho_prev, alpha, omega, beta, nbo = −β·ω, rtv, ts, tt, ss, rr, resid, true_resid; flags it, status (−1 running), frozen, first, half, wasted).
+ * One-wave scalar-step kernels turn the folded inner products into the next scalars with the operations, in the order, the host uses in
+ * mgs_bicgstab; the vector passes read their coefficients from the state block and evaluate the expressions of the kernels mgs_bicgstab runs
+ * (a·x + b·y (+ c·z), unfused; the passes with sums with k_update_dot2's grids, partial layout and fold), and everything else is the very
+ * launches mgs_bicgstab makes — so every bit of x agrees with mgs_bicgstab's.  One iteration i is a fixed launch sequence:
+ *   RHO     :95     rho = the r̃·r the last residual pass (or INIT) left
+ *           :96-99  rho == 0: frozen, status 2; resid keeps √(r·r)/‖b‖
+ *           :103    not the first iteration: beta = (rho/rho_prev)·(alpha/omega), nbo = −beta·omega
+ *   p-pass  :100-101 first: p ← r;  :104 else p = 1.0·r + nbo·v + beta·p
+ *   cycle   :106    p̂ = M·p (a copy when h is NULL), projected when the null space is declared
+ *   SpMV    :107    v = A·p̂ with r̃·v from the same pass
+ *   ALPHA   :108    alpha = rho/(r̃·v); no test for zero: a non-finite alpha propagates as in mgs_bicgstab
+ *   s-pass  :109    s = 1.0·r + (−alpha)·v with ‖s‖²
+ *   HALF    :110    resid = ‖s‖/‖b‖; below tol: frozen, status 0, half = 1
+ *   cycle   :116    ŝ = M·s, projected likewise
+ *   SpMV    :117    t = A·ŝ with (t·s, t·t)
+ *   OMEGA   :118    omega = (t·s)/(t·t)
+ *   x-pass  :119    x = alpha·p̂ + omega·ŝ + 1.0·x;  :111 frozen with half: x = alpha·p̂ + 1.0·x (p̂ is intact: p did not change)
+ *   r-pass  :120    r = 1.0·s + (−omega)·t with (‖r‖², r̃·r)
+ *   RES     :122    rho_prev = rho;  :123-127 resid = ‖r‖/‖b‖ below tol: frozen, status 0;  :128-131 else omega == 0: frozen, status 3; the post
+ * Nothing on the host depends on a device value.  Once `frozen` is set, later iterations change no vector the solve depends on: their scalar
+ * steps do nothing (RHO counts into `wasted`), their vector passes return at once (the half-step x-pass excepted); cycles, SpMVs and folds
+ * still run.  INIT (:80-92): ‖b‖ (‖Πb‖ with a declared null space), 0 replaced by 1; r = b − A·x, projected likewise; r̃ ← r; (‖r‖², r̃·r);
+ * resid <= tol: frozen, status 0, iteration 0.
+ *   create: borrows A and h (may be NULL); both must outlive the plan.  mgs_bicgstab's acceptance rules (the null-space kinds of A and h must
+ *     agree); runs mgs_csr_optimize(A); allocates p, p̂, s, ŝ, t, v, r, r̃ and the state block (inside the arena when one exists; not from the
+ *     work-vector pool), a ring of 1024 posted results of 64 bytes in mapped host memory, the partial-sum buffer, and runs the cycles p → p̂
+ *     and s → ŝ on ones so that the hierarchy's operands exist and both cycles are captured: no later call allocates.  The vectors never move,
+ *     so the two cycles replay from two captured graphs for the life of the plan.
+ *   solve: mgs_bicgstab's contract and bits for every ahead >= 0 (clamped to 1022).  Write-back as mgs_bicgstab: status 0: *max_iter = the
+ *     iteration, *tol = resid; statuses 2 and 3: *tol only, *max_iter untouched; status 1: *tol = resid; *max_iter = 0: status 1 unless INIT
+ *     converged.  Status 0 is decided on the recursive residual, as in mgs_bicgstab; there is no restart branch.  The host looks once per
+ *     iteration (RES posts ticket, iteration, status, frozen, wasted, resid, ‖b‖ into the ring) and looks BEHIND the queue: iteration k is
+ *     not enqueued before the post of iteration k − 1 − ahead has been seen, and never beyond *max_iter; on a frozen post the host stops
+ *     enqueuing.  With a declared null space x ← Πx follows the last update, before the call returns.
+ *   enqueue: no host wait at all.  INIT, `iters` iterations, then FINAL: x ← Πx (declared null space), the true residual b − A·x into t
+ *     (projected likewise), true_resid = ‖t‖/‖b‖, and the status: 0 only if the recursion froze as converged AND true_resid is below tol; 2
+ *     or 3 as found; else 1.  x and b must stay alive and untouched until the result is read or the stream is synchronised.
+ *   result (synchronises): of the last enqueue: *iters_done = where the solve froze, or iters; *resid = the true relative residual;
+ *     *recursive_resid (may be NULL) = the recursion's; *status.  Status 1 with iters_done < iters: the recursion had drifted — enqueue
+ *     again; x is then the initial guess.  (mgs_bicgstab itself has no true-residual confirmation and does not change.)  After a solve:
+ *     what that solve returned.
+ *   info: out = device bytes held, solves + enqueues so far, iterations enqueued by the last call, of those the iterations that ran frozen
+ *     (known after solve / result), host waits the last call made, 0 (the PCG plan's restarts; there is no restart here).
+ * MGS_ERR_INVALID, with a message: a NULL argument; a matrix without rows; a row shard (A->cols > A->rows, a context that sums over ranks, a
+ * hierarchy with halo columns, callbacks, native plans or a tail); h's fine operator carrying another null-space kind than A; vectors shorter
+ * than A's rows; x aliasing b; ahead < 0; iters < 0.  MGS_ERR_STATE: the context's stream is being captured. */
+typedef struct mgs_bicgstab_plan mgs_bicgstab_plan;
+int mgs_bicgstab_plan_create(const mgs_csr *A, mgs_hier *h, mgs_bicgstab_plan **out);
+int mgs_bicgstab_plan_destroy(mgs_bicgstab_plan *p);
+int mgs_bicgstab_plan_solve(mgs_bicgstab_plan *p, mgs_vec *x, const mgs_vec *b, int ahead, int *max_iter, double *tol, int *status);
+int mgs_bicgstab_plan_enqueue(mgs_bicgstab_plan *p, mgs_vec *x, const mgs_vec *b, int iters, double tol);
+int mgs_bicgstab_plan_result(mgs_bicgstab_plan *p, int *iters_done, double *resid, double *recursive_resid, int *status);
+int mgs_bicgstab_plan_info(const mgs_bicgstab_plan *p, int64_t out[6]);
+
 /* ------------------------------------- projected initial guesses for successive right-hand sides */
 /* Nearest reference line: none: the reference solves one right-hand side, bicg.cpp:159-166.  A caller who solves with the same operator again and
  * again (time stepping, Picard / Newton, the pressure Poisson equation) gets a better start than its last solution by projecting the new

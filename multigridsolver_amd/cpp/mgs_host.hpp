@@ -396,6 +396,39 @@ class PcgPlan {
   mgs_pcg_plan *handle() const { return p_.get(); }
 };
 
+// ---------------------------------------------------------------- BiCGSTAB with device-resident scalars (mgs.h: mgs_bicgstab_plan)
+// bicg.cpp:74-136 has no asynchronous form.  BiCGSTABiml's arithmetic and bits with one host look per iteration (solve), or none at all
+// (enqueue + result, which also reports the true residual bicg.cpp never forms).  With SolutionGuess(A, MGS_GUESS_RESIDUAL):
+//   guess.applyAsync(b, x);  plan.enqueue(x, b, iters, tol);  /* ... other host work ... */  plan.result(it, resid);  guess.update(x);
+// The plan keeps the DeviceMatrix and the preconditioner alive.  x and b must stay alive until result() (or a synchronisation).
+class BicgstabPlan {
+  DeviceMatrix A_;
+  MultiGridPrecond M_;
+  std::shared_ptr<mgs_bicgstab_plan> p_;
+ public:
+  BicgstabPlan(const DeviceMatrix &A, const MultiGridPrecond &M) : A_(A), M_(M) {
+    mgs_bicgstab_plan *p = nullptr;
+    check(mgs_bicgstab_plan_create(A.handle(), M.use_preconditioner() ? M.handle() : nullptr, &p), context());
+    p_ = std::shared_ptr<mgs_bicgstab_plan>(p, [](mgs_bicgstab_plan *q) { mgs_bicgstab_plan_destroy(q); });
+  }
+  // BiCGSTABiml's contract: returns the status, max_iter and tol are written back; `ahead` iterations stay enqueued beyond the last outcome seen
+  int solve(Vector &x, const Vector &b, int &max_iter, double &tol, int ahead = 1) {
+    int status = -1;
+    check(mgs_bicgstab_plan_solve(p_.get(), x.out(), b.handle(), ahead, &max_iter, &tol, &status), context());
+    return status;
+  }
+  // INIT, `iters` iterations and the final true residual, enqueued; no host wait
+  void enqueue(Vector &x, const Vector &b, int iters, double tol) { check(mgs_bicgstab_plan_enqueue(p_.get(), x.out(), b.handle(), iters, tol), context()); }
+  // of the last enqueue (synchronises): returns the status; iterations done, the true relative residual and (optionally) the recursion's
+  int result(int &iters_done, double &resid, double *recursive_resid = nullptr) {
+    int status = -1;
+    check(mgs_bicgstab_plan_result(p_.get(), &iters_done, &resid, recursive_resid, &status), context());
+    return status;
+  }
+  int64_t info(int i) const { int64_t o[6]; check(mgs_bicgstab_plan_info(p_.get(), o), context()); return o[i]; }
+  mgs_bicgstab_plan *handle() const { return p_.get(); }
+};
+
 // ---------------------------------------------------------------- TicToc.cpp:18-53
 class TicToc {
   std::chrono::time_point<std::chrono::system_clock> start;

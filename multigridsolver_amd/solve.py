@@ -24,11 +24,12 @@ def main(argv=None):
     ap.add_argument("--P", default=None, help="prolongation .mtx from the AGMG setup (single GPU only); default: aggregate on device")
     ap.add_argument("--tol", type=float, default=1e-6)           # bicg.cpp:148
     ap.add_argument("--max-iter", type=int, default=10000)       # bicg.cpp:164
-    ap.add_argument("--solver", choices=["bicgstab", "fgcr", "pcg"], default="bicgstab")
+    ap.add_argument("--solver", choices=["bicgstab", "fgcr", "pcg"], default=None, help="default: bicgstab")
     ap.add_argument("--pcg-flexible", action="store_true", help="--solver pcg: flexible β, for a preconditioner that is not a fixed symmetric operator (--nu1 != --nu2, --kcycle)")
     ap.add_argument("--ahead", type=int, default=None, metavar="N",
-                    help="--solver pcg: solve through a PcgPlan (scalars stay on the device, one host look per iteration) that keeps N iterations "
-                         "enqueued beyond the last outcome seen; same result as without the flag; single GPU only")
+                    help="--solver pcg or --solver bicgstab, named on the command line: solve through a PcgPlan resp. BicgstabPlan (scalars stay on the "
+                         "device, one host look per iteration) that keeps N iterations enqueued beyond the last outcome seen; same result as without "
+                         "the flag; single GPU only")
     ap.add_argument("--kcycle", type=int, default=0)
     ap.add_argument("--kcycle-energy", action="store_true", help="K-cycle coefficients from energy inner products (flexible-CG form; symmetric positive definite operators only)")
     ap.add_argument("--omega", type=float, default=0.6)
@@ -49,8 +50,10 @@ def main(argv=None):
         raise SystemExit("multi-GPU: FP64 operands only (--operand-bits 32 is a single-GPU option)")
     if world > 1 and args.nullspace != "none":
         raise SystemExit("multi-GPU: --nullspace is a single-GPU option (row shards carry no null-space declaration)")
-    if args.ahead is not None and (args.solver != "pcg" or world > 1 or args.ahead < 0):
-        raise SystemExit("--ahead N (N >= 0) goes with --solver pcg on a single GPU")
+    if args.ahead is not None and (args.solver not in ("pcg", "bicgstab") or world > 1 or args.ahead < 0):
+        raise SystemExit("--ahead N (N >= 0) goes with --solver pcg or --solver bicgstab, named explicitly, on a single GPU")
+    if args.solver is None:
+        args.solver = "bicgstab"
     if world > 1:
         import torch  # noqa: F401  — before libmgs.so: both link a HIP runtime, the first one loaded serves the process
     import multigridsolver_amd as mg
@@ -74,7 +77,9 @@ def main(argv=None):
         if args.operand_bits != 64:
             h.set_operand_precision(args.operand_bits)
         x, b = ctx.vec(rows), ctx.vec(bg)
-        plan = mg.PcgPlan(A, h, args.pcg_flexible) if args.ahead is not None else None      # allocations and the cycle's capture: outside the timer
+        plan = None                                                                         # allocations and the cycles' capture: outside the timer
+        if args.ahead is not None:
+            plan = mg.PcgPlan(A, h, args.pcg_flexible) if args.solver == "pcg" else mg.BicgstabPlan(A, h)
         ctx.sync(); t0 = time.perf_counter()
         if plan is not None:
             st, it, tol = plan.solve(x, b, args.max_iter, args.tol, args.ahead)
