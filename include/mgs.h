@@ -507,6 +507,66 @@ int mgs_bicgstab_plan_enqueue(mgs_bicgstab_plan *p, mgs_vec *x, const mgs_vec *b
 int mgs_bicgstab_plan_result(mgs_bicgstab_plan *p, int *iters_done, double *resid, double *recursive_resid, int *status);
 int mgs_bicgstab_plan_info(const mgs_bicgstab_plan *p, int64_t out[6]);
 
+/* ------------------------------------- flexible GCR with device-resident coefficients: enqueue-only solves, one host look per iteration */
+/* Nearest reference line: the Krylov call of src/CPU_Matlab/solve.m:28-33; the reference has no flexible method and no asynchronous form.  mgs_fgcr
+ * fetches three results per iteration (the h_j of the multi-dot, (ρ_k, t) of the orthogonalisation pass, ‖r‖² of the residual pass), hands the
+ * coefficients U_jk = h_j/ρ_j to the orthogonalisation kernel by value, solves (I + U)·y = α on the host when a window closes and cannot
+ * return before the solve is over.  A plan keeps them in one state block in device memory (normb, resid, true_resid, rr; ρ, α, h, y, cf = −y of
+ * 16 entries each; U of 16 × 16; flags it, status (−1 running), frozen, why, m_open, wasted).  One-wave scalar-step kernels form every scalar
+ * with the operation, in the order, the host code of mgs_fgcr uses; three vector passes read their coefficients from the state block and
+ * evaluate the expressions of the kernels mgs_fgcr runs (maxpy_dot2_kernel's z = x − Σ cf_j·w_j with its 16-byte and 8-byte arms, grid, partial
+ * layout and fold; k_update_dot2's 1.0·r + (−α_k)·v with its launch decisions and store rule); everything else is the very launches mgs_fgcr
+ * makes — so every bit of x agrees with mgs_fgcr's.  One iteration at window slot k (the host always knows k) is a fixed launch sequence:
+ *   cycle   C[k] = M·r (a copy when h is NULL), projected when the null space is declared
+ *   SpMV    V[k] = A·C[k]
+ *   dots    k = 0: (V[0]·V[0], V[0]·r) by k_dot2;  k > 0: h_j = V[j]·V[k], j < k, by k_mdot into the state block
+ *   COEF    U_jk = ρ_j != 0 ? h_j/ρ_j : 0
+ *   orth    V[k] ← V[k] − Σ_{j<k} U_jk·V[j] with (V[k]·V[k], V[k]·r)                                      (k > 0)
+ *   RHOK    ρ_k, t from the fold; m_open = k + 1; ρ_k == 0: α_k = 0, frozen as "breakdown"; else α_k = t/ρ_k
+ *   r-pass  r ← 1.0·r + (−α_k)·V[k] with ‖r‖²
+ *   RES     resid = √(‖r‖²)/‖b‖; below tol: frozen as "the recursion says converged"; the post, unless the iteration closes its window
+ * and a window close is
+ *   YSOLVE  (I + U)·y = α over the m_open directions by back substitution, cf_j = −y_j
+ *   x-pass  x ← x − Σ_{j<m_open} cf_j·C[j]; guarded by m_open, not by frozen
+ *   x ← Πx  where mgs_fgcr projects (a close that may decide a return), declared null space only
+ *   r = b − A·x (projected likewise) and its norm
+ *   WIN     resid = the true residual; running and below tol: frozen, status 0; frozen as "the recursion says converged": status 0, or "drifted";
+ *           frozen as "breakdown": status 0 or 2; m_open = 0; the post
+ * Once `frozen` is set, later iterations change no vector the solve depends on: COEF, RHOK and RES do nothing (RHOK counts into `wasted`), the
+ * orth and r passes return at once, and cycle and SpMV write C[k], V[k] of slots behind the open ones only.  The first close after a freeze
+ * applies the open window once; every later close is a no-op.  INIT: ‖b‖ (‖Πb‖), 0 replaced by 1; x ← Πx; r = b − A·x; resid <= tol: frozen,
+ * status 0, iteration 0.
+ *   create: borrows A and h (may be NULL); both must outlive the plan.  restart in 1..16 (one multi-vector pass holds 16 vectors, a hierarchy
+ *     caches 16 captured cycles; mgs_fgcr itself keeps 1..64).  mgs_fgcr's acceptance rules (the null-space kinds of A and h must agree); runs
+ *     mgs_csr_optimize(A); allocates r, C[0..restart), V[0..restart) and the state block (inside the arena when one exists; not from the
+ *     work-vector pool), a ring of 1024 posted results of 64 bytes in mapped host memory, the partial-sum buffer, and runs the cycle r → C[k]
+ *     once for every k so that the hierarchy's operands exist and the cycles are captured: no later call allocates.
+ *   solve: mgs_fgcr's contract and bits for every ahead >= 0 (clamped to 1022): statuses 0/1/2, *max_iter = the iterations run and *tol = the
+ *     residual on every path, status 0 only on the true residual, `<=` at iteration 0 and `<` later.  The host looks once per iteration, BEHIND
+ *     the queue: iteration k is not enqueued before the post of iteration k − 1 − ahead has been seen, and never beyond *max_iter.  On a posted
+ *     "the recursion says converged" or "breakdown" the host stops enqueuing, enqueues close, projection and true residual, and looks: it
+ *     returns, or ("drifted") clears `frozen` on the stream and goes on from the next iteration with an empty window — mgs_fgcr's restart from
+ *     the true residual.  The close behind the last iteration of all is enqueued behind its look as well.
+ *   enqueue: no host wait at all.  INIT, `iters` iterations with a scheduled close every `restart` iterations, then FINAL: the open window is
+ *     closed, x ← Πx (declared null space), the true residual b − A·x, and the status: 0 only if the true residual is below tol; 2 for a
+ *     breakdown whose true residual is not; else 1.  There is no restart from the true residual on the device.  x and b must stay alive and
+ *     untouched until the result is read or the stream is synchronised.
+ *   result (synchronises): of the last enqueue: *iters_done = where the solve froze, or iters; *resid = the true relative residual;
+ *     *recursive_resid (may be NULL) = the recursion's; *status.  Status 1 with iters_done < iters: the recursion had drifted — enqueue again
+ *     from x.  After a solve: what that solve returned.
+ *   info: out = device bytes held, solves + enqueues so far, iterations enqueued by the last call, of those the iterations that ran frozen
+ *     (known after solve / result), host waits the last call made, restarts from the true residual after a drifted convergence in the last call.
+ * MGS_ERR_INVALID, with a message: a NULL argument; a matrix without rows; a row shard (A->cols > A->rows, a context that sums over ranks, a
+ * hierarchy with halo columns, callbacks, native plans or a tail); h's fine operator carrying another null-space kind than A; vectors shorter
+ * than A's rows; x aliasing b; ahead < 0; iters < 0; restart outside 1..16.  MGS_ERR_STATE: the context's stream is being captured. */
+typedef struct mgs_fgcr_plan mgs_fgcr_plan;
+int mgs_fgcr_plan_create(const mgs_csr *A, mgs_hier *h, int restart, mgs_fgcr_plan **out);
+int mgs_fgcr_plan_destroy(mgs_fgcr_plan *p);
+int mgs_fgcr_plan_solve(mgs_fgcr_plan *p, mgs_vec *x, const mgs_vec *b, int ahead, int *max_iter, double *tol, int *status);
+int mgs_fgcr_plan_enqueue(mgs_fgcr_plan *p, mgs_vec *x, const mgs_vec *b, int iters, double tol);
+int mgs_fgcr_plan_result(mgs_fgcr_plan *p, int *iters_done, double *resid, double *recursive_resid, int *status);
+int mgs_fgcr_plan_info(const mgs_fgcr_plan *p, int64_t out[6]);
+
 /* ------------------------------------- projected initial guesses for successive right-hand sides */
 /* Nearest reference line: none: the reference solves one right-hand side, bicg.cpp:159-166.  A caller who solves with the same operator again and
  * again (time stepping, Picard / Newton, the pressure Poisson equation) gets a better start than its last solution by projecting the new

@@ -142,6 +142,12 @@ PROTOTYPES = {
     "mgs_bicgstab_plan_enqueue": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double]),
     "mgs_bicgstab_plan_result": (C.c_int, [C.c_void_p, c_int_p, c_dbl_p, c_dbl_p, c_int_p]),
     "mgs_bicgstab_plan_info": (C.c_int, [C.c_void_p, c_i64_p]),
+    "mgs_fgcr_plan_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "mgs_fgcr_plan_destroy": (C.c_int, [C.c_void_p]),
+    "mgs_fgcr_plan_solve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, c_int_p, c_dbl_p, c_int_p]),
+    "mgs_fgcr_plan_enqueue": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double]),
+    "mgs_fgcr_plan_result": (C.c_int, [C.c_void_p, c_int_p, c_dbl_p, c_dbl_p, c_int_p]),
+    "mgs_fgcr_plan_info": (C.c_int, [C.c_void_p, c_i64_p]),
     "mgs_guess_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "mgs_guess_destroy": (C.c_int, [C.c_void_p]),
     "mgs_guess_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_dbl_p]),

@@ -429,6 +429,40 @@ class BicgstabPlan {
   mgs_bicgstab_plan *handle() const { return p_.get(); }
 };
 
+// ---------------------------------------------------------------- flexible GCR with device-resident coefficients (mgs.h: mgs_fgcr_plan)
+// The reference has no flexible method (nearest line: src/CPU_Matlab/solve.m:28-33) and no asynchronous form.  mgs_fgcr's arithmetic and bits —
+// the Krylov method the K-cycle needs on nonsymmetric operators — with one host look per iteration (solve), or none at all (enqueue + result):
+//   guess.applyAsync(b, x);  plan.enqueue(x, b, iters, tol);  /* ... other host work ... */  plan.result(it, resid);  guess.update(x);
+// The plan keeps the DeviceMatrix and the preconditioner alive.  x and b must stay alive until result() (or a synchronisation).
+class FgcrPlan {
+  DeviceMatrix A_;
+  MultiGridPrecond M_;
+  std::shared_ptr<mgs_fgcr_plan> p_;
+ public:
+  FgcrPlan(const DeviceMatrix &A, const MultiGridPrecond &M, int restart = 10) : A_(A), M_(M) {      // restart in 1..16
+    mgs_fgcr_plan *p = nullptr;
+    check(mgs_fgcr_plan_create(A.handle(), M.use_preconditioner() ? M.handle() : nullptr, restart, &p), context());
+    p_ = std::shared_ptr<mgs_fgcr_plan>(p, [](mgs_fgcr_plan *q) { mgs_fgcr_plan_destroy(q); });
+  }
+  // mgs_fgcr's contract: returns the status, max_iter and tol are written back; `ahead` iterations stay enqueued beyond the last outcome seen
+  // (0 by default: with a K-cycle the iteration that ahead = 1 runs frozen costs more than the look it hides, profiles/r14_fgcr_plan.md)
+  int solve(Vector &x, const Vector &b, int &max_iter, double &tol, int ahead = 0) {
+    int status = -1;
+    check(mgs_fgcr_plan_solve(p_.get(), x.out(), b.handle(), ahead, &max_iter, &tol, &status), context());
+    return status;
+  }
+  // INIT, `iters` iterations with their scheduled window closes and the final true residual, enqueued; no host wait
+  void enqueue(Vector &x, const Vector &b, int iters, double tol) { check(mgs_fgcr_plan_enqueue(p_.get(), x.out(), b.handle(), iters, tol), context()); }
+  // of the last enqueue (synchronises): returns the status; iterations done, the true relative residual and (optionally) the recursion's
+  int result(int &iters_done, double &resid, double *recursive_resid = nullptr) {
+    int status = -1;
+    check(mgs_fgcr_plan_result(p_.get(), &iters_done, &resid, recursive_resid, &status), context());
+    return status;
+  }
+  int64_t info(int i) const { int64_t o[6]; check(mgs_fgcr_plan_info(p_.get(), o), context()); return o[i]; }
+  mgs_fgcr_plan *handle() const { return p_.get(); }
+};
+
 // ---------------------------------------------------------------- TicToc.cpp:18-53
 class TicToc {
   std::chrono::time_point<std::chrono::system_clock> start;

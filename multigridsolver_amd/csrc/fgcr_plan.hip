@@ -1,0 +1,644 @@
+// fgcr_plan.hip — flexible GCR(m) whose coefficients never leave the device (mgs_fgcr_plan, include/mgs.h).
+// Reference: the Krylov driver of src/CPU_Matlab/solve.m:28-33 is the nearest line; the reference has no flexible method and no asynchronous form.
+//
+// mgs_fgcr (mgs_api.hip) fetches the h_j of the multi-dot, (ρ_k, t) of the orthogonalisation pass and ‖r‖² of the residual pass — three host looks
+// per iteration —, hands the coefficients U_jk = h_j/ρ_j to the orthogonalisation kernel by value and solves (I + U)·y = α on the host when a
+// window closes.  Here ρ, α, U, y live in one state block in device memory, as bicgstab_plan.hip keeps mgs_bicgstab's scalars.  One-wave "scalar
+// step" kernels form every scalar with the operation, and in the order, the host code of mgs_fgcr uses (no fast-math, no contraction; FP64
+// division and sqrt are correctly rounded), and three new vector passes evaluate the expressions of maxpy_dot2_kernel and of
+// update_dot2_partial(_vec)_kernel with their coefficients read from the state block.  Everything else is the launches mgs_fgcr makes, called
+// with a NULL host pointer: the cycle, the projection, the SpMV, k_dot2, k_mdot, mgs_residual and the folds.  So every bit agrees with mgs_fgcr's.
+//
+// One iteration at window slot k (the host always knows k) is the fixed launch sequence
+//   cycle r → C[k] (projected) · SpMV V[k] = A·C[k] · k = 0: k_dot2 (V0·V0, V0·r); k > 0: k_mdot → h_j · COEF · orthogonalisation pass + fold
+//   · RHOK · residual pass + fold · RES
+// and a window close is YSOLVE · x-pass · (projection of x) · mgs_residual and its norm · WIN.
+// A solve that converges by the recursion, converges by a true residual, or breaks down sets `frozen`; from then on COEF, RHOK and RES are no-ops
+// (RHOK counts into `wasted`) and the orthogonalisation and residual passes return before they touch a vector.  Cycles, SpMVs and reductions of a
+// frozen iteration still run; they write C[k], V[k] of slots behind the open ones (k ≥ m_open) and scratch only.  The x-pass of a close is guarded
+// by `m_open`, not by `frozen`: the first close after a freeze applies the open window once, WIN sets m_open = 0, every later close is a no-op.
+//
+// RES and WIN (and INIT) post (iteration, status, why, frozen, wasted, resid) and a ticket into a ring of slots in mapped, coherent host memory.
+// mgs_fgcr_plan_solve looks at one slot per iteration, `ahead` iterations behind the queue, and orchestrates every restart from the true residual
+// itself (mgs_fgcr's restart_now); mgs_fgcr_plan_enqueue never looks and its windows are fixed.
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <deque>
+#include <time.h>
+
+#include "mgs_internal.hpp"
+
+namespace {
+constexpr int PTB = 256;                 // lanes per workgroup of the vector passes (the BLAS-1 kernels' TB)
+constexpr int RING = 1024;               // posted slots; at most RING − 1 posts are outstanding, so no slot is rewritten before the host has read it
+constexpr int RED = MGS_DOT_BLOCKS;      // red_dev[RED], red_dev[RED + 1]: what the last fold left
+constexpr int FW = 16;                   // the widest window: one multi-vector pass holds 16 vectors (kernels_aux.hip: MDOT_MAX), a hierarchy caches 16 graphs
+typedef double fd2 __attribute__((ext_vector_type(2)));
+
+// why a solve froze
+enum { WHY_NONE = 0, WHY_RECURSION = 1, WHY_BREAKDOWN = 2, WHY_INIT = 3, WHY_TRUE = 4 };
+// status: −1 running, 0 converged on a true residual, 2 breakdown, 4 the recursion says converged (no true residual yet), 5 drifted (the recursion
+// said converged, the true residual does not); after FINAL: 0, 1 or 2 as mgs_fgcr reports them
+enum { ST_RUNNING = -1, ST_OK = 0, ST_BREAKDOWN = 2, ST_RECURSION = 4, ST_DRIFTED = 5 };
+
+struct FgState {
+  double normb, resid, true_resid, rr;
+  double rho[FW], alpha[FW], hj[FW], y[FW], cf[FW];   // cf_j = −y_j: the coefficients of the x-pass
+  double U[FW * FW];                                    // U[j·FW + k] = h_j/ρ_j of iteration k, j < k
+  int it;        // the last iteration that ran unfrozen (the one that froze, once frozen)
+  int status;
+  int frozen;
+  int why;
+  int m_open;    // directions of the open window that x has not received yet
+  int wasted;    // iterations that ran frozen
+};
+struct FgSlot {    // 64 bytes of mapped host memory
+  unsigned long long ticket;
+  double resid, normb;
+  int it, status, frozen, wasted, why, m_open;
+  unsigned long long pad[2];
+};
+static_assert(sizeof(FgSlot) == 64, "one slot per 64 bytes");
+
+enum { STEP_NORMB = 0, STEP_INIT, STEP_COEF, STEP_RHOK, STEP_RES, STEP_YSOLVE, STEP_WIN, STEP_RESUME, STEP_FINAL };
+
+__device__ __forceinline__ void post_slot(FgSlot *s, const FgState *st, unsigned long long ticket) {
+  __hip_atomic_store(&s->resid, st->resid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(&s->normb, st->normb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(&s->it, st->it, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(&s->status, st->status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(&s->frozen, st->frozen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(&s->wasted, st->wasted, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(&s->why, st->why, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(&s->m_open, st->m_open, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(&s->ticket, ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// The scalar steps: one wave, lane 0 works.  red = ctx->red_dev + RED.  k: the window slot (COEF, RHOK); `it`: the iteration the step belongs to
+// (FINAL: the iterations enqueued); `tol`: the tolerance (INIT, RES, WIN, FINAL); slot = NULL: nothing is posted.  Line numbers: mgs_api.hip, mgs_fgcr.
+__global__ void fgp_step_kernel(int step, FgState *__restrict__ st, const double *__restrict__ red, int k, int it, double tol, FgSlot *slot, unsigned long long ticket) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  switch (step) {
+    case STEP_NORMB: {                      // ‖b‖ (‖Πb‖), 0 replaced by 1; a fresh state
+      double nb = sqrt(red[0]);
+      if (nb == 0.0) nb = 1.0;
+      st->normb = nb;
+      st->resid = st->true_resid = st->rr = 0.0;
+      st->it = 0; st->status = ST_RUNNING; st->frozen = 0; st->why = WHY_NONE; st->m_open = 0; st->wasted = 0;
+      break;
+    }
+    case STEP_INIT: {                       // red[0] = ‖b − A·x‖²: the `<=` of iteration 0
+      st->rr = red[0];
+      const double nr = sqrt(red[0]);
+      st->resid = nr / st->normb;
+      if (st->resid <= tol) { st->frozen = 1; st->status = ST_OK; st->why = WHY_INIT; }
+      if (slot) post_slot(slot, st, ticket);
+      break;
+    }
+    case STEP_COEF: {                       // U_jk = ρ_j != 0 ? h_j/ρ_j : 0
+      if (st->frozen) break;
+      for (int j = 0; j < k; ++j) st->U[j * FW + k] = st->rho[j] != 0.0 ? st->hj[j] / st->rho[j] : 0.0;
+      break;
+    }
+    case STEP_RHOK: {                       // red = (ρ_k, t)
+      if (st->frozen) { st->wasted += 1; break; }
+      st->it = it;
+      st->rho[k] = red[0];
+      st->m_open = k + 1;
+      if (st->rho[k] == 0.0) { st->alpha[k] = 0.0; st->frozen = 1; st->status = ST_BREAKDOWN; st->why = WHY_BREAKDOWN; break; }
+      st->alpha[k] = red[1] / st->rho[k];
+      break;
+    }
+    case STEP_RES: {                        // red[0] = ‖r‖² of the recursion
+      if (!st->frozen) {
+        st->rr = red[0];
+        st->resid = sqrt(red[0]) / st->normb;
+        if (st->resid < tol) { st->frozen = 1; st->status = ST_RECURSION; st->why = WHY_RECURSION; }
+      }
+      if (slot) post_slot(slot, st, ticket);
+      break;
+    }
+    case STEP_YSOLVE: {                     // close_window: (I + U)·y = α over the m_open directions, cf_j = −y_j
+      const int m = st->m_open;
+      for (int q = m - 1; q >= 0; --q) {
+        double s = st->alpha[q];
+        for (int p = q + 1; p < m; ++p) s -= st->U[q * FW + p] * st->y[p];
+        st->y[q] = s;
+      }
+      for (int q = 0; q < m; ++q) st->cf[q] = -st->y[q];
+      break;
+    }
+    case STEP_WIN: {                        // red[0] = ‖b − A·x‖² behind a close
+      const double t = sqrt(red[0]) / st->normb;
+      st->true_resid = t;
+      if (!st->frozen) {
+        st->resid = t;
+        if (t < tol) { st->frozen = 1; st->status = ST_OK; st->why = WHY_TRUE; }
+      } else if (st->why == WHY_RECURSION) { st->resid = t; st->status = t < tol ? ST_OK : ST_DRIFTED; }
+      else if (st->why == WHY_BREAKDOWN) { st->resid = t; st->status = t < tol ? ST_OK : ST_BREAKDOWN; }
+      st->m_open = 0;
+      if (slot) post_slot(slot, st, ticket);
+      break;
+    }
+    case STEP_RESUME: {                     // the host has seen "drifted": go on from the true residual with an empty window
+      st->frozen = 0; st->status = ST_RUNNING; st->why = WHY_NONE; st->m_open = 0;
+      break;
+    }
+    case STEP_FINAL: {                      // behind the last close, the projection of x and r = b − A·x: red[0] = ‖r‖²
+      const double t = sqrt(red[0]) / st->normb;
+      st->true_resid = t;
+      if (!st->frozen) { st->it = it; st->status = t < tol ? 0 : 1; }
+      else if (st->why == WHY_INIT) st->status = t <= tol ? 0 : 1;
+      else if (st->why == WHY_BREAKDOWN) st->status = t < tol ? 0 : 2;
+      else st->status = t < tol ? 0 : 1;
+      st->frozen = 1; st->m_open = 0;
+      break;
+    }
+  }
+}
+
+__device__ __forceinline__ void fst2(fd2 *p, fd2 v, bool nt) {      // streaming store, as st2 in kernels_aux.hip
+  if (nt) asm volatile("global_store_dwordx4 %0, %1, off nt" : : "v"(p), "v"(v) : "memory");
+  else *p = v;
+}
+
+struct FgVecs { const double *w[FW]; };
+
+// Orthogonalisation pass: v ← v − Σ_{j<K} U_jK·w_j with the partial pairs (v·v, v·u), maxpy_dot2_kernel's expression (its z = x = v, u2 = NULL),
+// arms, partial layout [2][gridDim.x] and in-workgroup fold; the coefficients come from the state block.  Frozen: v and the partials stay.
+template <bool VEC>
+__global__ __launch_bounds__(PTB) void fgp_orth_kernel(int64_t n, int K, const FgState *__restrict__ st, double *v, const FgVecs W, const double *__restrict__ u,
+                                                       double *__restrict__ part) {
+  if (st->frozen) return;
+  __shared__ double sh[2][PTB / 64];
+  double cf[FW];
+#pragma unroll
+  for (int k = 0; k < FW; ++k) cf[k] = k < K ? st->U[k * FW + K] : 0.0;
+  double s0 = 0.0, s1 = 0.0;
+  const int64_t stride = (int64_t)gridDim.x * PTB;
+  if (VEC) {
+    const int64_t n2 = n >> 1;
+    fd2 *vv = reinterpret_cast<fd2 *>(v);
+    const fd2 *__restrict__ uv = reinterpret_cast<const fd2 *>(u);
+    for (int64_t i = (int64_t)blockIdx.x * PTB + threadIdx.x; i < n2; i += stride) {
+      fd2 zi = vv[i];
+#pragma unroll
+      for (int k = 0; k < FW; ++k)
+        if (k < K) { const fd2 wi = reinterpret_cast<const fd2 *>(W.w[k])[i]; zi.x -= cf[k] * wi.x; zi.y -= cf[k] * wi.y; }
+      vv[i] = zi;
+      s0 += zi.x * zi.x; s0 += zi.y * zi.y;
+      const fd2 q = uv[i]; s1 += zi.x * q.x; s1 += zi.y * q.y;
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+      double zi = v[n - 1];
+#pragma unroll
+      for (int k = 0; k < FW; ++k) if (k < K) zi -= cf[k] * W.w[k][n - 1];
+      v[n - 1] = zi;
+      s0 += zi * zi;
+      s1 += zi * u[n - 1];
+    }
+  } else {
+    for (int64_t i = (int64_t)blockIdx.x * PTB + threadIdx.x; i < n; i += stride) {
+      double zi = v[i];
+#pragma unroll
+      for (int k = 0; k < FW; ++k) if (k < K) zi -= cf[k] * W.w[k][i];
+      v[i] = zi;
+      s0 += zi * zi;
+      s1 += zi * u[i];
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) { s0 += __shfl_down(s0, off); s1 += __shfl_down(s1, off); }
+  if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = s0; sh[1][threadIdx.x >> 6] = s1; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t0 = 0.0, t1 = 0.0;
+    for (int q = 0; q < PTB / 64; ++q) { t0 += sh[0][q]; t1 += sh[1][q]; }
+    part[blockIdx.x] = t0; part[gridDim.x + blockIdx.x] = t1;
+  }
+}
+
+// x-pass of a window close: x ← x − Σ_{j<m_open} cf_j·c_j, maxpy_dot2_kernel's expression without sums; m_open and cf from the state block.
+// Guarded by m_open alone: the close behind a freeze still owes x its window, a close with nothing open touches nothing.
+template <bool VEC>
+__global__ __launch_bounds__(PTB) void fgp_x_kernel(int64_t n, const FgState *__restrict__ st, double *x, const FgVecs W) {
+  const int K = st->m_open;
+  if (K <= 0) return;
+  double cf[FW];
+#pragma unroll
+  for (int k = 0; k < FW; ++k) cf[k] = k < K ? st->cf[k] : 0.0;
+  const int64_t stride = (int64_t)gridDim.x * PTB;
+  if (VEC) {
+    const int64_t n2 = n >> 1;
+    fd2 *xv = reinterpret_cast<fd2 *>(x);
+    for (int64_t i = (int64_t)blockIdx.x * PTB + threadIdx.x; i < n2; i += stride) {
+      fd2 zi = xv[i];
+#pragma unroll
+      for (int k = 0; k < FW; ++k)
+        if (k < K) { const fd2 wi = reinterpret_cast<const fd2 *>(W.w[k])[i]; zi.x -= cf[k] * wi.x; zi.y -= cf[k] * wi.y; }
+      xv[i] = zi;
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+      double zi = x[n - 1];
+#pragma unroll
+      for (int k = 0; k < FW; ++k) if (k < K) zi -= cf[k] * W.w[k][n - 1];
+      x[n - 1] = zi;
+    }
+  } else {
+    for (int64_t i = (int64_t)blockIdx.x * PTB + threadIdx.x; i < n; i += stride) {
+      double zi = x[i];
+#pragma unroll
+      for (int k = 0; k < FW; ++k) if (k < K) zi -= cf[k] * W.w[k][i];
+      x[i] = zi;
+    }
+  }
+}
+
+// Residual pass in place: r ← 1.0·r + (−α_k)·v with the partial pairs (r·r, 0) of update_dot2_partial_vec_kernel<false> / update_dot2_partial_kernel —
+// the same per-element expression, the same order of additions per lane, the same layout [2][gridDim.x].  Frozen: r and the partials stay.
+__global__ __launch_bounds__(PTB) void fgp_resid_vec_kernel(int64_t n, int k, const FgState *__restrict__ st, double *r, const double *__restrict__ v,
+                                                            double *__restrict__ part, int nts) {
+  if (st->frozen) return;
+  const double a = 1.0, b = -st->alpha[k];
+  __shared__ double sh[2][PTB / 64];
+  const int64_t n2 = n >> 1;
+  fd2 *rv = reinterpret_cast<fd2 *>(r);
+  const fd2 *__restrict__ yv = reinterpret_cast<const fd2 *>(v);
+  double s0 = 0.0, s1 = 0.0;
+  const int64_t stride = (int64_t)gridDim.x * PTB;
+  for (int64_t i = (int64_t)blockIdx.x * PTB + threadIdx.x; i < n2; i += stride) {
+    const fd2 p = rv[i], o = yv[i]; fd2 q;
+    q.x = a * p.x + b * o.x; q.y = a * p.y + b * o.y;
+    fst2(rv + i, q, nts != 0);
+    s0 += q.x * q.x; s0 += q.y * q.y;
+  }
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+    const double zi = a * r[n - 1] + b * v[n - 1];
+    r[n - 1] = zi; s0 += zi * zi;
+  }
+  for (int off = 32; off > 0; off >>= 1) { s0 += __shfl_down(s0, off); s1 += __shfl_down(s1, off); }
+  if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = s0; sh[1][threadIdx.x >> 6] = s1; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t0 = 0.0, t1 = 0.0;
+    for (int q = 0; q < PTB / 64; ++q) { t0 += sh[0][q]; t1 += sh[1][q]; }
+    part[blockIdx.x] = t0; part[gridDim.x + blockIdx.x] = t1;
+  }
+}
+__global__ __launch_bounds__(PTB) void fgp_resid_kernel(int64_t n, int k, const FgState *__restrict__ st, double *r, const double *__restrict__ v, double *__restrict__ part) {
+  if (st->frozen) return;
+  const double a = 1.0, b = -st->alpha[k];
+  __shared__ double sh[2][PTB / 64];
+  double s0 = 0.0, s1 = 0.0;
+  int64_t i = (int64_t)blockIdx.x * PTB + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * PTB;
+  for (; i < n; i += stride) {
+    const double zi = a * r[i] + b * v[i];
+    r[i] = zi;
+    s0 += zi * zi;
+  }
+  for (int off = 32; off > 0; off >>= 1) { s0 += __shfl_down(s0, off); s1 += __shfl_down(s1, off); }
+  if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = s0; sh[1][threadIdx.x >> 6] = s1; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t0 = 0.0, t1 = 0.0;
+    for (int q = 0; q < PTB / 64; ++q) { t0 += sh[0][q]; t1 += sh[1][q]; }
+    part[blockIdx.x] = t0; part[gridDim.x + blockIdx.x] = t1;
+  }
+}
+
+inline bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// workgroups of maxpy_dot2_kernel (k_maxpy_dot2) and of mdot_partial_kernel (k_mdot)
+inline int maxpy_grid(int64_t n) { return (int)std::min<int64_t>(std::max<int64_t>((n + (int64_t)PTB * 4 - 1) / ((int64_t)PTB * 4), 1), 1 << 20); }
+inline int mdot_grid(int64_t n) { return (int)std::min<int64_t>(std::max<int64_t>((n / 2 + (int64_t)PTB * 4 - 1) / ((int64_t)PTB * 4), 1), 2048); }
+}   // namespace
+
+struct mgs_fgcr_plan {
+  mgs_ctx *ctx = nullptr;
+  const mgs_csr *A = nullptr;
+  mgs_hier *h = nullptr;
+  bool ns = false;
+  int n = 0, restart = 0;
+  double *block = nullptr;            // r, C[0..restart), V[0..restart) (stride doubles each), then the state
+  int64_t stride = 0, bytes = 0;
+  mgs_vec r, C[FW], V[FW];            // views into block
+  FgState *st = nullptr;
+  FgSlot *ring = nullptr, *ring_dev = nullptr;        // RING slots, then one FgState the result is copied into (mapped, coherent host memory)
+  FgState *snap = nullptr;
+  unsigned long long seq = 0;         // ticket of the last posting step enqueued
+  // what info and result report
+  int64_t calls = 0, enq_iters = 0, wasted = 0, waits = 0, restarts = 0;
+  bool unread = false;                // an enqueue whose result has not been read yet
+  int res_it = 0, res_status = 1; double res_resid = 0.0, res_rec = 0.0;
+};
+
+namespace {
+struct Look { int it, status, frozen, wasted, why; double resid; };
+
+int step(mgs_fgcr_plan *P, int which, int k, int it, double tol, bool post) {
+  mgs_ctx *ctx = P->ctx;
+  FgSlot *slot = nullptr;
+  if (post) { ++P->seq; slot = P->ring_dev + (P->seq % RING); }
+  hipLaunchKernelGGL(fgp_step_kernel, dim3(1), dim3(64), 0, ctx->stream, which, P->st, ctx->red_dev + RED, k, it, tol, slot, P->seq);
+  MGS_HIP(ctx, hipGetLastError());
+  return MGS_OK;
+}
+inline int nts_of(const mgs_ctx *ctx, int64_t n) { return ctx->opt_nt_store > 0 && n >= ctx->opt_nt_store; }
+
+// the grid, the arms, the partial buffer and the fold of k_maxpy_dot2 with sums (the plan's vectors are 256-byte aligned: the 16-byte arm whenever n >= 2)
+int launch_orth(mgs_fgcr_plan *P, int k) {
+  mgs_ctx *ctx = P->ctx; const int64_t n = P->n;
+  FgVecs W;
+  for (int j = 0; j < FW; ++j) W.w[j] = j < k ? P->V[j].d : P->V[k].d;
+  const int nb = maxpy_grid(n);
+  double *part = ctx->red_dev;
+  if (nb > MGS_DOT_BLOCKS / 2) { MGS_TRY(mgs_ensure_dot_part(ctx, 2 * (int64_t)nb)); part = ctx->dot_part; }
+  if (n >= 2) hipLaunchKernelGGL(fgp_orth_kernel<true>, dim3(nb), dim3(PTB), 0, ctx->stream, n, k, P->st, P->V[k].d, W, P->r.d, part);
+  else hipLaunchKernelGGL(fgp_orth_kernel<false>, dim3(nb), dim3(PTB), 0, ctx->stream, n, k, P->st, P->V[k].d, W, P->r.d, part);
+  MGS_HIP(ctx, hipGetLastError());
+  return k_dot2_finish(ctx, nb, part, nullptr);
+}
+int launch_x(mgs_fgcr_plan *P, double *x) {
+  mgs_ctx *ctx = P->ctx; const int64_t n = P->n;
+  FgVecs W;
+  for (int j = 0; j < FW; ++j) W.w[j] = j < P->restart ? P->C[j].d : x;      // slots at and behind m_open are never read
+  const int nb = maxpy_grid(n);
+  if (n >= 2 && al16(x)) hipLaunchKernelGGL(fgp_x_kernel<true>, dim3(nb), dim3(PTB), 0, ctx->stream, n, P->st, x, W);
+  else hipLaunchKernelGGL(fgp_x_kernel<false>, dim3(nb), dim3(PTB), 0, ctx->stream, n, P->st, x, W);
+  MGS_HIP(ctx, hipGetLastError());
+  return MGS_OK;
+}
+// the grids, the partial buffer, the store rule and the fold of k_update_dot2
+int launch_resid(mgs_fgcr_plan *P, int k) {
+  mgs_ctx *ctx = P->ctx; const int64_t n = P->n;
+  int nb = (int)((n + PTB - 1) / PTB);
+  if (nb > MGS_DOT_BLOCKS / 2) nb = MGS_DOT_BLOCKS / 2;
+  if (nb < 1) nb = 1;
+  if (ctx->opt_blas1_vec) {
+    nb = mgs_blas1_grid(ctx, (n + 1) / 2);
+    double *part = ctx->red_dev;
+    if (nb > MGS_DOT_BLOCKS / 2) { MGS_TRY(mgs_ensure_dot_part(ctx, 2 * (int64_t)nb)); part = ctx->dot_part; }
+    hipLaunchKernelGGL(fgp_resid_vec_kernel, dim3(nb), dim3(PTB), 0, ctx->stream, n, k, P->st, P->r.d, P->V[k].d, part, nts_of(ctx, n));
+    MGS_HIP(ctx, hipGetLastError());
+    return k_dot2_finish(ctx, nb, part, nullptr);
+  }
+  hipLaunchKernelGGL(fgp_resid_kernel, dim3(nb), dim3(PTB), 0, ctx->stream, n, k, P->st, P->r.d, P->V[k].d, ctx->red_dev);
+  MGS_HIP(ctx, hipGetLastError());
+  return k_dot2_finish(ctx, nb, ctx->red_dev, nullptr);
+}
+// r = b − A·x (r = Π(b − A·x)) with ‖r‖² left in red: mgs_fgcr's true_residual without its look
+int true_residual(mgs_fgcr_plan *P, const mgs_vec *xv, const mgs_vec *bv) {
+  MGS_TRY(mgs_residual(P->A, xv, bv, &P->r));
+  return P->ns ? k_project_const_nrm2_fold(P->ctx, P->n, P->r.d) : k_dot(P->ctx, P->n, P->r.d, P->r.d, nullptr);
+}
+// INIT: ‖b‖ (‖Πb‖), x ← Πx, the true residual, the freeze with (status 0, it 0) when it is within tol already
+int enqueue_init(mgs_fgcr_plan *P, mgs_vec *xv, const mgs_vec *bv, double tol, bool post) {
+  mgs_ctx *ctx = P->ctx; const int64_t n = P->n;
+  if (P->ns) MGS_TRY(k_const_dev_nrm2_fold(ctx, n, bv->d)); else MGS_TRY(k_dot(ctx, n, bv->d, bv->d, nullptr));
+  MGS_TRY(step(P, STEP_NORMB, 0, 0, 0.0, false));
+  if (P->ns) MGS_TRY(k_project_const(ctx, n, xv->d));
+  MGS_TRY(true_residual(P, xv, bv));
+  return step(P, STEP_INIT, 0, 0, tol, post);
+}
+int enqueue_iteration(mgs_fgcr_plan *P, int k, int it, double tol, bool post) {
+  mgs_ctx *ctx = P->ctx; const int64_t n = P->n;
+  if (P->h) MGS_TRY(mgs_vcycle(P->h, &P->r, &P->C[k], 1)); else MGS_TRY(mgs_vec_copy(&P->r, &P->C[k]));
+  if (P->ns) MGS_TRY(k_project_const(ctx, n, P->C[k].d));
+  MGS_TRY(mgs_spmv(P->A, &P->C[k], &P->V[k]));
+  if (k == 0) MGS_TRY(k_dot2(ctx, n, P->V[0].d, P->V[0].d, P->V[0].d, P->r.d, nullptr));
+  else {
+    const double *w[FW];
+    for (int q = 0; q < k; ++q) w[q] = P->V[q].d;
+    MGS_TRY(k_mdot(ctx, n, k, P->V[k].d, w, P->st->hj, nullptr));
+    MGS_TRY(step(P, STEP_COEF, k, it, 0.0, false));
+    MGS_TRY(launch_orth(P, k));
+  }
+  MGS_TRY(step(P, STEP_RHOK, k, it, 0.0, false));
+  MGS_TRY(launch_resid(P, k));
+  P->enq_iters++;
+  return step(P, STEP_RES, k, it, tol, post);
+}
+// a window close; `last`: the step behind it is FINAL (enqueue) instead of WIN
+int enqueue_close(mgs_fgcr_plan *P, mgs_vec *xv, const mgs_vec *bv, bool project, int it, double tol, bool post, bool last) {
+  MGS_TRY(step(P, STEP_YSOLVE, 0, it, 0.0, false));
+  MGS_TRY(launch_x(P, xv->d));
+  if (project && P->ns) MGS_TRY(k_project_const(P->ctx, P->n, xv->d));
+  MGS_TRY(true_residual(P, xv, bv));
+  return step(P, last ? STEP_FINAL : STEP_WIN, 0, it, tol, post);
+}
+// wait until the post with ticket `want` is visible (no slot is rewritten before it has been read: see RING)
+int wait_post(mgs_fgcr_plan *P, unsigned long long want, Look *out) {
+  mgs_ctx *ctx = P->ctx;
+  FgSlot *s = P->ring + (want % RING);
+  P->waits++;
+  const auto t0 = std::chrono::steady_clock::now();
+  double next_query = 2e-3;
+  for (;;) {
+    if (__atomic_load_n(&s->ticket, __ATOMIC_ACQUIRE) == want) break;
+    const double waited = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (waited < 300e-6) { for (int k = 0; k < 8; ++k) __builtin_ia32_pause(); continue; }
+    if (waited > next_query) {           // a queue that has drained (or failed) without the ticket will never deliver it
+      next_query = waited + 2e-3;
+      const hipError_t e = hipStreamQuery(ctx->stream);
+      if (e == hipSuccess) {
+        if (__atomic_load_n(&s->ticket, __ATOMIC_ACQUIRE) == want) break;
+        return mgs_fail(ctx, MGS_ERR_HIP, "mgs_fgcr_plan: posted results never reached the host ring");
+      }
+      if (e != hipErrorNotReady) return mgs_fail(ctx, MGS_ERR_HIP, "mgs_fgcr_plan: %s", hipGetErrorString(e));
+    }
+    struct timespec ts = {0, 25000}; nanosleep(&ts, nullptr);
+  }
+  out->it = s->it; out->status = s->status; out->frozen = s->frozen; out->wasted = s->wasted; out->why = s->why; out->resid = s->resid;
+  return MGS_OK;
+}
+int check_call(mgs_fgcr_plan *P, const mgs_vec *x, const mgs_vec *b, const char *who) {
+  mgs_ctx *ctx = P->ctx;
+  MGS_CHECK(ctx, x->n >= P->n && b->n >= P->n, MGS_ERR_INVALID, "%s: vectors of %lld and %lld entries, the operator has %d rows", who, (long long)x->n, (long long)b->n, P->n);
+  MGS_CHECK(ctx, x->d != b->d, MGS_ERR_INVALID, "%s: x must not alias b", who);
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  MGS_HIP(ctx, hipStreamIsCapturing(ctx->stream, &cs));
+  MGS_CHECK(ctx, cs == hipStreamCaptureStatusNone, MGS_ERR_STATE, "%s: the context's stream is being captured", who);
+  return MGS_OK;
+}
+}   // namespace
+
+int mgs_fgcr_plan_destroy(mgs_fgcr_plan *P) {
+  if (!P) return MGS_OK;
+  if (P->block || P->ring) hipStreamSynchronize(P->ctx->stream);
+  if (P->block) mgs_hip_free(P->block);
+  if (P->ring) hipHostFree(P->ring);
+  delete P;
+  return MGS_OK;
+}
+
+int mgs_fgcr_plan_create(const mgs_csr *A, mgs_hier *h, int restart, mgs_fgcr_plan **out) {
+  mgs_ctx *ctx = A ? A->ctx : (h ? h->ctx : nullptr);
+  MGS_CHECK(ctx, A && out, MGS_ERR_INVALID, "mgs_fgcr_plan_create: NULL argument");
+  MGS_CHECK(ctx, restart >= 1 && restart <= FW, MGS_ERR_INVALID, "mgs_fgcr_plan_create: restart = %d outside 1..%d (wider windows are served by mgs_fgcr)", restart, FW);
+  MGS_CHECK(ctx, A->rows == A->cols && !ctx->ncomm && !ctx->allreduce, MGS_ERR_INVALID, "mgs_fgcr_plan_create: the matrix is %d x %d%s (a square unsharded operator is required)",
+            A->rows, A->cols, A->cols > A->rows ? ", halo columns: a row shard" : (A->rows == A->cols ? ", on a context that sums over ranks" : ", not square"));
+  MGS_CHECK(ctx, A->rows > 0, MGS_ERR_INVALID, "mgs_fgcr_plan_create: the matrix has no rows");
+  if (h) {
+    bool shard = h->halo || h->halo_begin || h->halo_end || h->halo_fused || h->coarse || h->native || h->ntail;
+    for (const mgs_level &L : h->lev) shard = shard || L.nx || (L.A && L.A->cols > L.A->rows);
+    MGS_CHECK(ctx, !shard, MGS_ERR_INVALID, "mgs_fgcr_plan_create: the hierarchy has halo columns, exchange callbacks, native plans or a tail (a square unsharded operator is required)");
+    MGS_CHECK(ctx, h->ctx == ctx && !h->lev.empty() && h->lev[0].n == A->rows, MGS_ERR_INVALID, "mgs_fgcr_plan_create: the hierarchy's fine level has %d rows, A has %d",
+              h->lev.empty() ? 0 : h->lev[0].n, A->rows);
+    MGS_CHECK(ctx, h->finalized, MGS_ERR_STATE, "mgs_fgcr_plan_create: call mgs_hier_finalize first");
+  }
+  bool ns = false;
+  MGS_TRY(mgs_krylov_nullspace(A, h, "mgs_fgcr_plan_create", &ns));
+  MGS_TRY(mgs_csr_optimize(const_cast<mgs_csr *>(A)));
+  mgs_fgcr_plan *P = new mgs_fgcr_plan();
+  P->ctx = ctx; P->A = A; P->h = h; P->ns = ns; P->n = A->rows; P->restart = restart;
+  P->stride = (((int64_t)P->n + 31) / 32) * 32;                                          // every vector 256-byte aligned
+  const int nvec = 1 + 2 * restart;
+  const size_t nstate = (sizeof(FgState) + 255) / 256 * 32;                              // doubles
+  const size_t ndoubles = (size_t)nvec * P->stride + nstate;
+  int rc = mgs_dev_alloc(ctx, &P->block, ndoubles);
+  if (rc == MGS_OK && hipMemsetAsync(P->block, 0, sizeof(double) * ndoubles, ctx->stream) != hipSuccess) rc = mgs_fail(ctx, MGS_ERR_HIP, "mgs_fgcr_plan_create: hipMemsetAsync failed");
+  if (rc == MGS_OK) {
+    const size_t hb = sizeof(FgSlot) * RING + (sizeof(FgState) + 255) / 256 * 256;
+    if (hipHostMalloc((void **)&P->ring, hb, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) { P->ring = nullptr; rc = mgs_fail(ctx, MGS_ERR_ALLOC, "mgs_fgcr_plan_create: mapped host ring"); }
+    else {
+      memset(P->ring, 0, hb);
+      P->snap = reinterpret_cast<FgState *>(P->ring + RING);
+      if (hipHostGetDevicePointer((void **)&P->ring_dev, P->ring, 0) != hipSuccess) rc = mgs_fail(ctx, MGS_ERR_HIP, "mgs_fgcr_plan_create: the host ring is not mappable into the device");
+    }
+  }
+  if (rc != MGS_OK) { mgs_fgcr_plan_destroy(P); return rc; }
+  auto view = [&](mgs_vec &v, int64_t k) { v.ctx = ctx; v.n = P->n; v.d = P->block + k * P->stride; v.owns = false; };
+  view(P->r, 0);
+  for (int k = 0; k < restart; ++k) { view(P->C[k], 1 + k); view(P->V[k], 1 + restart + k); }
+  P->st = reinterpret_cast<FgState *>(P->block + (int64_t)nvec * P->stride);
+  P->bytes = (int64_t)(sizeof(double) * ndoubles);
+  // the partial sums of every reduction a solve launches, and the hierarchy's operands and one captured cycle r → C[k] per slot: no later call allocates
+  int64_t np = 2 * std::max<int64_t>(std::max<int64_t>(mgs_row_blocks(A), mgs_blas1_grid(ctx, ((int64_t)P->n + 1) / 2)), maxpy_grid(P->n));
+  np = std::max<int64_t>(np, (int64_t)restart * mdot_grid(P->n));
+  rc = mgs_ensure_dot_part(ctx, std::max<int64_t>(np, 2));
+  if (rc == MGS_OK && h) rc = k_fill(ctx, P->r.d, P->n, 1.0);
+  for (int k = 0; k < restart && rc == MGS_OK && h; ++k) rc = mgs_vcycle(h, &P->r, &P->C[k], 1);
+  if (rc != MGS_OK) { mgs_fgcr_plan_destroy(P); return rc; }
+  *out = P;
+  return MGS_OK;
+}
+
+int mgs_fgcr_plan_enqueue(mgs_fgcr_plan *P, mgs_vec *x, const mgs_vec *b, int iters, double tol) {
+  MGS_CHECK(P ? P->ctx : nullptr, P && x && b, MGS_ERR_INVALID, "mgs_fgcr_plan_enqueue: NULL argument");
+  mgs_ctx *ctx = P->ctx;
+  MGS_CHECK(ctx, iters >= 0, MGS_ERR_INVALID, "mgs_fgcr_plan_enqueue: iters = %d < 0", iters);
+  MGS_TRY(check_call(P, x, b, "mgs_fgcr_plan_enqueue"));
+  mgs_vec xv, bv;
+  xv.ctx = bv.ctx = ctx; xv.n = bv.n = P->n; xv.d = x->d; bv.d = b->d; xv.owns = bv.owns = false;
+  P->calls++; P->enq_iters = 0; P->wasted = 0; P->waits = 0; P->restarts = 0; P->unread = true;
+  MGS_TRY(enqueue_init(P, &xv, &bv, tol, false));
+  int k = 0;
+  for (int i = 1; i <= iters; ++i) {
+    MGS_TRY(enqueue_iteration(P, k, i, tol, false));
+    if (++k == P->restart && i < iters) { MGS_TRY(enqueue_close(P, &xv, &bv, false, i, tol, false, false)); k = 0; }   // a scheduled close: x catches up, r ← b − A·x
+  }
+  // FINAL: the open window, the projection of x (an x that no iteration followed was projected by INIT), the true residual, the status
+  MGS_TRY(enqueue_close(P, &xv, &bv, iters > 0, iters, tol, false, true));
+  MGS_HIP(ctx, hipMemcpyAsync(P->snap, P->st, sizeof(FgState), hipMemcpyDeviceToHost, ctx->stream));
+  return MGS_OK;
+}
+
+int mgs_fgcr_plan_result(mgs_fgcr_plan *P, int *iters_done, double *resid, double *recursive_resid, int *status) {
+  MGS_CHECK(P ? P->ctx : nullptr, P, MGS_ERR_INVALID, "mgs_fgcr_plan_result: NULL plan");
+  mgs_ctx *ctx = P->ctx;
+  MGS_CHECK(ctx, P->calls > 0, MGS_ERR_STATE, "mgs_fgcr_plan_result: nothing has been solved or enqueued");
+  if (P->unread) {
+    MGS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    P->res_it = P->snap->it; P->res_status = P->snap->status; P->res_resid = P->snap->true_resid; P->res_rec = P->snap->resid; P->wasted = P->snap->wasted;
+    P->unread = false;
+  }
+  if (iters_done) *iters_done = P->res_it;
+  if (resid) *resid = P->res_resid;
+  if (recursive_resid) *recursive_resid = P->res_rec;
+  if (status) *status = P->res_status;
+  return MGS_OK;
+}
+
+int mgs_fgcr_plan_info(const mgs_fgcr_plan *P, int64_t out[6]) {
+  MGS_CHECK(P ? P->ctx : nullptr, P && out, MGS_ERR_INVALID, "mgs_fgcr_plan_info: NULL argument");
+  out[0] = P->bytes; out[1] = P->calls; out[2] = P->enq_iters; out[3] = P->wasted; out[4] = P->waits; out[5] = P->restarts;
+  return MGS_OK;
+}
+
+int mgs_fgcr_plan_solve(mgs_fgcr_plan *P, mgs_vec *x, const mgs_vec *b, int ahead, int *max_iter, double *tol, int *status) {
+  MGS_CHECK(P ? P->ctx : nullptr, P && x && b && max_iter && tol && status, MGS_ERR_INVALID, "mgs_fgcr_plan_solve: NULL argument");
+  mgs_ctx *ctx = P->ctx;
+  MGS_CHECK(ctx, ahead >= 0, MGS_ERR_INVALID, "mgs_fgcr_plan_solve: ahead = %d < 0", ahead);
+  MGS_TRY(check_call(P, x, b, "mgs_fgcr_plan_solve"));
+  const int n = P->n, R = P->restart;
+  mgs_vec xv, bv;
+  xv.ctx = bv.ctx = ctx; xv.n = bv.n = n; xv.d = x->d; bv.d = b->d; xv.owns = bv.owns = false;
+  P->calls++; P->enq_iters = 0; P->wasted = 0; P->waits = 0; P->restarts = 0; P->unread = false;
+  const int maxit = *max_iter;
+  const double tl = *tol;
+  const int win = std::min(ahead, RING - 2);          // at most win + 1 posts of iterations are outstanding
+  struct Out { int it; unsigned long long seq; };
+  std::deque<Out> outq;                               // enqueued, outcome not seen yet
+  Look L = {0, ST_RUNNING, 0, 0, WHY_NONE, 0.0};
+  int r_it = 0, r_status = 1; double r_resid = 0.0;   // what the call returns
+  MGS_TRY(enqueue_init(P, &xv, &bv, tl, true));
+  outq.push_back({0, P->seq});
+  {
+    int next = 1, k = 0, seen = -1;                   // next iteration to enqueue and its window slot; outcomes are known through iteration `seen` (0: INIT)
+    for (;;) {
+      while (next <= maxit && next - 1 - win <= seen) {
+        // the iteration that fills its window closes it and posts from WIN; the last iteration of all posts from RES and the host closes behind
+        // its look: that close projects x, which no iteration run on speculation may do twice
+        const bool closing = k == R - 1 && next < maxit;
+        MGS_TRY(enqueue_iteration(P, k, next, tl, !closing));
+        if (closing) MGS_TRY(enqueue_close(P, &xv, &bv, false, next, tl, true, false));
+        outq.push_back({next, P->seq});
+        ++next; k = closing ? 0 : k + 1;
+      }
+      // the outcome the next enqueue waits for; with nothing left to enqueue, the last one (a freeze is sticky: every later post shows it)
+      const int need = next <= maxit ? std::max(next - 1 - win, outq.front().it) : outq.back().it;
+      while (outq.front().it < need) outq.pop_front();
+      MGS_TRY(wait_post(P, outq.front().seq, &L));
+      outq.pop_front();
+      seen = need;
+      if (!L.frozen) {
+        if (seen < maxit) continue;
+        if (seen == 0) { r_it = 0; r_resid = L.resid; r_status = 1; break; }      // *max_iter <= 0: nothing has touched x since INIT projected it
+        // the iterations are used up: x catches up (projected), the true residual decides between 0 and 1
+        MGS_TRY(enqueue_close(P, &xv, &bv, true, maxit, tl, true, false));
+        MGS_TRY(wait_post(P, P->seq, &L));
+        r_it = maxit; r_resid = L.resid; r_status = (L.frozen && L.status == ST_OK) ? 0 : 1;
+        break;
+      }
+      // frozen at iteration L.it: nothing enqueued behind it has changed x, r or the open window
+      outq.clear();
+      r_it = L.it;
+      if (L.why == WHY_INIT) { r_resid = L.resid; r_status = 0; break; }      // `<=` at iteration 0: x (projected by INIT) stays as it is
+      if (L.why == WHY_TRUE) {                       // a full window's true residual is below tol: x ← Πx behind it, as fin() does
+        if (P->ns) MGS_TRY(k_project_const(ctx, n, xv.d));
+        r_resid = L.resid; r_status = 0;
+        break;
+      }
+      // the recursion says converged, or a breakdown: close (a no-op if a scheduled close has run already), x ← Πx, the true residual decides
+      const int why = L.why;
+      MGS_TRY(enqueue_close(P, &xv, &bv, true, L.it, tl, true, false));
+      MGS_TRY(wait_post(P, P->seq, &L));
+      r_resid = L.resid;
+      if (why == WHY_BREAKDOWN) { r_status = L.status == ST_OK ? 0 : 2; break; }
+      if (L.status == ST_OK) { r_status = 0; break; }
+      // the recursion had drifted: r holds the true residual, go on from it with an empty window (mgs_fgcr's restart_now)
+      P->restarts++;
+      r_status = 1;
+      if (r_it >= maxit) break;
+      MGS_TRY(step(P, STEP_RESUME, 0, r_it, 0.0, false));
+      next = r_it + 1; seen = r_it; k = 0;
+      L.frozen = 0;
+    }
+  }
+  MGS_HIP(ctx, hipMemcpyAsync(P->snap, P->st, sizeof(FgState), hipMemcpyDeviceToHost, ctx->stream));
+  MGS_TRY(mgs_sync(ctx));
+  P->wasted = P->snap->wasted;
+  *max_iter = r_it; *tol = r_resid; *status = r_status;
+  P->res_it = r_it; P->res_status = r_status; P->res_resid = r_resid; P->res_rec = P->snap->resid;
+  return MGS_OK;
+}

@@ -31,6 +31,9 @@ def main(argv=None):
                          "device, one host look per iteration) that keeps N iterations enqueued beyond the last outcome seen; same result as without "
                          "the flag; single GPU only")
     ap.add_argument("--kcycle", type=int, default=0)
+    ap.add_argument("--fgcr-ahead", type=int, default=None, metavar="N",
+                    help="--solver fgcr: solve through an FgcrPlan (coefficients stay on the device, one host look per iteration) that keeps N iterations "
+                         "enqueued beyond the last outcome seen; same result as without the flag; single GPU only")
     ap.add_argument("--kcycle-energy", action="store_true", help="K-cycle coefficients from energy inner products (flexible-CG form; symmetric positive definite operators only)")
     ap.add_argument("--omega", type=float, default=0.6)
     ap.add_argument("--nu1", type=int, default=1)
@@ -52,6 +55,8 @@ def main(argv=None):
         raise SystemExit("multi-GPU: --nullspace is a single-GPU option (row shards carry no null-space declaration)")
     if args.ahead is not None and (args.solver not in ("pcg", "bicgstab") or world > 1 or args.ahead < 0):
         raise SystemExit("--ahead N (N >= 0) goes with --solver pcg or --solver bicgstab, named explicitly, on a single GPU")
+    if args.fgcr_ahead is not None and (args.solver != "fgcr" or world > 1 or args.fgcr_ahead < 0):
+        raise SystemExit("--fgcr-ahead N (N >= 0) goes with --solver fgcr on a single GPU")
     if args.solver is None:
         args.solver = "bicgstab"
     if world > 1:
@@ -80,9 +85,11 @@ def main(argv=None):
         plan = None                                                                         # allocations and the cycles' capture: outside the timer
         if args.ahead is not None:
             plan = mg.PcgPlan(A, h, args.pcg_flexible) if args.solver == "pcg" else mg.BicgstabPlan(A, h)
+        if args.fgcr_ahead is not None:
+            plan = mg.FgcrPlan(A, h, 10)
         ctx.sync(); t0 = time.perf_counter()
         if plan is not None:
-            st, it, tol = plan.solve(x, b, args.max_iter, args.tol, args.ahead)
+            st, it, tol = plan.solve(x, b, args.max_iter, args.tol, args.ahead if args.fgcr_ahead is None else args.fgcr_ahead)
         elif args.solver == "pcg":
             st, it, tol = mg.pcg(A, x, b, h, args.max_iter, args.tol, args.pcg_flexible)
         else:

@@ -1,0 +1,137 @@
+"""fgcr_ref: a restatement of mgs_fgcr's host loop (multigridsolver_amd/csrc/mgs_api.hip) in plain float64 numpy, with the scalar operations in
+the host's order: the window of directions c_k = M·r, v_k = A·c_k orthogonalised against the v_j of the window with U_jk = h_j/ρ_j (0 where ρ_j is
+0), α_k = t/ρ_k, r ← 1.0·r + (−α_k)·v_k, the back substitution (I + U)·y = α and x ← x − Σ (−y_j)·c_j when a window closes, the true residual at
+every close, status 0 only on the true residual, the restart of the window from the true residual when the recursion had drifted, `<=` at
+iteration 0 and `<` later, and the write-back of every path.
+
+→ (status, iterations, resid, x, restarts): `iterations` is what *max_iter holds on return, `restarts` counts the restarts from the true residual
+after a drifted convergence.  `A` is an oracle_py.Csr, a dense array or a callable v -> A·v; `precond` a callable v -> M·v or None for the identity;
+project=True declares the constant null space (Π = I − 1·1ᵀ/n where mgs_fgcr projects)."""
+import numpy as np
+
+
+def _dot(a, b):
+    return np.float64(a @ b)      # a numpy scalar: x/0 gives ±inf or NaN as on the device, where a Python float would raise
+
+
+def _spmv_of(A):
+    if callable(A):
+        return A
+    if isinstance(A, np.ndarray):
+        return lambda v: A @ v
+    return A.spmv
+
+
+def proj(v):
+    return v - np.float64(v.sum() / v.shape[0])
+
+
+def maxpy(x, ws, cfs):
+    """maxpy_dot2_kernel's expression: z = x, then z −= cf_j·w_j for j in order"""
+    z = np.array(x, copy=True)
+    for w, cf in zip(ws, cfs):
+        z = z - cf * w
+    return z
+
+
+def back_substitute(alpha, U, m):
+    """close_window: (I + U)·y = α over the m directions of the open window"""
+    y = [np.float64(0.0)] * m
+    for k in range(m - 1, -1, -1):
+        s = alpha[k]
+        for q in range(k + 1, m):
+            s = s - U[k][q] * y[q]
+        y[k] = s
+    return y
+
+
+def fgcr_ref(A, b, precond=None, restart=10, tol=1e-6, max_iter=1000, x0=None, project=False):
+    spmv = _spmv_of(A)
+    M = (lambda v: np.array(v, copy=True)) if precond is None else precond
+    b = np.ascontiguousarray(b, dtype=np.float64)
+    n = b.shape[0]
+    x = np.zeros(n) if x0 is None else np.array(x0, dtype=np.float64)
+    restarts = 0
+    with np.errstate(all="ignore"):
+        if project:
+            pb = proj(b); normb = np.sqrt(_dot(pb, pb))
+        else:
+            normb = np.sqrt(_dot(b, b))
+        if normb == 0.0:
+            normb = np.float64(1.0)
+        st = {"x": x, "x_mean": project, "r": None}
+
+        def true_residual(last):
+            if last and st["x_mean"]:
+                st["x"] = proj(st["x"]); st["x_mean"] = False
+            r = b - spmv(st["x"])
+            if project:
+                r = proj(r)
+            st["r"] = r
+            return np.sqrt(_dot(r, r)) / normb
+
+        def fin():
+            if st["x_mean"]:
+                st["x"] = proj(st["x"]); st["x_mean"] = False
+
+        C = [None] * restart; V = [None] * restart
+        rho = [np.float64(0.0)] * restart; alpha = [np.float64(0.0)] * restart
+        U = [[np.float64(0.0)] * restart for _ in range(restart)]
+
+        def close_window(m):
+            if m <= 0:
+                return
+            st["x_mean"] = project
+            y = back_substitute(alpha, U, m)
+            st["x"] = maxpy(st["x"], C[:m], [-y[q] for q in range(m)])
+
+        resid = true_residual(True)
+        if resid <= tol:
+            return 0, 0, resid, st["x"], restarts
+        it = 0
+        while it < max_iter:
+            m = 0
+            restart_now = False
+            k = 0
+            while k < restart and it < max_iter and not restart_now:
+                r = st["r"]
+                C[k] = M(r)
+                if project:
+                    C[k] = proj(C[k])
+                V[k] = spmv(C[k])
+                if k == 0:
+                    d0, d1 = _dot(V[0], V[0]), _dot(V[0], r)
+                else:
+                    hj = [_dot(V[k], V[j]) for j in range(k)]
+                    for j in range(k):
+                        U[j][k] = hj[j] / rho[j] if rho[j] != 0.0 else np.float64(0.0)
+                    V[k] = maxpy(V[k], V[:k], [U[j][k] for j in range(k)])
+                    d0, d1 = _dot(V[k], V[k]), _dot(V[k], r)
+                rho[k] = d0
+                it += 1; m = k + 1
+                if rho[k] == 0.0:
+                    alpha[k] = np.float64(0.0)
+                    close_window(m)
+                    resid = true_residual(True)
+                    fin()
+                    return (0 if resid < tol else 2), it, resid, st["x"], restarts
+                alpha[k] = d1 / rho[k]
+                st["r"] = 1.0 * r + (-alpha[k]) * V[k]
+                resid = np.sqrt(_dot(st["r"], st["r"])) / normb
+                if resid < tol:
+                    close_window(m); m = 0
+                    resid = true_residual(True)
+                    if resid < tol:
+                        fin()
+                        return 0, it, resid, st["x"], restarts
+                    restart_now = True
+                    restarts += 1
+                k += 1
+            if m:
+                close_window(m)
+                resid = true_residual(it >= max_iter)
+                if resid < tol:
+                    fin()
+                    return 0, it, resid, st["x"], restarts
+        fin()
+        return (0 if resid < tol else 1), it, resid, st["x"], restarts
