@@ -179,6 +179,38 @@ int mgs_csr_poisson2d(mgs_ctx *ctx, int n, mgs_csr **out);
 int mgs_csr_transpose(const mgs_csr *A, mgs_csr **out);
 /* A_c = PᵀAP (bicg.cpp:33).  Runs on device.                                          */
 int mgs_csr_galerkin(const mgs_csr *A, const mgs_xfer *P, mgs_csr **out);
+/* ---- sparse products on the device ----
+ * Nearest reference line: bicg.cpp:32-33, the Eigen products `Ptrans * A * P`; a product of two caller-supplied matrices has no other
+ * reference counterpart.  mgs_csr_galerkin with a P that is not a 0/1 aggregation is (Pᵀ·A)·P through these kernels.
+ * mgs_csr_spgemm — C = A·B for A (m × k) and B (k × n) of one context.  C is an ordinary matrix, indistinguishable from an uploaded one
+ * (launch plan, mgs_csr_optimize, hierarchies, mgs_csr_update_values*).  The pattern is structural: a product that is 0 and sums that
+ * cancel stay entries (the pattern is what mgs_hier_refresh keys on); columns come out ascending inside a row; rows without products
+ * are empty.  The work is enqueued on the context's stream and the call synchronises before it returns, as mgs_csr_upload does (it
+ * needs counts on the host).
+ * Arithmetic, which makes the result bit-reproducible and restatable on a host: row i of C visits the entries (i, l) of A in storage
+ * order and for each the entries (l, j) of B in storage order; every product a_il·b_lj is rounded once (no fused multiply-add); the first
+ * product that reaches column j is stored — a lone -0.0 stays -0.0 — and every later one is added to it, in the order met.  No atomics
+ * on values: two identical calls give identical bits.
+ * MGS_ERR_INVALID, with a message: a NULL argument; different contexts; A->cols != B->rows; a row shard as either factor (cols > rows on
+ * a matrix generated as a plane range by mgs_csr_poisson3d or living in a context that sums over ranks: its halo columns are not a
+ * product the library can interpret); more than 2^31 - 1 entries in C; a row of C with more than MGS_SPGEMM_MAX_ROW distinct columns
+ * (the message names the lowest such row) — a documented limit like MGS_COO_MAX_ROW: such a row is collected by one workgroup in a
+ * 16384-slot hash table in 64 KB of LDS, kept at most half full.  On failure nothing is written to *C and everything the call
+ * allocated is released.
+ * mgs_csr_spgemm_numeric — the values of C again, in place, from the current values of A and B (mgs_csr_update_values*).  Precondition:
+ * A and B have the patterns they had when C was built.  It runs the product's own numeric pass, so the bits are those of a fresh
+ * mgs_csr_spgemm; C's arrays do not move, so hierarchies built on C and their cached graphs stay valid (follow with
+ * mgs_hier_refresh); no allocation, scan or count pass.  misses == NULL: enqueued on the context's stream with no host wait.
+ * misses given: the call synchronises and writes the number of products whose column is not in C's pattern; MGS_ERR_STATE when that
+ * number is not 0 (C's values are then unspecified).  MGS_ERR_INVALID: a NULL matrix; different contexts; a row shard; shapes that do
+ * not fit C; a C that mgs_csr_spgemm did not build; a value-carrying pattern code on C (option "valcode").
+ * mgs_csr_spgemm_info — diagnostics: out[0] rows handled by the lane-per-row kernel (at most 64 products), out[1] rows handled by the
+ * workgroup-per-row kernel, out[2] longest row of C, out[3] the largest per-row product count, the sum over the row's entries (i, l)
+ * of the length of B's row l.  All four are 0 for a matrix that was not built by a product.  MGS_ERR_INVALID: NULL argument. */
+#define MGS_SPGEMM_MAX_ROW 8192   /* most distinct columns one row of C may hold */
+int mgs_csr_spgemm(const mgs_csr *A, const mgs_csr *B, mgs_csr **C);
+int mgs_csr_spgemm_numeric(const mgs_csr *A, const mgs_csr *B, mgs_csr *C, int64_t *misses);
+int mgs_csr_spgemm_info(const mgs_csr *C, int64_t out[4]);
 
 /* -------------------------------------------------------------------- device vectors */
 /* Eigen::VectorXd on the device (bicg.cpp:153-162).                                    */

@@ -20,6 +20,7 @@ COARSE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p)
 HALO_FUSED_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int)
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, c_dbl_p, C.c_int)
 P2P_HANDLE_BYTES = 96          # MGS_P2P_HANDLE_BYTES
+MGS_SPGEMM_MAX_ROW = 8192      # most distinct columns one row of a product may hold
 
 # name -> (restype, argtypes); every symbol declared in include/mgs.h
 PROTOTYPES = {
@@ -86,6 +87,9 @@ PROTOTYPES = {
     "mgs_csr_poisson2d": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     "mgs_csr_transpose": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "mgs_csr_galerkin": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "mgs_csr_spgemm": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "mgs_csr_spgemm_numeric": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_i64_p]),
+    "mgs_csr_spgemm_info": (C.c_int, [C.c_void_p, c_i64_p]),
     "mgs_vec_create": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]),
     "mgs_vec_wrap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]),
     "mgs_vec_destroy": (C.c_int, [C.c_void_p]),

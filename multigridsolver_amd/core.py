@@ -8,6 +8,7 @@ import numpy as np
 from ._lib import ALLREDUCE_FN, HALO_FN, HALO_FUSED_FN, MgsError, check, lib
 
 OP_SPMV, OP_RESIDUAL, OP_JACOBI = 0, 1, 2
+_check = check      # for methods whose own argument is called `check`
 
 
 def _ip(a):
@@ -307,6 +308,33 @@ class Csr:
 
     def galerkin(self, xfer):
         h = C.c_void_p(); check(lib().mgs_csr_galerkin(self.h, xfer.h, C.byref(h)), self.ctx.h); return Csr(self.ctx, h)
+
+    def matmul(self, B):
+        """C = self·B on the device (mgs_csr_spgemm): structural pattern, ascending columns, products summed in storage order"""
+        if not isinstance(B, Csr):
+            raise TypeError(f"matmul: a Csr expected, got {type(B).__name__}")
+        h = C.c_void_p(); check(lib().mgs_csr_spgemm(self.h, B.h, C.byref(h)), self.ctx.h); return Csr(self.ctx, h)
+
+    def __matmul__(self, B):
+        return self.matmul(B) if isinstance(B, Csr) else NotImplemented
+
+    def matmul_update(self, A, B, check=False):
+        """this matrix = A.matmul(B) built earlier: its values again, in place, from the current values of A and B with their patterns
+        unchanged (mgs_csr_spgemm_numeric); returns self.  check=False: enqueued, no host wait.  check=True: synchronises and raises
+        MgsError (MGS_ERR_STATE, .misses set) when products fall outside this matrix's pattern.  Follow with Hierarchy.refresh()."""
+        if not check:
+            _check(lib().mgs_csr_spgemm_numeric(A.h, B.h, self.h, None), self.ctx.h); return self
+        m = C.c_int64(-1)
+        try:
+            _check(lib().mgs_csr_spgemm_numeric(A.h, B.h, self.h, C.byref(m)), self.ctx.h)
+        except MgsError as e:
+            e.misses = int(m.value)
+            raise
+        return self
+
+    def spgemm_info(self):
+        out = (C.c_int64 * 4)(); check(lib().mgs_csr_spgemm_info(self.h, out), self.ctx.h)
+        return dict(zip(["lane_rows", "workgroup_rows", "max_row_len", "max_row_products"], [int(v) for v in out]))
 
     def spmv(self, x, y=None):
         y = y or Vec(self.ctx, self.shape[0])

@@ -171,6 +171,19 @@ class DeviceMatrix {
     if (!same) throw Error(MGS_ERR_INVALID, "DeviceMatrix::update_values: the sparsity pattern differs from the uploaded matrix's");
     check(mgs_csr_update_values(a_.get(), A.val.data(), nnz), context());
   }
+  // C = (*this)·B on the device (mgs.h: mgs_csr_spgemm; the Eigen products of bicg.cpp:32-33): structural pattern, ascending columns,
+  // products summed in storage order.  multiplyUpdate: this matrix is A.multiply(B) built earlier — its values again, in place, from
+  // the current values of A and B with their patterns unchanged (mgs_csr_spgemm_numeric).  Without `misses` the call is enqueued
+  // only; with it the call synchronises, writes the number of products outside this matrix's pattern and throws Error(MGS_ERR_STATE)
+  // when that is not 0.
+  DeviceMatrix multiply(const DeviceMatrix &B) const {
+    mgs_csr *p = nullptr;
+    check(mgs_csr_spgemm(a_.get(), B.a_.get(), &p), context());
+    return adopt(p, rows_, B.cols_);
+  }
+  void multiplyUpdate(const DeviceMatrix &A, const DeviceMatrix &B, int64_t *misses = nullptr) {
+    check(mgs_csr_spgemm_numeric(A.a_.get(), B.a_.get(), a_.get(), misses), context());
+  }
   Vector operator*(const Vector &x) const {            // bicg.cpp:57,82,107,117
     Vector y(rows_); check(mgs_spmv(a_.get(), x.handle(), y.out()), context()); return y;
   }

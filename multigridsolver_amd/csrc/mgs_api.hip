@@ -420,6 +420,7 @@ int mgs_csr_destroy(mgs_csr *A) {
   if (A->blkptr) mgs_hip_free(A->blkptr);
   if (A->origin) mgs_hip_free(A->origin);
   mgs_free_rowcode(A->code);
+  mgs_free_spgemm(A->spg);
   delete A;
   return MGS_OK;
 }
@@ -433,7 +434,11 @@ int mgs_csr_rowcode_info(const mgs_csr *A, int64_t out[4]) {
   out[2] = A->code ? A->code->tab_total : 0; out[3] = A->code ? A->code->tab_cap : 0;
   return MGS_OK;
 }
-int mgs_csr_poisson3d(mgs_ctx *ctx, int N, int plane_lo, int plane_hi, int local_cols, mgs_csr **out) { return k_poisson3d(ctx, N, plane_lo, plane_hi, local_cols, out); }
+int mgs_csr_poisson3d(mgs_ctx *ctx, int N, int plane_lo, int plane_hi, int local_cols, mgs_csr **out) {
+  MGS_TRY(k_poisson3d(ctx, N, plane_lo, plane_hi, local_cols, out));
+  (*out)->halo_cols = (*out)->cols > (*out)->rows;      // a plane range of the N³ operator: a row shard
+  return MGS_OK;
+}
 int mgs_csr_poisson2d(mgs_ctx *ctx, int n, mgs_csr **out) { return k_poisson2d(ctx, n, out); }
 int mgs_csr_transpose(const mgs_csr *A, mgs_csr **out) { return k_transpose(A, out); }
 // declared null space: a word on the matrix that hierarchies (finalize / refresh) and the Krylov solvers read; nothing is verified here
@@ -491,6 +496,10 @@ int mgs_csr_galerkin(const mgs_csr *A, const mgs_xfer *T, mgs_csr **out) {
   MGS_CHECK(A->ctx, T->n_fine == A->rows && A->rows == A->cols, MGS_ERR_INVALID, "galerkin: A is %d x %d, P has %d rows", A->rows, A->cols, T->n_fine);
   return T->aggregation ? k_galerkin_agg(A, T, out) : k_galerkin_general(A, T, out);
 }
+// sparse products on the device (spgemm.hip)
+int mgs_csr_spgemm(const mgs_csr *A, const mgs_csr *B, mgs_csr **C) { return k_spgemm(A, B, C); }
+int mgs_csr_spgemm_numeric(const mgs_csr *A, const mgs_csr *B, mgs_csr *C, int64_t *misses) { return k_spgemm_numeric(A, B, C, misses); }
+int mgs_csr_spgemm_info(const mgs_csr *C, int64_t out[4]) { return k_spgemm_info(C, out); }
 
 // ------------------------------------------------------------------ vectors
 int mgs_vec_create(mgs_ctx *ctx, int64_t n, mgs_vec **out) {

@@ -139,7 +139,12 @@ struct mgs_csr {
   int64_t coo_ntrip = 0;
   int coo_max_row = 0;      // most triples one row received
   int nullspace = MGS_NULLSPACE_NONE;   // mgs_csr_set_nullspace: what the caller declared (hierarchies and Krylov solvers act on it)
+  struct mgs_spgemm_plan *spg = nullptr;   // matrices built by mgs_csr_spgemm (spgemm.hip; owned): the row bins its numeric pass launches over
+  bool halo_cols = false;   // generated as a row shard (mgs_csr_poisson3d on a plane range): the columns beyond the rows are halo columns
 };
+// a row shard as far as the library can tell: more columns than rows AND generated as a shard or living in a context that sums over ranks
+// (a rectangular matrix of a single-process context is just a rectangular matrix)
+static inline bool mgs_csr_is_shard(const mgs_csr *A) { return A->cols > A->rows && (A->halo_cols || A->ctx->allreduce || A->ctx->ncomm); }
 constexpr int MGS_RB = 256;   // rows per row block of the row-block kernels (kernels_spmv.hip) == their threads per workgroup
 static inline int mgs_row_blocks(const mgs_csr *A) { return (A->rows + MGS_RB - 1) / MGS_RB; }
 
@@ -453,6 +458,11 @@ int k_csr_from_device(mgs_ctx *ctx, int rows, int cols, int64_t nnz, const void 
 int k_csr_from_coo_device(mgs_ctx *ctx, int rows, int cols, int64_t ntrip, const void *row_dev, const void *col_dev, int index_bits, const void *val_dev, int keep_map,
                           mgs_csr **out);
 int k_csr_update_values_coo(mgs_csr *A, const void *val_dev);
+// (spgemm.hip) C = A·B on the device, its values again for an unchanged pattern, and the general Galerkin product through them
+int k_spgemm(const mgs_csr *A, const mgs_csr *B, mgs_csr **out);
+int k_spgemm_numeric(const mgs_csr *A, const mgs_csr *B, mgs_csr *C, int64_t *misses);
+int k_spgemm_info(const mgs_csr *C, int64_t out[4]);
+void mgs_free_spgemm(struct mgs_spgemm_plan *p);
 
 // helpers (mgs_api.hip)
 int mgs_csr_alloc(mgs_ctx *ctx, int rows, int cols, int64_t nnz, mgs_csr **out);

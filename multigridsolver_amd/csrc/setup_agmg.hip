@@ -657,40 +657,7 @@ int k_galerkin_numeric(const mgs_csr *A, int nc, const int *cptr, const int *mem
   return MGS_OK;
 }
 
-// general P (not an aggregation): host Gustavson product, as the reference does with Eigen on
-// the CPU at setup (bicg.cpp:33).  Setup only — never on the solve path.
-int k_galerkin_general(const mgs_csr *A, const mgs_xfer *T, mgs_csr **out) {
-  mgs_ctx *ctx = A->ctx;
-  auto pull = [&](const mgs_csr *M, std::vector<int> &rp, std::vector<int> &ci, std::vector<double> &v) -> int {
-    rp.resize((size_t)M->rows + 1); ci.resize((size_t)M->nnz); v.resize((size_t)M->nnz);
-    return mgs_csr_download(M, rp.data(), ci.data(), v.data());
-  };
-  std::vector<int> arp, aci, prp, pci, trp, tci; std::vector<double> av, pv, tv;
-  MGS_TRY(pull(A, arp, aci, av)); MGS_TRY(pull(T->P, prp, pci, pv)); MGS_TRY(pull(T->Pt, trp, tci, tv));
-  auto spgemm = [](int n, int m, const std::vector<int> &rp1, const std::vector<int> &c1, const std::vector<double> &v1,
-                   const std::vector<int> &rp2, const std::vector<int> &c2, const std::vector<double> &v2,
-                   std::vector<int> &rpo, std::vector<int> &co, std::vector<double> &vo) {
-    std::vector<double> acc((size_t)m, 0.0); std::vector<int> mark((size_t)m, -1);
-    rpo.assign((size_t)n + 1, 0); co.clear(); vo.clear();
-    for (int i = 0; i < n; ++i) {
-      size_t base = co.size();
-      for (int ka = rp1[i]; ka < rp1[i + 1]; ++ka) {
-        int k = c1[ka]; double a = v1[ka];
-        for (int kb = rp2[k]; kb < rp2[k + 1]; ++kb) {
-          int j = c2[kb];
-          if (mark[j] != i) { mark[j] = i; co.push_back(j); acc[j] = a * v2[kb]; } else acc[j] += a * v2[kb];
-        }
-      }
-      std::sort(co.begin() + base, co.end());
-      for (size_t q = base; q < co.size(); ++q) vo.push_back(acc[co[q]]);
-      rpo[i + 1] = (int)co.size();
-    }
-  };
-  std::vector<int> r1, c1, r2, c2; std::vector<double> v1, v2;
-  spgemm(T->n_coarse, A->cols, trp, tci, tv, arp, aci, av, r1, c1, v1);
-  spgemm(T->n_coarse, T->n_coarse, r1, c1, v1, prp, pci, pv, r2, c2, v2);
-  return mgs_csr_upload(ctx, T->n_coarse, T->n_coarse, (int64_t)c2.size(), r2.data(), c2.data(), v2.data(), out);
-}
+// (general P, not an aggregation: k_galerkin_general is two device products, spgemm.hip)
 
 // the union pattern of M and Mᵀ (union_pattern_kernel) in device buffers; returns with the stream idle, so the caller may free Mᵀ
 static int union_pattern(const mgs_csr *M, const mgs_csr *Mt, DevBuf &uptr, DevBuf &ucol, DevBuf &uij, DevBuf &uji, int *unnz_out) {
