@@ -810,6 +810,11 @@ int mgs_hier_group_info(const mgs_hier *h, int level, int64_t out[4]);
  * leaves its row-block group (other entries are not written).  *nodiag (may be NULL): 1 if the pass ran on the operand without Â's
  * diagonal entries (option "pre_nodiag": coded row blocks stream val_nd and a byte per row; the result has the same bits either way).  Enqueued on the context's stream. */
 int mgs_hier_pre_pass(mgs_hier *h, int level, const mgs_vec *b, mgs_vec *t, mgs_vec *r, mgs_vec *rc, int *nodiag);
+/* Packed operand values of level `level` (option "pack7"; filled in by the first cycle): out[0] row blocks of the pre pass's operand, out[1] those of
+ * them whose slice is packed (the others read the FP64 array), out[2] which array that copy is of (0 none, 1 Â's values, 2 Â's values without the
+ * diagonal entries), out[3] whether the last launch of the level's pre pass ran the packed form of its kernel (1 / 0; −1: no launch yet),
+ * out[4] / out[5] / out[6] the same three of the post pass's operand A·P, out[7] bytes of device memory the copies take.  The host waits for the stream. */
+int mgs_hier_pack_info(mgs_hier *h, int level, int64_t out[8]);
 /* The fused post pass of level `level` alone, into the caller's vectors (tests and diagnostics): the operand, the kernel and the launch are
  * the ones the level's own cycle uses under the options as they stand — merged A·P, aggregate-mapped A (ω/a_ii from the streamed diagonal
  * with option "diag_from_values") or the gather form on A; FP64 or FP32 operand values; option "group_sweep" (whole-level launches of a grouped level).
@@ -851,7 +856,9 @@ int mgs_hier_graph_info(const mgs_hier *h, int64_t out[4]);
  * aggregate-mapped columns; default 1; equal to rounding, not bit for bit), "fuse_restrict" / "group_blocks" / "group_stray_pct" / "group_min_blocks" / "group_strip"
  * (grouped pre pass: restriction inside the pre-smoothing pass, see mgs_hier_group_info), "pre_nodiag" (the grouped pre pass of an unsharded FP64 level whose rows
  * hold exactly one diagonal entry streams Â's diagonal entry — ω up to three roundings for every row — as one byte, its distance from ω in units of the last place: 7 B per row less, +8 B of HBM per
- * off-diagonal entry and 1 B per row; default 1, the same bits as with 0), "diag_from_values", "fuse_dots", "lds_pad", "blkptr".
+ * off-diagonal entry and 1 B per row; default 1, the same bits as with 0), "pack7" (the fused passes of an unsharded FP64 level stream a packed copy of their operands' values, 7 bytes per
+ * entry — sign, three exponent bits against a base exponent per row block, 52 mantissa bits — in the coded row blocks whose values span fewer than 8 binades; +7 B of HBM per entry; the same
+ * bits as with 0; see mgs_hier_pack_info), "diag_from_values", "fuse_dots", "lds_pad", "blkptr".
  * Unknown key: MGS_ERR_INVALID. */
 int mgs_ctx_set_option(mgs_ctx *ctx, const char *key, int value);
 

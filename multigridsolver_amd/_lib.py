@@ -67,6 +67,7 @@ PROTOTYPES = {
     "mgs_csr_rowcode_info": (C.c_int, [C.c_void_p, c_i64_p]),
     "mgs_hier_graph_info": (C.c_int, [C.c_void_p, c_i64_p]),
     "mgs_hier_group_info": (C.c_int, [C.c_void_p, C.c_int, c_i64_p]),
+    "mgs_hier_pack_info": (C.c_int, [C.c_void_p, C.c_int, c_i64_p]),
     "mgs_hier_pre_pass": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
     "mgs_hier_post_pass": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
     "mgs_csr_update_values": (C.c_int, [C.c_void_p, c_dbl_p, C.c_int64]),

@@ -557,6 +557,13 @@ class Hierarchy:
         out = (C.c_int64 * 4)(); check(lib().mgs_hier_group_info(self.h, level, out), self.ctx.h)
         return dict(zip(["groups", "paired_groups", "stray_aggregates", "blocks"], [int(v) for v in out]))
 
+    def pack_info(self, level):
+        """packed operand values of one level (mgs_hier_pack_info, option pack7): blocks / packed blocks of the pre and the post pass's operand,
+        which array the pre pass's copy is of (0 none, 1 Â's values, 2 those without the diagonal entries), whether the last launch of each pass
+        ran the packed form (1 / 0, −1 before any launch), and the copies' bytes"""
+        out = (C.c_int64 * 8)(); check(lib().mgs_hier_pack_info(self.h, level, out), self.ctx.h)
+        return dict(zip(["pre_blocks", "pre_packed", "pre_source", "pre_ran", "post_blocks", "post_packed", "post_ran", "bytes"], [int(v) for v in out]))
+
     def pre_pass(self, level, b, t, r, rc):
         """the grouped pre pass of one level alone (mgs_hier_pre_pass); returns True if it ran without Â's streamed diagonal"""
         nd = C.c_int(0); check(lib().mgs_hier_pre_pass(self.h, level, b.h, t.h, r.h, rc.h, C.byref(nd)), self.ctx.h)

@@ -246,6 +246,51 @@ __global__ void drop_diag_vals_kernel(int n, const int *__restrict__ rowptr, con
   if (d < -127 || d > 127) { atomicAdd(bad, 1); d = 0; }
   code[i] = (signed char)d;
 }
+// Packed copy of an FP64 operand of the fused passes (option pack7): 7 bytes per entry, the same bits.  Row block blk owns the
+// entries [blkptr[blk] − s(blk), blkptr[blk + 1] − s(blk + 1)) of src, s(q) = 0 for an operand in CSR storage order and min(q·256, nd_rows) for
+// the operand without diagonal entries (nd_rows ≥ 0: its row i starts at rowptr[i] − i).  Pass 1: one workgroup per row block finds the block's
+// smallest biased exponent E0; e0[blk] = E0 if every entry is a normal number with exponent in [E0, E0 + 7], −1 otherwise (zero, denormal, Inf,
+// NaN, 8 binades or more, or no entry at all: such a block keeps reading src).  Pass 2: entry k goes into the 112-byte record k / 16 — sixteen
+// low dwords, sixteen 16-bit words (mantissa bits 32–47), sixteen bytes sign << 7 | (exponent − E0) << 4 | mantissa bits 48–51 — coded against
+// the E0 of the block that owns it (a record may straddle two blocks; a kernel decodes only its own block's entries).
+__device__ __forceinline__ void pack7_slice(const int *__restrict__ blkptr, int blk, int nd_rows, int &a, int &b) {
+  a = blkptr[blk]; b = blkptr[blk + 1];
+  if (nd_rows >= 0) { a -= min(blk * MGS_RB, nd_rows); b -= min((blk + 1) * MGS_RB, nd_rows); }
+}
+__global__ __launch_bounds__(MGS_RB) void pack7_scan_kernel(const int *__restrict__ blkptr, int nd_rows, const double *__restrict__ src, int *__restrict__ e0) {
+  __shared__ int s_min, s_max;
+  const int blk = blockIdx.x, tid = threadIdx.x;
+  int a, b;
+  pack7_slice(blkptr, blk, nd_rows, a, b);
+  if (tid == 0) { s_min = 0x7fffffff; s_max = -1; }
+  __syncthreads();
+  int mn = 0x7fffffff, mx = -1;
+  for (int k = a + tid; k < b; k += MGS_RB) {
+    const int ex = (int)((unsigned long long)__double_as_longlong(src[k]) >> 52) & 0x7ff;
+    mn = min(mn, ex); mx = max(mx, ex);
+  }
+  if (mx >= 0) { atomicMin(&s_min, mn); atomicMax(&s_max, mx); }
+  __syncthreads();
+  // exponent 0: zero or denormal, 2047: Inf or NaN
+  if (tid == 0) e0[blk] = (s_max >= 0 && s_min >= 1 && s_max <= 2046 && s_max - s_min <= 7) ? s_min : -1;
+}
+__global__ __launch_bounds__(MGS_RB) void pack7_fill_kernel(const int *__restrict__ blkptr, int nd_rows, const double *__restrict__ src, const int *__restrict__ e0,
+                                                             unsigned char *__restrict__ out) {
+  const int blk = blockIdx.x, tid = threadIdx.x;
+  int a, b;
+  pack7_slice(blkptr, blk, nd_rows, a, b);
+  const int E0 = e0[blk];
+  for (int k = a + tid; k < b; k += MGS_RB) {
+    const unsigned long long bits = (unsigned long long)__double_as_longlong(src[k]);
+    const unsigned hi = (unsigned)(bits >> 32);
+    const int d = E0 >= 0 ? (int)((hi >> 20) & 0x7ffu) - E0 : 0;      // a block that is not packed: its bytes are never decoded
+    unsigned char *rec = out + (size_t)112 * (size_t)(k >> 4);
+    const int i = k & 15;
+    reinterpret_cast<unsigned *>(rec)[i] = (unsigned)bits;
+    reinterpret_cast<unsigned short *>(rec + 64)[i] = (unsigned short)(hi & 0xffffu);
+    rec[96 + i] = (unsigned char)(((hi >> 31) << 7) | ((unsigned)(d & 7) << 4) | ((hi >> 16) & 15u));
+  }
+}
 __global__ void map_cols_kernel(int n, const int *__restrict__ rowptr, const int *__restrict__ col, const int *__restrict__ cmap, int *__restrict__ out) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -1058,6 +1103,14 @@ int k_diag_count(const mgs_csr *A, int *bad_count_host) {
 }
 int k_drop_diag_vals(mgs_ctx *ctx, const mgs_csr *A, const double *val, double omega, double *out, signed char *code, int *bad_dev) {
   if (A->rows) hipLaunchKernelGGL(drop_diag_vals_kernel, dim3(mgs_grid(A->rows, TB)), dim3(TB), 0, ctx->stream, A->rows, A->rowptr, A->col, val, omega, out, code, bad_dev);
+  MGS_HIP(ctx, hipGetLastError());
+  return MGS_OK;
+}
+int k_pack7(mgs_ctx *ctx, const int *blkptr, int nblocks, int nd_rows, const double *src, int *e0, unsigned char *out) {
+  if (nblocks > 0) {
+    hipLaunchKernelGGL(pack7_scan_kernel, dim3(nblocks), dim3(MGS_RB), 0, ctx->stream, blkptr, nd_rows, src, e0);
+    hipLaunchKernelGGL(pack7_fill_kernel, dim3(nblocks), dim3(MGS_RB), 0, ctx->stream, blkptr, nd_rows, src, e0, out);
+  }
   MGS_HIP(ctx, hipGetLastError());
   return MGS_OK;
 }

@@ -88,6 +88,17 @@ template <> struct val_traits<float> { typedef float4_t v16; typedef int4_t i16;
 // doubles of LDS the value region of a row block takes: capv values + what the alignment of the slice's two ends adds
 template <class VT> __host__ __device__ __forceinline__ int val_region(int capv) { return sizeof(VT) == 4 ? (capv + 8) >> 1 : capv + 2; }
 
+// Option pack7: value e of a packed slice in LDS (112-byte records of sixteen entries: low dwords, 16-bit words of mantissa bits 32–47, bytes
+// sign << 7 | (exponent − E0) << 4 | mantissa bits 48–51).  e0sh = E0 << 20.  Three LDS reads instead of one; the double is the stored one, bit for bit.
+__device__ __forceinline__ double pk7_fetch(const unsigned char *__restrict__ lds, int e, unsigned e0sh) {
+  const unsigned char *rec = lds + 112 * (e >> 4);
+  const int i = e & 15;
+  const unsigned lo = reinterpret_cast<const unsigned *>(rec)[i];
+  const unsigned mid = reinterpret_cast<const unsigned short *>(rec + 64)[i];
+  const unsigned b = rec[96 + i];
+  return __hiloint2double((int)(((b & 0x80u) << 24) + ((b & 0x7fu) << 16) + e0sh + mid), (int)lo);
+}
+
 // Workgroup → row-block map.  (1) XCD-contiguous: workgroups are dealt round-robin over the 8
 // XCDs, so XCD x = bid & 7 sweeps the x-th eighth of the row blocks.  (2) Optional strip-major
 // sweep inside an XCD for operators with a far band at ±D row blocks (the e±N² planes of the
@@ -420,7 +431,10 @@ __device__ __forceinline__ void coded_row_range(const int *__restrict__ ints, in
 // VAL: the tuples carry the values as well (`vtab`, option valcode): a coded block then streams no matrix entry at all.
 // one 256-row block of the pattern-coded kernel (the two __global__ wrappers below call it once per workgroup, or once per row block
 // of a group of blocks)
-template <int OP, int U, bool HALO, bool VAL, class VT = double>
+// PK (option pack7; RESIDUAL and the post pass on FP64 values, no halo, no value tuples): a coded + staged block whose pk_e0 entry is not −1 stages
+// its slice of the packed copy pk (7/8 as many 16-byte pieces, from the block's first entry rounded down to a multiple of 16) and fetches every
+// value through pk7_fetch; indices, products and their order are those of the FP64 walk.  Every other block reads val as before.
+template <int OP, int U, bool HALO, bool VAL, class VT = double, bool PK = false>
 __device__ __forceinline__ void coded_block_body(
     const int blk, int n, const int *__restrict__ rowptr, const int *__restrict__ idx, const VT *__restrict__ val,
     const unsigned char *__restrict__ pid, const int *__restrict__ tptr, const int *__restrict__ tab,
@@ -430,9 +444,11 @@ __device__ __forceinline__ void coded_block_body(
     const double *__restrict__ hv /*row shards: values of the indices >= split*/, int split, const double *__restrict__ vtab,
     const unsigned char *__restrict__ dpos /*t-form post pass: position of a_ii inside the row (NULL: read wd)*/,
     const double *__restrict__ dot_w1, double *__restrict__ dot_part /*SpMV: (y·w1, y·y) partials [2][nblocks] of this launch (NULL: none)*/,
-    int dot_nb, int flags /*kernel-uniform; bit 0: no row is longer than U → the gather step runs once, without a loop; bit 1: loop-free staging (option stage_unroll); bit 2: option rowptr_scan*/) {
+    int dot_nb, int flags /*kernel-uniform; bit 0: no row is longer than U → the gather step runs once, without a loop; bit 1: loop-free staging (option stage_unroll); bit 2: option rowptr_scan*/,
+    const unsigned char *__restrict__ pk = nullptr, const int *__restrict__ pk_e0 = nullptr) {
   extern __shared__ double lds_raw[];
   constexpr bool POST = OP == FUSE_POST_MAPPED;
+  static_assert(!PK || (sizeof(VT) == 8 && !HALO && !VAL && (OP == MGS_OP_RESIDUAL || POST)), "packed values: pre and post pass of an unsharded FP64 level only");
   constexpr bool F32 = sizeof(VT) == 4;      // FP32 operand values: no value tuples, no fused dots, ωD⁻¹ from wd; the code may be absent (tptr = NULL)
   constexpr int VA = val_traits<VT>::VA;
   typedef typename val_traits<VT>::v16 v16_t;
@@ -452,6 +468,14 @@ __device__ __forceinline__ void coded_block_body(
   const int nent = hi - start;
   const bool coded = tlen > 0 && tlen <= capi_abs && (!VAL || tlen <= capv);
   const bool staged = hi - lo <= capv && (coded || nent + VA - 1 <= capi_abs);     // block-uniform
+  // PK: records of the block's packed slice, and whether the block runs on it (block-uniform; the records must fit the value region)
+  int pk_nrec = 0, pk_e = -1;
+  bool packed = false;
+  if constexpr (PK) {
+    pk_nrec = ((hi + 15) >> 4) - (lo >> 4);
+    pk_e = pk_e0[blk];
+    packed = coded && staged && pk_e >= 0 && 14 * pk_nrec <= val_region<VT>(capv);
+  }
   int ga = 0, ge = 0, base = row;
   double bi = 0.0, di = 0.0, xi = 0.0, pei = 0.0;
   const bool dmode = POST && dpos != nullptr && xin == nullptr;    // ωD⁻¹ from the streamed diagonal entry (same bits as wd = ω·(1/a_ii))
@@ -484,8 +508,25 @@ __device__ __forceinline__ void coded_block_body(
   };
   double s = 0.0;
   if (staged) {
-    const int nch = (nent + VA - 1) >> (VA == 4 ? 2 : 1);      // 16-byte pieces of the value slice
-    if (coded) {
+    const int nch = (PK && packed) ? 7 * pk_nrec : (nent + VA - 1) >> (VA == 4 ? 2 : 1);      // 16-byte pieces of the value slice
+    if (PK && packed) {      // the packed slice: whole records from the block's first entry rounded down to a multiple of 16, staged like the values
+      const v16_t *__restrict__ psrc = reinterpret_cast<const v16_t *>(pk + (size_t)112 * (size_t)(lo >> 4));
+      if (nch <= 4 * RB && (flags & 2)) {
+        v16_t rr[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { const int c = tid + k * RB; if (c < nch) rr[k] = psrc[c]; }
+        int tw = 0;
+        if (tid < tlen) tw = tab[t0 + tid];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { const int c = tid + k * RB; if (c < nch) reinterpret_cast<v16_t *>(vals)[c] = rr[k]; }
+        if (tid < tlen) ints[tid] = tw;
+        for (int c = tid + RB; c < tlen; c += RB) ints[c] = tab[t0 + c];
+      } else {
+#pragma unroll 4
+        for (int c = tid; c < nch; c += RB) reinterpret_cast<v16_t *>(vals)[c] = psrc[c];
+        for (int c = tid; c < tlen; c += RB) ints[c] = tab[t0 + c];
+      }
+    } else if (coded) {
       if (VAL) { for (int c = tid; c < tlen; c += RB) vals[c] = vtab[t0 + c]; }     // value tuples instead of the value slice (tlen <= capv)
       else if (nch <= 4 * RB && (flags & 2)) {
         // No loop in front of the barrier: four predicated 16-byte loads per lane, all in flight together with the prologue's per-row
@@ -543,9 +584,37 @@ __device__ __forceinline__ void coded_block_body(
         };
         // rows that all fit one step (7-point operators with U = 7, A·P with U = 5): straight-line code, so the loads issued behind
         // the barrier (e_c of the own aggregate) stay in flight beside the gathers instead of being drained at a loop header
-        if ((flags & 3) == 3) step(my_a, 0);
+        if constexpr (PK) {
+          if (packed) {      // the same walk, every value through pk7_fetch (the packed slice starts at a multiple of 16 entries)
+            const unsigned char *__restrict__ pvals = reinterpret_cast<const unsigned char *>(lds_raw);
+            const int pk_sh = start - (lo & ~15);
+            const unsigned pk_e0sh = (unsigned)pk_e << 20;
+            auto step_pk = [&](const int k, const int j) {
+              int oq[U]; double xv[U], vq[U];
+#pragma unroll
+              for (int q = 0; q < U; ++q) oq[q] = ints[ps + min(j + q, last)];
+#pragma unroll
+              for (int q = 0; q < U; ++q) {
+                if (POST) {
+                  const bool neg = oq[q] == CODE_NEG;
+                  const double g = x[neg ? 0 : base + oq[q]];
+                  xv[q] = neg ? 0.0 : g;
+                } else xv[q] = x[base + oq[q]];
+              }
+#pragma unroll
+              for (int q = 0; q < U; ++q) vq[q] = pk7_fetch(pvals, min(k + q, lim) + pk_sh, pk_e0sh);
+#pragma unroll
+              for (int q = 0; q < U; ++q) s += (k + q < my_e) ? vq[q] * xv[q] : 0.0;
+            };
+            if ((flags & 3) == 3) step_pk(my_a, 0);
+            else for (int k = my_a, j = 0; k < my_e; k += U, j += U) step_pk(k, j);
+            if (POST && dmode && dp != 255) di = omega * (1.0 / pk7_fetch(pvals, my_a + (int)dp + pk_sh, pk_e0sh));
+          }
+        }
+        if (PK && packed) {}
+        else if ((flags & 3) == 3) step(my_a, 0);
         else for (int k = my_a, j = 0; k < my_e; k += U, j += U) step(k, j);
-        if (POST && dmode && dp != 255) di = omega * (1.0 / (VAL ? vals[ps + (int)dp] : vals[my_a + (int)dp]));
+        if (POST && dmode && dp != 255 && !(PK && packed)) di = omega * (1.0 / (VAL ? vals[ps + (int)dp] : vals[my_a + (int)dp]));
       } else {
         for (int k = my_a; k < my_e; k += U) {
           int cq[U]; double xv[U], vq[U];
@@ -597,7 +666,8 @@ __device__ __forceinline__ void coded_block_body(
   }
 }
 
-#define CODED_PARAMS                                                                                                                    \
+#define CODED_PARAMS CODED_PARAMS_T(VT)
+#define CODED_PARAMS_T(VT)                                                                                                              \
     int n, const int *__restrict__ rowptr, const int *__restrict__ idx, const VT *__restrict__ val,                                      \
     const unsigned char *__restrict__ pid, const int *__restrict__ tptr, const int *__restrict__ tab, const double *__restrict__ x,      \
     const double *__restrict__ b, const double *__restrict__ dinv, double omega, const double *__restrict__ xin,                         \
@@ -613,6 +683,15 @@ __global__ __launch_bounds__(RB, OP == FUSE_POST_MAPPED ? 8 : 1) void csr_rowblo
   const int vb = map_block(bm, blockIdx.x);
   if (vb < 0) return;
   coded_block_body<OP, U, HALO, VAL, VT>(block_of(bm, vb), CODED_ARGS);
+}
+// the packed form (option pack7): the same body with PK, and the packed copy behind the parameters of the form above
+// (the post pass with U = 7 / 8 needs more than the 64 registers of eight waves per SIMD: unbounded there, instead of a bound that spills)
+template <int OP, int U>
+__global__ __launch_bounds__(RB, OP == FUSE_POST_MAPPED && U <= 5 ? 8 : 1) void csr_rowblock_coded_pk_kernel(CODED_PARAMS_T(double), const unsigned char *__restrict__ pk,
+                                                                                                  const int *__restrict__ pk_e0) {
+  const int vb = map_block(bm, blockIdx.x);
+  if (vb < 0) return;
+  coded_block_body<OP, U, false, false, double, true>(block_of(bm, vb), CODED_ARGS, pk, pk_e0);
 }
 // the same row blocks swept group by group (descriptors of the grouped pre pass: up to GRP_BLOCKS blocks per workgroup, one after the
 // other) — experiment: does the post pass gain what the grouped pre pass gains from fewer, fatter workgroups?
@@ -935,15 +1014,20 @@ __global__ void restrict_stray_kernel(int ns, const int *__restrict__ stray, con
 // value is rebuilt from omega and the row's byte of nd_code (the distance of the stored entry from omega in units of the last place, taken on
 // the bit patterns) and multiplies b_i — no LDS value, no gather — and behind it the value index is the pattern position minus one.  The rebuilt
 // value IS the stored one, so the sum keeps its bits; the other branches read val as they always did.
-template <int U, bool HALO, class VT = double, bool ND = false>
-__global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(6))) void csr_group_pre_kernel(
+// PK (option pack7; unsharded FP64 levels): a coded + staged block whose pk_e0 entry is not −1 stages its slice of the packed copy pk of the operand it
+// streams (val_nd with ND, val otherwise) and fetches its values through pk7_fetch; see coded_block_body.
+template <int U, bool HALO, class VT = double, bool ND = false, bool PK = false>
+// (PK with U = 8 needs more than the 80 registers of six waves: five there, instead of a bound that spills)
+__global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(PK && U == 8 ? 5 : 6))) void csr_group_pre_kernel(
     int n, const int *__restrict__ rowptr, const int *__restrict__ idx, const VT *__restrict__ val,
     const unsigned char *__restrict__ pid, const int *__restrict__ tptr, const int *__restrict__ tab,
     const double *__restrict__ x, const double *__restrict__ b, double *__restrict__ t_out, double *__restrict__ r_out,
     double *__restrict__ rc_out, const int *__restrict__ gdesc, const unsigned long long *__restrict__ acode,
     const unsigned *__restrict__ wmask, int capv, int capi, BlockMap bm, const double *__restrict__ hv, int split, int nts /*bit 0: streaming store of t; bit 1: slice staged by LDS-DMA, no loop; bit 2: option rowptr_scan*/,
-    const int *__restrict__ gorder, int gper, const double *__restrict__ val_nd, const signed char *__restrict__ nd_code, double omega) {
+    const int *__restrict__ gorder, int gper, const double *__restrict__ val_nd, const signed char *__restrict__ nd_code, double omega,
+    const unsigned char *__restrict__ pk, const int *__restrict__ pk_e0) {
   extern __shared__ double lds_raw[];
+  static_assert(!PK || (sizeof(VT) == 8 && !HALO), "packed values: unsharded FP64 levels only");
   constexpr int VA = val_traits<VT>::VA;
   typedef typename val_traits<VT>::v16 v16_t;
   typedef typename val_traits<VT>::i16 i16_t;
@@ -991,10 +1075,23 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(6))) void cs
     double s = 0.0;
     // ND, coded block: its slice of val_nd (256 entries less; r1 − r0 less in the last block)
     const int nd_start = (lo - r0) & ~1, nd_nent = (hi - r1) - nd_start;
+    // PK: the block's slice [pk_a, pk_b) of the packed operand, its records, and whether the block runs on them (block-uniform)
+    int pk_a = 0, pk_nrec = 0, pk_e = -1, pk_sh = 0;
+    bool packed = false;
+    if constexpr (PK) {
+      pk_a = ND ? lo - r0 : lo;
+      pk_nrec = (((ND ? hi - r1 : hi) + 15) >> 4) - (pk_a >> 4);
+      pk_e = pk_e0[blk];
+      packed = coded && staged && pk_e >= 0 && 14 * pk_nrec <= val_region<VT>(capv);
+      pk_sh = (ND ? nd_start : start) - (pk_a & ~15);      // the packed slice starts at a multiple of 16 entries
+    }
+    const unsigned char *__restrict__ pvals = reinterpret_cast<const unsigned char *>(lds_raw);
+    const unsigned pk_e0sh = (unsigned)pk_e << 20;
     if (staged) {
-      const int nch = (ND && coded) ? (nd_nent + 1) >> 1 : (nent + VA - 1) >> (VA == 4 ? 2 : 1);      // 16-byte pieces of the value slice
+      const int nch = (PK && packed) ? 7 * pk_nrec : ((ND && coded) ? (nd_nent + 1) >> 1 : (nent + VA - 1) >> (VA == 4 ? 2 : 1));      // 16-byte pieces of the value slice
       if (coded && nch <= 4 * RB && (nts & 2)) {          // no loop and no staging registers in front of the barrier (see coded_block_body)
-        if (ND) stage_pairs_dma(val_nd + nd_start, reinterpret_cast<double *>(vals), nch, tid);
+        if (PK && packed) stage_pairs_dma(reinterpret_cast<const double *>(pk + (size_t)112 * (size_t)(pk_a >> 4)), reinterpret_cast<double *>(vals), nch, tid);
+        else if (ND) stage_pairs_dma(val_nd + nd_start, reinterpret_cast<double *>(vals), nch, tid);
         else stage_pairs_dma(val + start, vals, nch, tid);
         int tw = 0;
         if (tid < tlen) tw = tab[t0 + tid];
@@ -1004,7 +1101,8 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(6))) void cs
         // wave drains its own before it arrives (spelled out; the compiler happens to place the same wait in front of s_barrier today)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       } else if (coded) {
-        const VT *__restrict__ src = ND ? reinterpret_cast<const VT *>(val_nd) + nd_start : val + start;
+        const VT *__restrict__ src = (PK && packed) ? reinterpret_cast<const VT *>(pk + (size_t)112 * (size_t)(pk_a >> 4))
+                                                    : (ND ? reinterpret_cast<const VT *>(val_nd) + nd_start : val + start);
 #pragma unroll 4
         for (int c = tid; c < nch; c += RB) *reinterpret_cast<v16_t *>(vals + VA * c) = *reinterpret_cast<const v16_t *>(src + VA * c);
         for (int c = tid; c < tlen; c += RB) ints[c] = tab[t0 + c];
@@ -1026,6 +1124,21 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(6))) void cs
           const int na = ga - row - nd_start, nlim = max(nd_nent - 1, 0);      // the row's first off-diagonal value in the staged slice
           int behind = 0;                                                       // 1 once the walk has passed the diagonal
           const double om = __longlong_as_double(__double_as_longlong(omega) + (long long)dc);      // Â_ii as val holds it
+          if (PK && packed) {      // the same walk, every value through pk7_fetch
+            for (int k = ga, j = 0; k < ge; k += U, j += U) {
+              int oq[U], bq[U]; double xv[U], vq[U];
+#pragma unroll
+              for (int q = 0; q < U; ++q) oq[q] = ints[ps + min(j + q, last)];
+#pragma unroll
+              for (int q = 0; q < U; ++q) { bq[q] = behind; if (oq[q] == 0) behind = 1; }
+#pragma unroll
+              for (int q = 0; q < U; ++q) xv[q] = oq[q] == 0 ? bi : x[row + oq[q]];
+#pragma unroll
+              for (int q = 0; q < U; ++q) { const double v = pk7_fetch(pvals, min(na + j + q - bq[q], nlim) + pk_sh, pk_e0sh); vq[q] = oq[q] == 0 ? om : v; }
+#pragma unroll
+              for (int q = 0; q < U; ++q) s += (k + q < ge) ? vq[q] * xv[q] : 0.0;
+            }
+          } else
           for (int k = ga, j = 0; k < ge; k += U, j += U) {
             int oq[U], bq[U]; double xv[U], vq[U];
 #pragma unroll
@@ -1042,6 +1155,19 @@ __global__ __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(6))) void cs
         } else if (coded) {
           const int ps = ints[mypid];
           const int last = my_e - my_a - 1;
+          if (PK && packed) {      // the same walk, every value through pk7_fetch (PK: no halo)
+            for (int k = my_a, j = 0; k < my_e; k += U, j += U) {
+              int oq[U]; double xv[U], vq[U];
+#pragma unroll
+              for (int q = 0; q < U; ++q) oq[q] = ints[ps + min(j + q, last)];
+#pragma unroll
+              for (int q = 0; q < U; ++q) xv[q] = x[row + oq[q]];
+#pragma unroll
+              for (int q = 0; q < U; ++q) vq[q] = pk7_fetch(pvals, min(k + q, lim) + pk_sh, pk_e0sh);
+#pragma unroll
+              for (int q = 0; q < U; ++q) s += (k + q < my_e) ? vq[q] * xv[q] : 0.0;
+            }
+          } else
           for (int k = my_a, j = 0; k < my_e; k += U, j += U) {
             int oq[U]; double xv[U], vq[U];
 #pragma unroll
@@ -1613,6 +1739,10 @@ static int launch_coded(const mgs_csr *A, const mgs_rowcode *c, int op, const in
   if (dpos) omega = A->dpos_omega;
   // group sweep (views with A->sweep set; FP64 values, plain index codes, no halo): one workgroup per row-block group of the grouped pre pass
   const bool sweep = A->sweep && !f32 && !hv && !vtab && op == FUSE_POST_MAPPED;
+  // option pack7: the view carries a packed copy of its FP64 values that is in step with them (pre pass on Â, post pass on A·P; unsharded, no value tuples)
+  mgs_pack7 *pk = A->pk7;
+  const bool packed = pk && ctx->opt_pack7 && !pk->stale && !pk->nd && c && !f32 && !hv && !vtab && !sweep && (op == MGS_OP_RESIDUAL || op == FUSE_POST_MAPPED);
+  if (pk) pk->ran = packed ? 1 : 0;
   BlockMap gbm; dim3 ggrid(1);
   if (sweep) ggrid = plan_group_map(A, A->sweep, gbm);
   // the two wrappers share CODED_PARAMS; `more`: what the group wrapper takes behind them
@@ -1630,6 +1760,9 @@ static int launch_coded(const mgs_csr *A, const mgs_rowcode *c, int op, const in
       constexpr int UU = decltype(U)::value;
       if constexpr (OP == FUSE_POST_MAPPED && !HALO && !VAL && std::is_same_v<VT, double>) {
         if (sweep) return launch(csr_rowblock_coded_group_kernel<OP, UU, false, false>, vals, ggrid, gbm, A->sweep->gdesc);
+      }
+      if constexpr ((OP == FUSE_POST_MAPPED || OP == MGS_OP_RESIDUAL) && !HALO && !VAL && std::is_same_v<VT, double>) {
+        if (packed) return launch(csr_rowblock_coded_pk_kernel<OP, UU>, vals, grid, bm, (const unsigned char *)pk->data, (const int *)pk->e0);
       }
       launch(csr_rowblock_coded_kernel<OP, UU, HALO, VAL, VT>, vals, grid, bm);
     });
@@ -1797,7 +1930,8 @@ int mgs_build_groups(mgs_ctx *ctx, const mgs_csr *A, const mgs_xfer *T, mgs_grou
 }
 
 int mgs_launch_group_pre(const mgs_csr *A, const mgs_groups *G, const mgs_xfer *T, const double *x, const double *b,
-                         double *t_out, double *r_out, double *rc_out, const double *hv, int split, const double *val_nd, const signed char *nd_code, double omega) {
+                         double *t_out, double *r_out, double *rc_out, const double *hv, int split, const double *val_nd, const signed char *nd_code, double omega,
+                         mgs_pack7 *pk) {
   mgs_ctx *ctx = A->ctx;
   if (A->rows == 0 || G->ngroups == 0) return MGS_OK;
   const mgs_rowcode *c = (use_rowcode(A, A->code, hv != nullptr) && !A->code->vtab) ? A->code : nullptr;
@@ -1813,6 +1947,9 @@ int mgs_launch_group_pre(const mgs_csr *A, const mgs_groups *G, const mgs_xfer *
   const bool pairs = G->max_blocks <= 2 && ctx->opt_group_concurrent && !f32;     // 512 threads, both blocks of a pair at once (FP64 values only)
   const bool ordered = !pairs && G->gorder && ctx->opt_group_order > 0 && ctx->opt_xcd_remap;
   if (ordered) grid = dim3(8 * G->gorder_per_xcd);
+  // option pack7: a packed copy of the operand the coded blocks stream (val_nd or Â's values), in step with it
+  const bool packed = pk && ctx->opt_pack7 && !pk->stale && pk->nd == (val_nd != nullptr) && c && !f32 && !hv && !pairs;
+  if (pk) pk->ran = packed ? 1 : 0;
   // the pair kernel's parameters are the leading ones of the one-block kernel's; `more`: what the latter takes behind them
   auto launch = [&](auto kernel, auto vals, int threads, size_t lds, auto... more) {
     hipLaunchKernelGGL(kernel, grid, dim3(threads), lds + l.pad_bytes, ctx->stream, A->rows, A->rowptr, A->col, vals, c ? c->pid : nullptr,
@@ -1825,15 +1962,15 @@ int mgs_launch_group_pre(const mgs_csr *A, const mgs_groups *G, const mgs_xfer *
       with_bool(hv != nullptr, [&](auto H) { launch(csr_group2_pre_kernel<UU, decltype(H)::value>, (const double *)A->val, 2 * RB, 2 * regions + 2 * RB * 8); });
       return;
     }
-    auto form = [&](auto H, auto ND, auto vals) {      // (HALO, ND) ∈ {(true, false), (false, true), (false, false)} for double, neither for float
-      launch(csr_group_pre_kernel<UU, decltype(H)::value, pointee_t<decltype(vals)>, decltype(ND)::value>, vals, RB,
+    auto form = [&](auto H, auto ND, auto PK, auto vals) {      // (HALO, ND) ∈ {(true, false), (false, true), (false, false)} for double, neither for float; PK without HALO, for double
+      launch(csr_group_pre_kernel<UU, decltype(H)::value, pointee_t<decltype(vals)>, decltype(ND)::value, decltype(PK)::value>, vals, RB,
              regions + (size_t)G->max_blocks * RB * 8, kernel_flags(ctx, nt_store_on(A), true), ordered ? G->gorder : nullptr, G->gorder_per_xcd,
-             val_nd, nd_code, omega);
+             val_nd, nd_code, omega, (const unsigned char *)(decltype(PK)::value ? pk->data : nullptr), (const int *)(decltype(PK)::value ? pk->e0 : nullptr));
     };
     const std::false_type no{};
-    if (f32) form(no, no, A->val32);
-    else if (hv) form(std::true_type{}, no, (const double *)A->val);
-    else with_bool(val_nd != nullptr, [&](auto ND) { form(no, ND, (const double *)A->val); });
+    if (f32) form(no, no, no, A->val32);
+    else if (hv) form(std::true_type{}, no, no, (const double *)A->val);
+    else with_bool(val_nd != nullptr, [&](auto ND) { with_bool(packed, [&](auto PK) { form(no, ND, PK, (const double *)A->val); }); });
   });
   MGS_HIP(ctx, hipGetLastError());
   if (G->nstray) {
@@ -1893,6 +2030,7 @@ int mgs_launch_fused_range(const mgs_csr *A, int which, const double *wd, const 
   if (A->val32 && (which != FUSE_POST_MAPPED || hv)) return mgs_fail(ctx, MGS_ERR_INVALID, "FP32 operand values: fused pass %d has no float form", which);
   if (A->val32 || (which == FUSE_POST_MAPPED && use_rowcode(A, A->code)))      // A is the view whose col/code are the aggregate-mapped ones
     return launch_coded(A, A->code, FUSE_POST_MAPPED, A->col, ec, bvec, wd, 0.0, xin, agg, out, grid, bm);
+  if (A->pk7) A->pk7->ran = 0;      // the gather kernel reads the FP64 values (mgs_hier_pack_info)
   const int cap = A->lds_cap;
   const size_t lds = (size_t)(cap + 2) * 12 + 16;
   with_fused_pass(which, [&](auto W) {
@@ -1922,6 +2060,7 @@ int mgs_launch_csr_op_range(const mgs_csr *A, int op, const double *x, const dou
   if (ctx->opt_spmv_variant == 7 && A->max_wave_nnz <= 4096) return launch_wave(A, op, x, b, dinv, omega, out, grid, bm);
   if (ctx->opt_spmv_variant == 0 && !ctx->opt_nontemporal && use_rowcode(A, A->code))
     return launch_coded(A, A->code, op, A->col, x, b, dinv, omega, nullptr, nullptr, out, grid, bm);
+  if (A->pk7) A->pk7->ran = 0;      // none of the kernels below reads a packed copy (mgs_hier_pack_info)
   const size_t lds = sizeof(double) * (size_t)(cap > 0 ? cap : 1);
   // lanes per row of the long-row path: next power of two ≥ mean row length, in [4,64]
   const double mean = mean_row_len(A);

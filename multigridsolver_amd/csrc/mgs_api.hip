@@ -271,6 +271,7 @@ int mgs_ctx_set_option(mgs_ctx *ctx, const char *key, int value) {
   else if (k == "stage_unroll") ctx->opt_stage_unroll = value;
   else if (k == "rowptr_scan") ctx->opt_rowptr_scan = value;
   else if (k == "pre_nodiag") ctx->opt_pre_nodiag = value;
+  else if (k == "pack7") ctx->opt_pack7 = value;
   else if (k == "kcycle_energy") ctx->opt_kcycle_energy = value;
   else if (k == "aggpre_max_rows") ctx->opt_aggpre_max_rows = value;
   else if (k == "emu_split_self") ctx->opt_emu_split_self = value;
@@ -664,6 +665,7 @@ static void level_free(mgs_level &L) {
   if (L.val_wd) mgs_hip_free(L.val_wd);
   if (L.val_nd) mgs_hip_free(L.val_nd);
   if (L.nd_code) mgs_hip_free(L.nd_code);
+  for (mgs_pack7 *p : {L.pk_hat, L.pk_ap}) if (p) { if (p->data) mgs_hip_free(p->data); if (p->e0) mgs_hip_free(p->e0); delete p; }
   if (L.val_wd32) mgs_hip_free(L.val_wd32);
   if (L.ap_val32) mgs_hip_free(L.ap_val32);
   if (L.col_agg) mgs_hip_free(L.col_agg);
@@ -719,6 +721,31 @@ static int level_refresh_f32(mgs_hier *h, mgs_level &L, bool vals_changed) {
   return MGS_OK;
 }
 
+// option pack7: (re)builds the packed copies of a level's two operands where they are missing, stale or of the wrong source; all: whatever their
+// state (mgs_hier_refresh, whose new values sit in the buffers the cached graphs know).  Allocation drops the graphs; repacking in place does not.
+static int pack7_build(mgs_hier *h, mgs_pack7 *&p, const int *blkptr, int nblocks, int64_t nent, bool nd, int nd_rows, const double *src, bool all) {
+  mgs_ctx *ctx = h->ctx;
+  if (p && (p->nd != nd || p->nent != nent || p->nblocks != nblocks)) { mgs_hip_free(p->data); mgs_hip_free(p->e0); delete p; p = nullptr; drop_graph(h); }
+  if (!p) {
+    p = new mgs_pack7();
+    p->nd = nd; p->nent = nent; p->nblocks = nblocks;
+    const size_t bytes = (size_t)112 * (size_t)((nent + 15) / 16) + 16;      // padded to a whole record
+    MGS_TRY(mgs_dev_alloc(ctx, &p->data, bytes));
+    MGS_HIP(ctx, hipMemsetAsync(p->data, 0, bytes, ctx->stream));
+    MGS_TRY(mgs_dev_alloc(ctx, &p->e0, (size_t)nblocks));
+    drop_graph(h);
+  }
+  if (p->stale || all) { MGS_TRY(k_pack7(ctx, blkptr, nblocks, nd ? nd_rows : -1, src, p->e0, p->data)); p->stale = false; }
+  return MGS_OK;
+}
+static bool level_pack7_nd(const mgs_level &L) { return L.val_nd && L.nd_code && L.nd_ok && !L.nd_stale; }      // the pre pass's copy is of val_nd
+static int level_pack7(mgs_hier *h, mgs_level &L, bool all) {
+  const bool nd = level_pack7_nd(L);
+  MGS_TRY(pack7_build(h, L.pk_hat, L.A->blkptr, mgs_row_blocks(L.A), nd ? L.A->nnz - L.A->rows : L.A->nnz, nd, L.A->rows, nd ? L.val_nd : L.val_wd, all));
+  if (L.AP && L.AP->blkptr) MGS_TRY(pack7_build(h, L.pk_ap, L.AP->blkptr, mgs_row_blocks(L.AP), L.AP->nnz, false, 0, L.AP->val, all));
+  return MGS_OK;
+}
+
 // The operands of level l's two fused passes under the options as they stand — the ONE place that chooses them (cycle_level and
 // mgs_hier_post_pass both ask here).  Setup-time operands: Â = A·diag(wd) makes the pre pass the plain residual kernel with x = b (one
 // gather per entry); A·P (or col_agg = the coarse column of every entry) lets the post pass gather e_c directly.  On a shard the halo
@@ -744,6 +771,8 @@ static void level_fused_operands(const mgs_hier *h, int l, bool halo, fused_oper
   if (merged) { Amap = *L.AP; Amap.code = L.code_ap; Amap.owns = false; }      // A·P, merged: fewer entries, wd read per row
   o.f32 = level_runs_f32(h, l) && !halo;
   if (o.f32) { Ahat.val32 = L.val_wd32; Amap.val32 = L.ap_val32; }
+  // option pack7: packed copies of the two operands' FP64 values (unsharded FP64 levels; the launchers check that a copy serves their launch)
+  if (!halo) { Ahat.pk7 = L.pk_hat; if (merged) Amap.pk7 = L.pk_ap; }
   o.operands = ctx->opt_fuse_operands && L.val_wd && (L.col_agg || merged) && (!halo || mgs_rowcode_usable(&Ahat, true));
   o.post_form = !o.operands ? 0 : (merged ? 2 : 1);
   o.grouped = ctx->opt_fuse_restrict && o.operands && L.grp && !(Ahat.code && Ahat.code->vtab);
@@ -1163,6 +1192,9 @@ int mgs_hier_refresh(mgs_hier *h) {
     if (rc == MGS_OK && L.AP) rc = k_galerkin_numeric(L.A, L.A->rows, nullptr, nullptr, L.T->agg, L.AP, h->refresh_flags + 1);
     if (rc == MGS_OK && L.val_wd && L.val_wd32) rc = k_round_vals(ctx, L.val_wd, L.val_wd32, L.A->nnz);
     if (rc == MGS_OK && L.AP && L.ap_val32) rc = k_round_vals(ctx, L.AP->val, L.ap_val32, L.AP->nnz);
+    // packed copies follow their sources, in place (a level whose nd_ok ends below streams val_wd unpacked until the next cycle's setup repacks it)
+    if (rc == MGS_OK && L.pk_hat && L.pk_hat->nd == level_pack7_nd(L)) rc = level_pack7(h, L, true);
+    else if (L.pk_hat) L.pk_hat->stale = true;
   }
   int flags[2] = {0, 0}, nd_bad = 0;
   if (rc == MGS_OK && nd_built && hipMemcpyAsync(&nd_bad, h->nd_flag, sizeof nd_bad, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = mgs_fail(ctx, MGS_ERR_HIP, "mgs_hier_refresh: flag copy failed");
@@ -1208,6 +1240,29 @@ int mgs_hier_group_info(const mgs_hier *h, int level, int64_t out[4]) {
   out[0] = G ? G->ngroups : 0; out[1] = G ? G->nblocks - G->ngroups : 0;   /* blocks merged into another block's group */ out[2] = G ? G->nstray : 0; out[3] = mgs_row_blocks(h->lev[level].A);
   return MGS_OK;
 }
+int mgs_hier_pack_info(mgs_hier *h, int level, int64_t out[8]) {
+  MGS_CHECK(nullptr, h && out, MGS_ERR_INVALID, "mgs_hier_pack_info: NULL argument");
+  mgs_ctx *ctx = h->ctx;
+  MGS_CHECK(ctx, level >= 0 && level < (int)h->lev.size(), MGS_ERR_INVALID, "mgs_hier_pack_info: level %d out of range", level);
+  const mgs_level &L = h->lev[level];
+  for (int q = 0; q < 8; ++q) out[q] = 0;
+  out[3] = out[6] = -1;
+  const mgs_pack7 *ps[2] = {L.pk_hat, L.pk_ap};
+  for (int w = 0; w < 2; ++w) {
+    const mgs_pack7 *p = ps[w];
+    if (!p) continue;
+    std::vector<int> e0((size_t)p->nblocks);
+    MGS_HIP(ctx, hipMemcpyAsync(e0.data(), p->e0, sizeof(int) * e0.size(), hipMemcpyDeviceToHost, ctx->stream));
+    MGS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    int64_t packed = 0;
+    for (int v : e0) packed += v >= 0;
+    const bool unused = p->stale || L.op_bits != 64 || ctx->opt_valcode || !ctx->opt_pack7;      // no launch reads the copy as things stand
+    out[w ? 4 : 0] = p->nblocks; out[w ? 5 : 1] = unused ? 0 : packed; out[w ? 6 : 3] = p->ran;
+    if (!w) out[2] = p->nd ? 2 : 1;
+    out[7] += (int64_t)112 * ((p->nent + 15) / 16) + 16 + (int64_t)sizeof(int) * p->nblocks;
+  }
+  return MGS_OK;
+}
 int mgs_hier_pre_pass(mgs_hier *h, int level, const mgs_vec *b, mgs_vec *t, mgs_vec *r, mgs_vec *rc, int *nodiag) {
   MGS_CHECK(nullptr, h && b && t && r && rc, MGS_ERR_INVALID, "mgs_hier_pre_pass: NULL argument");
   mgs_ctx *ctx = h->ctx;
@@ -1222,7 +1277,7 @@ int mgs_hier_pre_pass(mgs_hier *h, int level, const mgs_vec *b, mgs_vec *t, mgs_
   level_fused_operands(h, level, false, ops);
   const bool nd = level_pre_nodiag(h, L, false, ops.f32);
   if (nodiag) *nodiag = nd ? 1 : 0;
-  return mgs_launch_group_pre(&ops.Ahat, L.grp, L.T, b->d, b->d, t->d, r->d, rc->d, nullptr, L.A->rows, nd ? L.val_nd : nullptr, L.nd_code, L.nd_omega);
+  return mgs_launch_group_pre(&ops.Ahat, L.grp, L.T, b->d, b->d, t->d, r->d, rc->d, nullptr, L.A->rows, nd ? L.val_nd : nullptr, L.nd_code, L.nd_omega, ops.Ahat.pk7);
 }
 int mgs_hier_post_pass(mgs_hier *h, int level, const mgs_vec *bvec, const mgs_vec *xin, const mgs_vec *ec, mgs_vec *x, const int range[4], int64_t info[8]) {
   MGS_CHECK(nullptr, h && bvec && ec && x && info, MGS_ERR_INVALID, "mgs_hier_post_pass: NULL argument");
@@ -1539,7 +1594,7 @@ static int cycle_level(mgs_hier *h, int l, const double *b, double *x, bool zero
       if (halo) MGS_TRY(exchange_now(l, b, L.hbuf->d));
       // option pre_nodiag: an eligible FP64 level streams Â's diagonal as a byte per row (the same bits as from val_wd)
       const bool nodiag = level_pre_nodiag(h, L, halo, f32);
-      MGS_TRY(mgs_launch_group_pre(&Ahat, L.grp, L.T, b, b, L.r->d, L.tmp->d, C.b->d, hv, L.A->rows, nodiag ? L.val_nd : nullptr, L.nd_code, L.nd_omega));
+      MGS_TRY(mgs_launch_group_pre(&Ahat, L.grp, L.T, b, b, L.r->d, L.tmp->d, C.b->d, hv, L.A->rows, nodiag ? L.val_nd : nullptr, L.nd_code, L.nd_omega, Ahat.pk7));
       MGS_TRY(coarse_solve(h, l + 1, C.b->d, C.x->d));
       Amap.sweep = ops.sweep;
       return post_operand(L.r->d, nullptr);
@@ -1653,7 +1708,7 @@ static int prepare_fused(mgs_hier *h) {
       bool new_vals = false;
       if (!L.val_wd) { MGS_TRY(mgs_dev_alloc(ctx, &L.val_wd, (size_t)L.A->nnz + 4)); MGS_TRY(k_scale_vals(ctx, L.A, L.wd->d, L.val_wd)); drop_graph(h); new_vals = true; }
       else if (rescale) { MGS_TRY(k_scale_vals(ctx, L.A, L.wd->d, L.val_wd)); new_vals = true; }
-      if (new_vals) L.nd_stale = true;
+      if (new_vals) { L.nd_stale = true; if (L.pk_hat) L.pk_hat->stale = true; }
       const int ncols_c = h->lev[l + 1].A->cols;      // coarse level's local columns: its rows + its halo slots
       if (ctx->opt_merge_ap && !L.AP) {
         MGS_TRY(k_build_ap(L.A, L.T, L.cmap_ext, ncols_c, &L.AP)); drop_graph(h);
@@ -1714,6 +1769,13 @@ static int prepare_fused(mgs_hier *h) {
       L.nd_omega = L.wd_omega; L.nd_stale = false;
       if (bad) { L.nd_ok = false; drop_graph(h); }
     }
+  }
+  // Packed copies of the operands' values (option pack7), allocated behind everything above for the same reason.  Unsharded FP64 levels with an
+  // aggregation transfer; the pre pass's copy is of val_nd where the level streams that, of val_wd otherwise; the values follow their sources.
+  for (size_t l = 0; ctx->opt_fuse_operands && ctx->opt_pack7 && !ctx->opt_valcode && l + 1 < h->lev.size(); ++l) {
+    mgs_level &L = h->lev[l];
+    if (!L.val_wd || !L.T || !L.T->aggregation || L.A->cols != L.A->rows || L.nx || !L.A->blkptr || L.op_bits != 64) continue;
+    MGS_TRY(level_pack7(h, L, false));
   }
   return MGS_OK;
 }

@@ -75,6 +75,9 @@ struct mgs_ctx {
                               // two rowptr loads per row: 4 B per row less to stream (kernels_spmv.hip: coded_row_range)
   int opt_pre_nodiag = 1;     // grouped pre pass of an unsharded FP64 level: Â's diagonal entries (ω up to three roundings) are streamed as one byte per row,
                               // their distance from ω, instead of a double (7 B per row less, the same bits; 0: the kernels read val_wd as it is)
+  int opt_pack7 = 1;          // fused passes of an unsharded FP64 level: coded + staged row blocks whose values span fewer than 8 binades stream a packed
+                              // copy of the operand's values, 7 bytes per entry (sign, 3 exponent bits against a per-block base, 52 mantissa bits: the same
+                              // bits; 0: every block reads the FP64 array)
   int opt_stage_unroll = 1;   // row-block kernels stage their value slice without a loop in front of the barrier (predicated 16-byte loads / LDS-DMA): −4 … −7 % per cycle
   int opt_blas1_pairs = 1;    // ... pairs per lane of those kernels: 1 = one-shot workgroups (0: capped persistent grid, k: k pairs per lane)
   int opt_blas1_vec = 1;      // axpby / axpbypcz / update+dots move 16 B per lane with four loads per stream in flight (same per-element bits)
@@ -101,6 +104,17 @@ struct mgs_rowcode {
   int tab_max = 0, tab_cap = 0;  // largest table / LDS budget covering 98.5 % of the coded blocks (ints)
   int coded_blocks = 0, nblocks = 0;
   int64_t tab_total = 0;
+};
+
+// packed copy of an FP64 operand's values (option pack7; kernels_aux.hip: pack7_scan_kernel / pack7_fill_kernel)
+struct mgs_pack7 {
+  unsigned char *data = nullptr;   // 112-byte records of sixteen entries, padded to a whole record
+  int *e0 = nullptr;               // nblocks: base exponent of each row block's slice, −1 = the block reads the FP64 array
+  int64_t nent = 0;                // entries of the source array
+  int nblocks = 0;
+  bool nd = false;                 // the source is the operand without diagonal entries (val_nd)
+  bool stale = true;               // the source array was rebuilt since
+  int ran = -1;                    // the last launch that could have read it did (1) or did not (0); −1: none yet (mgs_hier_pack_info)
 };
 
 struct mgs_csr {
@@ -130,6 +144,7 @@ struct mgs_csr {
   double dpos_omega = 0.0;               // kernel takes ω/a_ii from the values it streams anyway instead of reading wd (8 B → 1 B per row)
   const float *val32 = nullptr;   // views of the fused passes on an FP32 level only (not owned): the values rounded to float; the kernels' float forms read
                                   // these instead of val (products widened to FP64 before they are added)
+  mgs_pack7 *pk7 = nullptr;       // views of the fused passes on an unsharded FP64 level only (not owned): the packed copy of val (option pack7)
   int *origin = nullptr;   // coarse operators built by the device setup: the finest-level row each row descends from (its aggregate's
                            // leader, chained through the levels) — the index space the matching's tie-breaks work in; NULL = identity
   // matrices assembled from device triples (ingest.hip); the map is kept on request (keep_map) for mgs_csr_update_values_coo_dev
@@ -266,6 +281,8 @@ struct mgs_level {
   double nd_omega = 0.0;             // ω that nd_code counts from
   bool nd_tried = false, nd_ok = false;   // eligibility, decided once: grouped, unsharded, every row holds exactly one diagonal entry
   bool nd_stale = false;             // val_wd was rebuilt since val_nd was
+  // option pack7: packed copies of the pre pass's operand (val_nd where the level streams it, val_wd otherwise) and of A·P's values
+  mgs_pack7 *pk_hat = nullptr, *pk_ap = nullptr;
   mgs_vec *kc1 = nullptr, *kv1 = nullptr, *kc2 = nullptr, *kv2 = nullptr, *kr = nullptr;   // K-cycle work vectors
   double *kscal = nullptr;     // K-cycle scalars (device)
   double wd_omega = 0.0;       // ω that wd was built with
@@ -371,6 +388,8 @@ int k_diag_count(const mgs_csr *A, int *bad_count_host);                        
 int k_drop_diag_vals(mgs_ctx *ctx, const mgs_csr *A, const double *val, double omega, double *out, signed char *code, int *bad_dev);
                                                                                                // out: val without each row's diagonal entry (row i from rowptr[i] − i); code[i]: that entry's distance
                                                                                                // from omega in units of the last place; rows beyond ±127 are added to *bad_dev
+int k_pack7(mgs_ctx *ctx, const int *blkptr, int nblocks, int nd_rows, const double *src, int *e0, unsigned char *out);   // packed copy of src (nd_rows >= 0: of the
+                                                                                               // operand without diagonal entries of a matrix of nd_rows rows), e0 per row block
 int k_map_cols(mgs_ctx *ctx, const mgs_csr *A, const int *cmap, int *out);                     // out_k = cmap[col_k]
 int k_concat_i32(mgs_ctx *ctx, const int *a, int na, const int *b, int nb, int *out);
 int k_tail_scatter(mgs_ctx *ctx, const double *xt, int my_off, int n_loc, const int *halo_global, int n_halo, double *x);   // x[0..n_loc) = xt[my_off..], x[n_loc+s] = xt[halo_global[s]]
@@ -390,7 +409,8 @@ void mgs_free_groups(mgs_groups *g);
 // from omega (k_drop_diag_vals); coded + staged blocks then stream these instead of val — the same bits, 7 bytes per row less
 int mgs_launch_group_pre(const mgs_csr *Ahat, const mgs_groups *G, const mgs_xfer *T, const double *x, const double *b,
                          double *t_out, double *r_out, double *rc_out, const double *hv, int split,
-                         const double *val_nd = nullptr, const signed char *nd_code = nullptr, double omega = 0.0);
+                         const double *val_nd = nullptr, const signed char *nd_code = nullptr, double omega = 0.0, mgs_pack7 *pk = nullptr);
+                         // pk: packed copy of the operand the coded + staged blocks stream (val_nd if given, Ahat->val otherwise), or NULL
 // (kernels_aux.hip)
 int k_diag_inv(const mgs_csr *A, double *dinv, int *bad_count_host);
 int k_diag_inv_async(const mgs_csr *A, double *dinv, int *bad_dev);   // no host round trip: bad rows are added to *bad_dev

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """One kernel option on/off on ONE operator and hierarchy (same process, same allocations): pattern-coded SpMV / residual / Jacobi and the
-cycle, two rounds.  usage: ab_option.py OPTION [N=512] [on=1] [off=0]"""
+cycle, three rounds.  usage: ab_option.py OPTION [N=512] [on=1] [off=0] [operator=poisson|csky3d]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import multigridsolver_amd as mg
@@ -8,8 +8,14 @@ opt = sys.argv[1]
 N = int(sys.argv[2]) if len(sys.argv) > 2 else 512
 on = int(sys.argv[3]) if len(sys.argv) > 3 else 1
 off = int(sys.argv[4]) if len(sys.argv) > 4 else 0
+kind = sys.argv[5] if len(sys.argv) > 5 else "poisson"
 ctx = mg.Context(0); n = N ** 3
-A = ctx.poisson3d(N)
+if kind == "poisson":
+    A = ctx.poisson3d(N)
+else:      # the reference's convection-diffusion family (variable coefficients, nonsymmetric)
+    from multigridsolver_amd import synthetic
+    rp, ci, v = synthetic.csky3d(N, rowsum_floor=synthetic.CSKY_ROWSUM_MARGIN)
+    A = ctx.csr(n, n, rp, ci, v); del rp, ci, v
 h = mg.Hierarchy(A, 0.6, 1, 1).coarsen(10.0, 2, 8.0, 2500, 32).finalize()
 b = ctx.vec(n).rand(seed=0); x = ctx.vec(n); y = ctx.vec(n); xs = ctx.vec(n).rand(seed=1); dinv = A.diag_inv()
 A.optimize()
