@@ -810,6 +810,27 @@ int mgs_hier_group_info(const mgs_hier *h, int level, int64_t out[4]);
  * leaves its row-block group (other entries are not written).  *nodiag (may be NULL): 1 if the pass ran on the operand without Â's
  * diagonal entries (option "pre_nodiag": coded row blocks stream val_nd and a byte per row; the result has the same bits either way).  Enqueued on the context's stream. */
 int mgs_hier_pre_pass(mgs_hier *h, int level, const mgs_vec *b, mgs_vec *t, mgs_vec *r, mgs_vec *rc, int *nodiag);
+/* The fused pre pass of level `level` alone, whichever arm the level's own cycle runs under the options as they stand, into the caller's
+ * vectors (tests and diagnostics), with a report from the launcher.  With Â_ik = fl(a_ik·fl(ω·fl(1/a_kk))): s_i = Σ_k Â_ik·b_k over row i in
+ * stored order (summed from 0, one rounding per product and per sum; an FP32 level reads float(Â_ik), widened before the product; the gather
+ * form multiplies a_ik·fl(wd_k·b_k) instead), r_i = fl(b_i − s_i), t_i = fl(b_i + r_i), rc[a] = Σ r over the aggregate's members in ascending
+ * row order, summed from 0.  The grouped arm writes t and rc, and r only on the rows of the 64-row waves that hold a member of a stray
+ * aggregate; the other three arms write r on every row and rc, and leave t untouched.
+ * info: [0] arm (0 gather form on A with wd + restriction kernel, 1 residual kernel on Â + restriction kernel, 2 aggregate-parallel kernel,
+ * 3 grouped kernel), [1] kernel (0 gather kernel, 1 pattern-coded kernel FP64, 2 the same on FP32 values, 4 slice kernel, 5 aggregate-parallel
+ * kernel, 6 grouped kernel sweeping its row blocks one after the other, 7 the 512-thread pair kernel of option "group_concurrent"), [2] gather
+ * width U, [3] the kernel's flags word (coded kernels: bit 0 no row is longer than U; slice and grouped kernel: bit 0 streaming stores; bit 1
+ * option "stage_unroll"; bit 2 option "rowptr_scan"; 0 for the gather, the pair and the aggregate-parallel kernel), [4] / [5] LDS budget of a
+ * row block in values / ints, [6] what the launched instantiation has: bit 0 FP32 values, bit 1 the operand without diagonal entries (option
+ * "pre_nodiag"), bit 2 the packed form (option "pack7"; which row blocks are packed: mgs_hier_pack_info) — the pair kernel has neither of the
+ * last two, [7] row blocks that are coded and staged, [8] row blocks staged (coded, or with their index slice), [9] row blocks that walk their
+ * rows from global memory ([7..9] from the block bounds, the pattern tables' bounds and [4] / [5], the kernels' own conditions; −1 for the
+ * aggregate-parallel kernel), [10] stray aggregates of the level (grouped arm; 0 otherwise), [11] row blocks, [12..15] 0.
+ * Served and refused as by mgs_hier_post_pass: unsharded levels with a coarser level and an aggregation transfer that run the fused passes.
+ * MGS_ERR_INVALID: NULL argument, level out of range, vectors shorter than the level / its aggregates; MGS_ERR_STATE: before
+ * mgs_hier_finalize, a general P, a sharded or value-coded level, a level that does not run the fused passes.
+ * Enqueued on the context's stream; the host waits for the block bounds behind the launch, the caller synchronizes before reading. */
+int mgs_hier_pre_pass_info(mgs_hier *h, int level, const mgs_vec *b, mgs_vec *t, mgs_vec *r, mgs_vec *rc, int64_t info[16]);
 /* Packed operand values of level `level` (option "pack7"; filled in by the first cycle): out[0] row blocks of the pre pass's operand, out[1] those of
  * them whose slice is packed (the others read the FP64 array), out[2] which array that copy is of (0 none, 1 Â's values, 2 Â's values without the
  * diagonal entries), out[3] whether the last launch of the level's pre pass ran the packed form of its kernel (1 / 0; −1: no launch yet),

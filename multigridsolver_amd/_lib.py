@@ -69,6 +69,8 @@ PROTOTYPES = {
     "mgs_hier_group_info": (C.c_int, [C.c_void_p, C.c_int, c_i64_p]),
     "mgs_hier_pack_info": (C.c_int, [C.c_void_p, C.c_int, c_i64_p]),
     "mgs_hier_pre_pass": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    # info[16]: arm, kernel, U, flags, capv, capi, bits (1 FP32, 2 no diagonal, 4 packed), blocks coded / staged / global, strays, blocks (mgs.h)
+    "mgs_hier_pre_pass_info": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
     "mgs_hier_post_pass": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
     "mgs_csr_update_values": (C.c_int, [C.c_void_p, c_dbl_p, C.c_int64]),
     "mgs_csr_update_values_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),

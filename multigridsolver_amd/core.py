@@ -569,6 +569,21 @@ class Hierarchy:
         nd = C.c_int(0); check(lib().mgs_hier_pre_pass(self.h, level, b.h, t.h, r.h, rc.h, C.byref(nd)), self.ctx.h)
         return bool(nd.value)
 
+    PRE_PASS_INFO = ["arm", "kernel", "U", "flags", "capv", "capi", "bits", "blocks_coded", "blocks_staged", "blocks_global", "stray_aggregates", "blocks"]
+
+    def pre_pass_info(self, level, b, t, r, rc):
+        """the fused pre pass of one level alone, whichever arm its cycle runs (mgs_hier_pre_pass_info).  The grouped arm writes t, rc and the
+        r of the stray waves' rows; the other arms write r and rc and leave t alone.  Returns what the launcher decided: arm (0 gather form on
+        A, 1 residual on Â, 2 aggregate-parallel, 3 grouped), kernel (0 gather, 1 coded FP64, 2 coded FP32, 4 slice, 5 aggregate-parallel,
+        6 grouped sequential sweep, 7 pair kernel), U, flags, capv, capi, bits (1 FP32 values, 2 no diagonal, 4 packed) with fp32 / nodiag /
+        packed as booleans, row blocks coded + staged / staged / walking from global memory (−1: not a row-block kernel), the level's stray
+        aggregates and row blocks."""
+        out = (C.c_int64 * 16)()
+        check(lib().mgs_hier_pre_pass_info(self.h, level, b.h, t.h, r.h, rc.h, out), self.ctx.h)
+        d = dict(zip(self.PRE_PASS_INFO, [int(v) for v in out]))
+        d.update(fp32=bool(d["bits"] & 1), nodiag=bool(d["bits"] & 2), packed=bool(d["bits"] & 4))
+        return d
+
     def post_pass(self, level, bvec, xin, ec, x, range=None):
         """the fused post pass of one level alone (mgs_hier_post_pass): xin None = t-form (bvec holds t = b + r), else bvec = r and xin = b;
         range = (blk_lo, blk_hi, gap_at, gap_len) or None for the whole level.  Returns what the launcher decided."""

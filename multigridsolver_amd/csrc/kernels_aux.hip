@@ -1016,6 +1016,7 @@ int k_agg_pre(const mgs_csr *A, const double *valhat, const double *b, const dou
   else if (threads)
     hipLaunchKernelGGL(agg_pre_kernel<double>, dim3(mgs_grid(threads, TB)), dim3(TB), 0, ctx->stream, A->rows, T->n_coarse, A->rowptr, A->col, valhat, b, hv,
                        T->cptr, T->members, T->agg, r_out, rc_out);
+  report_launch(ctx, 5, 8, 0, 0, 0, valhat32 ? 1 : 0);      // aggregate-parallel: steps of 8 entries, no LDS
   MGS_HIP(ctx, hipGetLastError());
   return MGS_OK;
 }

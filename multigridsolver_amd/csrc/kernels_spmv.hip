@@ -1500,6 +1500,7 @@ int launch_slice(const mgs_csr *A, int lanes, dim3 grid, const double *x, const 
                          A->rows, A->rowptr, A->col, A->val, x, b, dinv, omega, out, cap, bm, A->max_row_len <= 64 ? 1 : 0, blkptr_opt(A), flags);
     });
   });
+  report_launch(A->ctx, 4, gather_width(A), flags, cap > 0 ? cap : 0, cap > 0 ? cap + 2 : 2);
   return MGS_OK;
 }
 template <int OP, bool NT>
@@ -1700,10 +1701,6 @@ static coded_lds coded_budget(const mgs_csr *A, const mgs_rowcode *c, bool f32) 
   l.pad_bytes = 16 + (size_t)A->ctx->opt_lds_pad;      // opt_lds_pad: occupancy experiments
   return l;
 }
-// the one statement that fills mgs_launch_report: what a post-pass launcher launched (NULL in every cycle: nothing written)
-static void report_launch(const mgs_ctx *ctx, int kernel, int u, int flags, int capv, int capi) {
-  if (ctx->report) *ctx->report = {kernel, u, flags, capv, capi};
-}
 // workgroup → group map: XCD-contiguous, strip-major for far bands (distances in groups instead of row blocks)
 static dim3 plan_group_map(const mgs_csr *A, const mgs_groups *G, BlockMap &bm) {
   const mgs_ctx *ctx = A->ctx;
@@ -1778,7 +1775,7 @@ static int launch_coded(const mgs_csr *A, const mgs_rowcode *c, int op, const in
       });
     });
   }
-  if (post) report_launch(ctx, f32 ? 2 : (sweep ? 3 : 1), u, flags, l.capv, l.capi);
+  report_launch(ctx, f32 ? 2 : (sweep ? 3 : 1), u, flags, l.capv, l.capi, (f32 ? 1 : 0) | (packed ? 4 : 0), c ? c->tptr : nullptr);
   MGS_HIP(ctx, hipGetLastError());
   return MGS_OK;
 }
@@ -1960,6 +1957,7 @@ int mgs_launch_group_pre(const mgs_csr *A, const mgs_groups *G, const mgs_xfer *
     constexpr int UU = decltype(U)::value;
     if (pairs) {
       with_bool(hv != nullptr, [&](auto H) { launch(csr_group2_pre_kernel<UU, decltype(H)::value>, (const double *)A->val, 2 * RB, 2 * regions + 2 * RB * 8); });
+      report_launch(ctx, 7, UU, 0, l.capv, l.capi, 0, c ? c->tptr : nullptr);      // the pair kernel reads Â's FP64 values as they are: neither ND nor PK
       return;
     }
     auto form = [&](auto H, auto ND, auto PK, auto vals) {      // (HALO, ND) ∈ {(true, false), (false, true), (false, false)} for double, neither for float; PK without HALO, for double
@@ -1971,6 +1969,8 @@ int mgs_launch_group_pre(const mgs_csr *A, const mgs_groups *G, const mgs_xfer *
     if (f32) form(no, no, no, A->val32);
     else if (hv) form(std::true_type{}, no, no, (const double *)A->val);
     else with_bool(val_nd != nullptr, [&](auto ND) { with_bool(packed, [&](auto PK) { form(no, ND, PK, (const double *)A->val); }); });
+    report_launch(ctx, 6, UU, kernel_flags(ctx, nt_store_on(A), true), l.capv, l.capi, (f32 ? 1 : 0) | (val_nd ? 2 : 0) | (packed ? 4 : 0),
+                  c ? c->tptr : nullptr);
   });
   MGS_HIP(ctx, hipGetLastError());
   if (G->nstray) {
@@ -2037,7 +2037,7 @@ int mgs_launch_fused_range(const mgs_csr *A, int which, const double *wd, const 
     hipLaunchKernelGGL((csr_rowblock_fused_kernel<decltype(W)::value>), grid, dim3(RB), lds, ctx->stream, A->rows, A->rowptr, A->col, A->val, wd, bvec,
                        xin, agg, ec, out, out2, cap, bm, hv, blkptr_opt(A));
   });
-  if (which != FUSE_PRE) report_launch(ctx, 0, 8, 0, cap, cap + 2);      // the gather kernel: steps of 8, index slice beside the values
+  report_launch(ctx, 0, 8, 0, cap, cap + 2);      // the gather kernel: steps of 8, index slice beside the values
   MGS_HIP(ctx, hipGetLastError());
   return MGS_OK;
 }

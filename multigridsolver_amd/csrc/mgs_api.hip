@@ -779,6 +779,38 @@ static void level_fused_operands(const mgs_hier *h, int l, bool halo, fused_oper
   o.sweep = (o.grouped && (ctx->opt_group_sweep & 1)) ? L.grp : nullptr;
 }
 
+// The arm of level l's fused pre pass under the options as they stand — the ONE place that chooses it (cycle_level and
+// mgs_hier_pre_pass_info both ask here).  shard_split: a row shard that launches its interior row blocks beside the halo exchange, uncaptured and
+// without the native transport (the grouped form exchanges first and launches once, so it does not serve that case).
+enum { PRE_ARM_GATHER = 0, PRE_ARM_RESIDUAL = 1, PRE_ARM_AGG = 2, PRE_ARM_GROUPED = 3 };
+static int level_pre_arm(const mgs_hier *h, int l, const fused_operands &o, bool shard_split) {
+  const mgs_ctx *ctx = h->ctx;
+  const mgs_level &L = h->lev[l];
+  if (o.grouped && !shard_split) return PRE_ARM_GROUPED;
+  // small level (a dispatch costs what it costs, whatever it does): pre pass and restriction in one aggregate-parallel kernel
+  if (ctx->opt_fuse_operands && L.val_wd && L.A->rows <= ctx->opt_aggpre_max_rows && L.A->max_row_len <= 64) return PRE_ARM_AGG;
+  return o.operands ? PRE_ARM_RESIDUAL : PRE_ARM_GATHER;
+}
+// The launches of that arm where they need no exchange between them: every arm of an unsharded level (hv NULL), and the two one-kernel arms of
+// a row shard once its halo values lie in hv.  Grouped: t_out = b + r, r_out the residuals of the stray waves' rows, rc_out = Pᵀr.
+// The other arms: r_out = r on every row, rc_out = Pᵀr; t_out is not touched.
+static int launch_pre_arm(const mgs_hier *h, int l, const fused_operands &o, int arm, const double *b, double *t_out, double *r_out, double *rc_out,
+                          const double *hv) {
+  mgs_ctx *ctx = h->ctx;
+  const mgs_level &L = h->lev[l];
+  if (arm == PRE_ARM_GROUPED) {
+    // option pre_nodiag: an eligible FP64 level streams Â's diagonal as a byte per row (the same bits as from val_wd)
+    const bool nodiag = level_pre_nodiag(h, L, hv != nullptr, o.f32);
+    return mgs_launch_group_pre(&o.Ahat, L.grp, L.T, b, b, t_out, r_out, rc_out, hv, L.A->rows, nodiag ? L.val_nd : nullptr, L.nd_code, L.nd_omega, o.Ahat.pk7);
+  }
+  if (arm == PRE_ARM_AGG) return k_agg_pre(L.A, L.val_wd, b, hv, L.T, r_out, rc_out, o.f32 ? L.val_wd32 : nullptr);
+  if (hv) return mgs_fail(ctx, MGS_ERR_STATE, "pre pass of level %d: a row shard launches this arm around its halo exchange", l);
+  // r = b − A·x1 with x1 = wd∘b (never stored: the POST pass recomputes it from b)
+  if (arm == PRE_ARM_RESIDUAL) MGS_TRY(mgs_launch_csr_op(&o.Ahat, MGS_OP_RESIDUAL, b, b, nullptr, 0.0, r_out));
+  else MGS_TRY(mgs_launch_fused_range(L.A, FUSE_PRE, L.wd->d, b, nullptr, nullptr, nullptr, r_out, nullptr, nullptr, 0, mgs_row_blocks(L.A), 0x7fffffff, 0));
+  return k_restrict_agg(ctx, L.T->n_coarse, L.T->cptr, L.T->members, r_out, rc_out);
+}
+
 extern "C" {
 
 int mgs_hier_create(mgs_ctx *ctx, const mgs_csr *A, double omega, int nu1, int nu2, mgs_hier **out) {
@@ -1277,7 +1309,57 @@ int mgs_hier_pre_pass(mgs_hier *h, int level, const mgs_vec *b, mgs_vec *t, mgs_
   level_fused_operands(h, level, false, ops);
   const bool nd = level_pre_nodiag(h, L, false, ops.f32);
   if (nodiag) *nodiag = nd ? 1 : 0;
-  return mgs_launch_group_pre(&ops.Ahat, L.grp, L.T, b->d, b->d, t->d, r->d, rc->d, nullptr, L.A->rows, nd ? L.val_nd : nullptr, L.nd_code, L.nd_omega, ops.Ahat.pk7);
+  return launch_pre_arm(h, level, ops, PRE_ARM_GROUPED, b->d, t->d, r->d, rc->d, nullptr);
+}
+int mgs_hier_pre_pass_info(mgs_hier *h, int level, const mgs_vec *b, mgs_vec *t, mgs_vec *r, mgs_vec *rc, int64_t info[16]) {
+  MGS_CHECK(nullptr, h && b && t && r && rc && info, MGS_ERR_INVALID, "mgs_hier_pre_pass_info: NULL argument");
+  mgs_ctx *ctx = h->ctx;
+  MGS_CHECK(ctx, h->finalized, MGS_ERR_STATE, "mgs_hier_pre_pass_info: call mgs_hier_finalize first");
+  MGS_CHECK(ctx, level >= 0 && level + 1 < (int)h->lev.size(), MGS_ERR_INVALID, "mgs_hier_pre_pass_info: level %d has no coarser level", level);
+  MGS_TRY(prepare_fused(h));
+  mgs_level &L = h->lev[level];
+  const mgs_level &C = h->lev[level + 1];
+  MGS_CHECK(ctx, L.T && L.T->aggregation, MGS_ERR_STATE, "mgs_hier_pre_pass_info: level %d has a general P (the fused pre pass serves aggregation transfers only)", level);
+  const bool plain = L.A->cols == L.A->rows && C.A->cols == C.A->rows && !L.nx && !L.cmap_ext && !ctx->opt_valcode && !(L.A->code && L.A->code->vtab) && !L.code_hat &&
+                     !(L.code_agg && L.code_agg->vtab) && !(L.code_ap && L.code_ap->vtab);
+  MGS_CHECK(ctx, plain, MGS_ERR_STATE, "mgs_hier_pre_pass_info: level %d is sharded or value-coded", level);
+  // what cycle_level asks before it takes the fused branch
+  MGS_CHECK(ctx, ctx->opt_fuse && !h->additive && h->nu1 == 1 && h->nu2 == 1 && L.wd && L.wd_omega == h->omega && L.A->lds_cap > 0, MGS_ERR_STATE,
+            "mgs_hier_pre_pass_info: level %d does not run the fused passes (option fuse, V(1,1), multiplicative)", level);
+  MGS_CHECK(ctx, b->n >= L.n && t->n >= L.n && r->n >= L.n && rc->n >= L.T->n_coarse, MGS_ERR_INVALID,
+            "mgs_hier_pre_pass_info: vectors shorter than the level (%d rows, %d aggregates)", L.n, L.T->n_coarse);
+  fused_operands ops;
+  level_fused_operands(h, level, false, ops);
+  const int arm = level_pre_arm(h, level, ops, false);
+  mgs_launch_report rep;
+  ctx->report = &rep;
+  const int rcode = launch_pre_arm(h, level, ops, arm, b->d, t->d, r->d, rc->d, nullptr);
+  ctx->report = nullptr;
+  MGS_TRY(rcode);
+  for (int q = 0; q < 16; ++q) info[q] = 0;
+  const int nb = mgs_row_blocks(L.A);
+  info[0] = arm; info[1] = rep.kernel; info[2] = rep.u; info[3] = rep.flags; info[4] = rep.capv; info[5] = rep.capi; info[6] = rep.bits;
+  info[7] = info[8] = info[9] = -1;
+  info[10] = arm == PRE_ARM_GROUPED ? L.grp->nstray : 0; info[11] = nb;
+  // what every row block of the launch did, from the operand's block bounds, the table bounds the launch handed over and its LDS budgets — the
+  // kernels' own block-uniform conditions (copies behind the launch; the host waits for them, the caller still synchronizes before it reads)
+  const mgs_csr *op = arm == PRE_ARM_GATHER ? L.A : &ops.Ahat;
+  if (op->blkptr && rep.kernel >= 0 && rep.kernel != 5) {
+    std::vector<int> bp((size_t)nb + 1), tp;
+    MGS_HIP(ctx, hipMemcpyAsync(bp.data(), op->blkptr, sizeof(int) * bp.size(), hipMemcpyDeviceToHost, ctx->stream));
+    if (rep.tptr) { tp.resize((size_t)nb + 1); MGS_HIP(ctx, hipMemcpyAsync(tp.data(), rep.tptr, sizeof(int) * tp.size(), hipMemcpyDeviceToHost, ctx->stream)); }
+    MGS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const int va = (rep.bits & 1) ? 4 : 2;      // values per 16-byte piece: the slice starts at a multiple of it
+    int64_t ncoded = 0, nstaged = 0;
+    for (int q = 0; q < nb; ++q) {
+      const int lo = bp[q], hi = bp[q + 1], tlen = rep.tptr ? tp[q + 1] - tp[q] : 0;
+      const bool coded = tlen > 0 && tlen <= rep.capi;
+      const bool staged = hi - lo <= rep.capv && (coded || hi - (lo & ~(va - 1)) + va - 1 <= rep.capi);
+      ncoded += coded && staged; nstaged += staged;
+    }
+    info[7] = ncoded; info[8] = nstaged; info[9] = nb - nstaged;
+  }
+  return MGS_OK;
 }
 int mgs_hier_post_pass(mgs_hier *h, int level, const mgs_vec *bvec, const mgs_vec *xin, const mgs_vec *ec, mgs_vec *x, const int range[4], int64_t info[8]) {
   MGS_CHECK(nullptr, h && bvec && ec && x && info, MGS_ERR_INVALID, "mgs_hier_post_pass: NULL argument");
@@ -1575,7 +1657,7 @@ static int cycle_level(mgs_hier *h, int l, const double *b, double *x, bool zero
     fused_operands ops;
     level_fused_operands(h, l, halo, ops);
     mgs_csr &Ahat = ops.Ahat, &Amap = ops.Amap;
-    const bool f32 = ops.f32, operands = ops.operands;
+    const bool operands = ops.operands;
     const int *cmap = L.cmap_ext ? L.cmap_ext : L.T->agg;        // gather forms: coarse column of every local column
     double *ec = C.x->d, *ec_halo = C.x->d + C.n;
     // e_c's halo: one exchange on the coarse level's plan — unless that level is the replicated tail's, whose solution already holds the
@@ -1589,34 +1671,33 @@ static int cycle_level(mgs_hier *h, int l, const double *b, double *x, bool zero
     // Grouped form: pre pass + restriction in one kernel (r stays in LDS; L.r receives t = b + r, L.tmp the residuals of the
     // few rows whose aggregate leaves its row-block group), post pass in its t-form.
     // On a row shard the right-hand side of the halo rows is exchanged first (no interior/boundary split in this form).
-    const bool grouped = ops.grouped && (!halo || L.nx || !split || (h->capturing));
-    if (grouped) {
+    const int arm = level_pre_arm(h, l, ops, halo && !L.nx && split && !h->capturing);
+    if (arm == PRE_ARM_GROUPED) {
       if (halo) MGS_TRY(exchange_now(l, b, L.hbuf->d));
-      // option pre_nodiag: an eligible FP64 level streams Â's diagonal as a byte per row (the same bits as from val_wd)
-      const bool nodiag = level_pre_nodiag(h, L, halo, f32);
-      MGS_TRY(mgs_launch_group_pre(&Ahat, L.grp, L.T, b, b, L.r->d, L.tmp->d, C.b->d, hv, L.A->rows, nodiag ? L.val_nd : nullptr, L.nd_code, L.nd_omega, Ahat.pk7));
+      MGS_TRY(launch_pre_arm(h, l, ops, arm, b, L.r->d, L.tmp->d, C.b->d, hv));
       MGS_TRY(coarse_solve(h, l + 1, C.b->d, C.x->d));
       Amap.sweep = ops.sweep;
       return post_operand(L.r->d, nullptr);
     }
-    // small level (a dispatch costs what it costs, whatever it does): pre pass and restriction in one aggregate-parallel kernel
-    if (ctx->opt_fuse_operands && L.val_wd && L.A->rows <= ctx->opt_aggpre_max_rows && L.A->max_row_len <= 64) {
+    if (arm == PRE_ARM_AGG) {
       if (halo) MGS_TRY(exchange_now(l, b, L.hbuf->d));
-      MGS_TRY(k_agg_pre(L.A, L.val_wd, b, hv, L.T, L.r->d, C.b->d, f32 ? L.val_wd32 : nullptr));
+      MGS_TRY(launch_pre_arm(h, l, ops, arm, b, nullptr, L.r->d, C.b->d, hv));
       MGS_TRY(coarse_solve(h, l + 1, C.b->d, C.x->d));
       if (operands) return post_operand(L.r->d, b);
       return pass_with_exchange(ec_exchange, l + 1, ec, ec_halo, [&](int b0, int b1, int ga, int gl) {
         return mgs_launch_fused_range(L.A, FUSE_POST, L.wd->d, L.r->d, b, cmap, ec, x, nullptr, nullptr, b0, b1, ga, gl); });
     }
-    // r = b − A·x1 with x1 = wd∘b (never stored: the POST pass recomputes it from b)
-    if (operands && halo)
-      MGS_TRY(pass_with_exchange(true, l, b, L.hbuf->d, [&](int b0, int b1, int ga, int gl) {
-        return mgs_launch_coded_range(&Ahat, MGS_OP_RESIDUAL, b, b, nullptr, 0.0, nullptr, nullptr, L.r->d, hv, L.A->rows, b0, b1, ga, gl); }));
-    else if (operands) MGS_TRY(mgs_launch_csr_op(&Ahat, MGS_OP_RESIDUAL, b, b, nullptr, 0.0, L.r->d));
-    else
-      MGS_TRY(pass_with_exchange(halo, l, b, halo ? L.hbuf->d : nullptr, [&](int b0, int b1, int ga, int gl) {
-        return mgs_launch_fused_range(L.A, FUSE_PRE, L.wd->d, b, nullptr, nullptr, nullptr, L.r->d, nullptr, hv, b0, b1, ga, gl); }));
-    MGS_TRY(k_restrict_agg(ctx, L.T->n_coarse, L.T->cptr, L.T->members, L.r->d, C.b->d));
+    // r = b − A·x1 with x1 = wd∘b (never stored: the POST pass recomputes it from b); a row shard launches around its exchange
+    if (!halo) MGS_TRY(launch_pre_arm(h, l, ops, arm, b, nullptr, L.r->d, C.b->d, nullptr));
+    else {
+      if (arm == PRE_ARM_RESIDUAL)
+        MGS_TRY(pass_with_exchange(true, l, b, L.hbuf->d, [&](int b0, int b1, int ga, int gl) {
+          return mgs_launch_coded_range(&Ahat, MGS_OP_RESIDUAL, b, b, nullptr, 0.0, nullptr, nullptr, L.r->d, hv, L.A->rows, b0, b1, ga, gl); }));
+      else
+        MGS_TRY(pass_with_exchange(true, l, b, L.hbuf->d, [&](int b0, int b1, int ga, int gl) {
+          return mgs_launch_fused_range(L.A, FUSE_PRE, L.wd->d, b, nullptr, nullptr, nullptr, L.r->d, nullptr, hv, b0, b1, ga, gl); }));
+      MGS_TRY(k_restrict_agg(ctx, L.T->n_coarse, L.T->cptr, L.T->members, L.r->d, C.b->d));
+    }
     MGS_TRY(coarse_solve(h, l + 1, C.b->d, C.x->d));
     // x = x1 + Pe + wd∘(r − A·Pe)
     if (operands) return post_operand(L.r->d, b);

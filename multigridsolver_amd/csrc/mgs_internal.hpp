@@ -12,11 +12,16 @@
 
 #include "../../include/mgs.h"
 
-// what the launcher of a fused post pass decided (mgs_hier_post_pass hands it to its caller): filled in by the launch path itself while
-// mgs_ctx::report points at one, so a test can tell which arm of the kernels its case ran
+// what the launcher of a fused pass decided (mgs_hier_post_pass and mgs_hier_pre_pass_info hand it to their callers): filled in by the launch
+// path itself while mgs_ctx::report points at one, so a test can tell which arm of the kernels its case ran
 struct mgs_launch_report {
-  int kernel = -1;   // 0 gather kernel (csr_rowblock_fused_kernel), 1 coded kernel FP64, 2 coded kernel FP32, 3 coded kernel swept group by group
+  // 0 gather kernel (csr_rowblock_fused_kernel), 1 coded kernel FP64, 2 coded kernel FP32, 3 coded kernel swept group by group, 4 slice kernel
+  // (csr_rowblock_slice_kernel), 5 aggregate-parallel pre pass (agg_pre_kernel), 6 grouped pre pass, sequential sweep (csr_group_pre_kernel),
+  // 7 grouped pre pass, 512-thread pair kernel (csr_group2_pre_kernel)
+  int kernel = -1;
   int u = 0, flags = 0, capv = 0, capi = 0;   // gather width, the kernel's flags word, LDS budgets (values / ints) of a row block
+  int bits = 0;                // the launched instantiation: 1 FP32 values, 2 operand without diagonal (ND), 4 packed form (PK)
+  const int *tptr = nullptr;   // device: table bounds of the pattern code the launch handed to its kernel (NULL: none, no block is coded)
 };
 constexpr int MGS_RED_VALS = 32;   // results one reduction can hand to the host (mgs_ctx::red_host)
 // mgs_ctx::red_dev (kernels_aux.hip): MGS_DOT_BLOCKS partial slots, then MGS_RED_VALS folded results, then MGS_RED_VALS device-only scalars
@@ -92,8 +97,12 @@ struct mgs_ctx {
   struct mgs_comm *ncomm = nullptr;   // native RCCL all-reduce of the inner products (takes precedence over the callback)
   mgs_allreduce_fn allreduce = nullptr;
   void *allreduce_user = nullptr;
-  mgs_launch_report *report = nullptr;   // diagnostics (mgs_hier_post_pass): the next post-pass launch describes itself here; NULL in every cycle
+  mgs_launch_report *report = nullptr;   // diagnostics (mgs_hier_post_pass, mgs_hier_pre_pass_info): the next fused-pass launch describes itself here; NULL in every cycle
 };
+// the one statement that fills mgs_launch_report: what a fused-pass launcher launched (NULL in every cycle: nothing written)
+static inline void report_launch(const mgs_ctx *ctx, int kernel, int u, int flags, int capv, int capi, int bits = 0, const int *tptr = nullptr) {
+  if (ctx->report) *ctx->report = {kernel, u, flags, capv, capi, bits, tptr};
+}
 
 // pattern code of a CSR-shaped index array (kernels_spmv.hip): one byte per row + a small table per row block
 struct mgs_rowcode {

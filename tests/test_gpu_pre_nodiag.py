@@ -8,10 +8,14 @@ sum.  The rebuilt entry is the stored one, so every comparison below could ask f
   * against the oracle's cycle on the downloaded hierarchy: ≤ 1e-10, the bar of every cycle test here;
   * FP32 operand levels and levels that do not qualify: the same bits as with the option off.
 The pre pass alone (mgs_hier_pre_pass) is held to a host restatement: a row's sum has at most 11 terms of one sign pattern each bounded by
-|Â||b|, so 1e-13 relative in the 2-norm leaves two orders of magnitude above 11·2⁻⁵³ ≈ 1.2e-15."""
+|Â||b|, so 1e-13 relative in the 2-norm leaves two orders of magnitude above 11·2⁻⁵³ ≈ 1.2e-15.  That host product does not have the kernel's
+summation order, so the pass is ALSO held, bit for bit, to the exact restatement of tests/pre_pass_ref.py (every operator here has rows of at
+most 64 entries, where the order is a promise): t, r_c and the written entries of r."""
 import numpy as np
 import pytest
 import scipy.sparse as sps
+
+import pre_pass_ref as Q
 
 pytestmark = pytest.mark.gpu
 
@@ -88,6 +92,12 @@ def pre_pass_against_host(ctx, mg, h, b, omega, want_nodiag):
     assert rel(t_np, b_np + r_ref) <= 1e-13 and rel(rc_np, rc_ref) <= 1e-13, (rel(t_np, b_np + r_ref), rel(rc_np, rc_ref))
     w = r_np != SENT                                       # r: the rows of stray aggregates only
     assert np.linalg.norm(r_np[w] - r_ref[w]) <= 1e-13 * np.linalg.norm(r_ref)
+    # the exact restatement: the kernel's own order, equal bits
+    assert np.diff(rp).max() <= 64
+    t_x, r_x, rc_x = Q.evaluate(A, omega, g, nc, b_np, np.float64, "hat")
+    assert np.array_equal(t_np, t_x), ("t: bits", np.flatnonzero(t_np != t_x)[:8])
+    assert np.array_equal(rc_np, rc_x), ("r_c: bits", np.flatnonzero(rc_np != rc_x)[:8])
+    assert np.array_equal(r_np[w], r_x[w]), ("r: bits", np.flatnonzero(w)[r_np[w] != r_x[w]][:8])
     return t_np, rc_np
 
 
