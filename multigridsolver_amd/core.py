@@ -692,150 +692,142 @@ class Guess:
         out = np.zeros(max(k * k, 1)); check(lib().mgs_guess_gram(self.h, _dp(out)), self.ctx.h); return out[: k * k].reshape(k, k)
 
 
-class PcgPlan:
+class _KrylovPlan:
+    """What PcgPlan, BicgstabPlan and FgcrPlan share: the handle's lifetime and the four calls.  _prefix: the C functions are
+    mgs_<_prefix>_plan_*; _recursive: mgs_<_prefix>_plan_result has a recursive_resid argument.  A subclass's __init__ sets ctx, A, hier, h."""
+    _prefix = None
+    _recursive = True
+    h = None
+    _keep = None
+
+    def _fn(self, name):
+        return getattr(lib(), f"mgs_{self._prefix}_plan_{name}")
+
+    def close(self):
+        """release the plan's vectors, state block and ring (synchronises); also done when the object goes away"""
+        if self.h and self.ctx.h:
+            self._fn("destroy")(self.h)
+        self.h = None
+        self._keep = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def solve(self, x, b, max_iter, tol, ahead):
+        mi, t, st = C.c_int(max_iter), C.c_double(tol), C.c_int(-1)
+        check(self._fn("solve")(self.h, x.h, b.h, int(ahead), C.byref(mi), C.byref(t), C.byref(st)), self.ctx.h)
+        return st.value, mi.value, t.value
+
+    def enqueue(self, x, b, iters, tol):
+        check(self._fn("enqueue")(self.h, x.h, b.h, int(iters), float(tol)), self.ctx.h)
+        self._keep = (self._keep, x, b)
+        return self
+
+    def result(self, recursive=False):
+        it, r, rec, st = C.c_int(), C.c_double(), C.c_double(), C.c_int(-1)
+        if self._recursive:
+            rc = self._fn("result")(self.h, C.byref(it), C.byref(r), C.byref(rec) if recursive else None, C.byref(st))
+        else:
+            rc = self._fn("result")(self.h, C.byref(it), C.byref(r), C.byref(st))
+        check(rc, self.ctx.h)
+        self._keep = None
+        return (st.value, it.value, r.value, rec.value) if recursive else (st.value, it.value, r.value)
+
+    def info(self):
+        out = (C.c_int64 * 6)(); check(self._fn("info")(self.h, out), self.ctx.h)
+        return [int(v) for v in out]
+
+
+class PcgPlan(_KrylovPlan):
     """Preconditioned CG with device-resident scalars (mgs_pcg_plan, include/mgs.h): mgs_pcg's arithmetic and bits, with one host look per
     iteration `ahead` iterations behind the queue (solve), or none at all (enqueue, then result).  A and hier must outlive the plan (they are
     kept referenced here)."""
+    _prefix, _recursive = "pcg", False
 
     def __init__(self, A, hier=None, flexible=False):
         self.ctx, self.A, self.hier = A.ctx, A, hier
         h = C.c_void_p()
         check(lib().mgs_pcg_plan_create(A.h, hier.h if hier else None, int(bool(flexible)), C.byref(h)), A.ctx.h)
         self.h = h
-        self._keep = None
-
-    def __del__(self):
-        try:
-            if self.h and self.ctx.h:
-                lib().mgs_pcg_plan_destroy(self.h)
-        except Exception:  # noqa: BLE001
-            pass
 
     def solve(self, x, b, max_iter=10000, tol=1e-6, ahead=1):
         """mgs_pcg's contract → (status, iterations, achieved_tol)"""
-        mi, t, st = C.c_int(max_iter), C.c_double(tol), C.c_int(-1)
-        check(lib().mgs_pcg_plan_solve(self.h, x.h, b.h, int(ahead), C.byref(mi), C.byref(t), C.byref(st)), self.ctx.h)
-        return st.value, mi.value, t.value
+        return super().solve(x, b, max_iter, tol, ahead)
 
     def enqueue(self, x, b, iters, tol):
         """INIT, `iters` iterations and the final true residual on the context's stream; no host wait.  x and b are kept referenced until result()"""
-        check(lib().mgs_pcg_plan_enqueue(self.h, x.h, b.h, int(iters), float(tol)), self.ctx.h)
-        self._keep = (self._keep, x, b)
-        return self
+        return super().enqueue(x, b, iters, tol)
 
     def result(self):
         """of the last enqueue (synchronises) → (status, iterations done, true relative residual)"""
-        it, r, st = C.c_int(), C.c_double(), C.c_int(-1)
-        check(lib().mgs_pcg_plan_result(self.h, C.byref(it), C.byref(r), C.byref(st)), self.ctx.h)
-        self._keep = None
-        return st.value, it.value, r.value
+        return super().result()
 
     def info(self):
         """[0] device bytes, [1] solves + enqueues, [2] iterations enqueued by the last call, [3] of those run frozen, [4] host waits, [5] restarts"""
-        out = (C.c_int64 * 6)(); check(lib().mgs_pcg_plan_info(self.h, out), self.ctx.h)
-        return [int(v) for v in out]
+        return super().info()
 
 
-class BicgstabPlan:
+class BicgstabPlan(_KrylovPlan):
     """BiCGSTAB with device-resident scalars (mgs_bicgstab_plan, include/mgs.h): mgs_bicgstab's arithmetic and bits, with one host look per
     iteration `ahead` iterations behind the queue (solve), or none at all (enqueue, then result).  A and hier must outlive the plan (they are
     kept referenced here)."""
+    _prefix = "bicgstab"
 
     def __init__(self, A, hier=None):
         self.ctx, self.A, self.hier = A.ctx, A, hier
         h = C.c_void_p()
         check(lib().mgs_bicgstab_plan_create(A.h, hier.h if hier else None, C.byref(h)), A.ctx.h)
         self.h = h
-        self._keep = None
-
-    def close(self):
-        """release the plan's vectors, state block and ring (synchronises); also done when the object goes away"""
-        if self.h and self.ctx.h:
-            lib().mgs_bicgstab_plan_destroy(self.h)
-        self.h = None
-        self._keep = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
 
     def solve(self, x, b, max_iter=10000, tol=1e-6, ahead=1):
         """mgs_bicgstab's contract → (status, iterations, achieved_tol), the tuple bicgstab() returns"""
-        mi, t, st = C.c_int(max_iter), C.c_double(tol), C.c_int(-1)
-        check(lib().mgs_bicgstab_plan_solve(self.h, x.h, b.h, int(ahead), C.byref(mi), C.byref(t), C.byref(st)), self.ctx.h)
-        return st.value, mi.value, t.value
+        return super().solve(x, b, max_iter, tol, ahead)
 
     def enqueue(self, x, b, iters, tol):
         """INIT, `iters` iterations and the final true residual on the context's stream; no host wait.  x and b are kept referenced until result()"""
-        check(lib().mgs_bicgstab_plan_enqueue(self.h, x.h, b.h, int(iters), float(tol)), self.ctx.h)
-        self._keep = (self._keep, x, b)
-        return self
+        return super().enqueue(x, b, iters, tol)
 
     def result(self, recursive=False):
         """of the last enqueue (synchronises) → (status, iterations done, true relative residual); recursive=True appends the recursion's residual"""
-        it, r, rec, st = C.c_int(), C.c_double(), C.c_double(), C.c_int(-1)
-        check(lib().mgs_bicgstab_plan_result(self.h, C.byref(it), C.byref(r), C.byref(rec) if recursive else None, C.byref(st)), self.ctx.h)
-        self._keep = None
-        return (st.value, it.value, r.value, rec.value) if recursive else (st.value, it.value, r.value)
+        return super().result(recursive)
 
     def info(self):
         """[0] device bytes, [1] solves + enqueues, [2] iterations enqueued by the last call, [3] of those run frozen, [4] host waits, [5] 0"""
-        out = (C.c_int64 * 6)(); check(lib().mgs_bicgstab_plan_info(self.h, out), self.ctx.h)
-        return [int(v) for v in out]
+        return super().info()
 
 
-class FgcrPlan:
+class FgcrPlan(_KrylovPlan):
     """Flexible GCR(restart) with device-resident coefficients (mgs_fgcr_plan, include/mgs.h): mgs_fgcr's arithmetic and bits, with one host look
     per iteration `ahead` iterations behind the queue (solve), or none at all (enqueue, then result).  restart in 1..16.  A and hier must outlive
     the plan (they are kept referenced here)."""
+    _prefix = "fgcr"
 
     def __init__(self, A, hier=None, restart=10):
         self.ctx, self.A, self.hier, self.restart = A.ctx, A, hier, int(restart)
         h = C.c_void_p()
         check(lib().mgs_fgcr_plan_create(A.h, hier.h if hier else None, int(restart), C.byref(h)), A.ctx.h)
         self.h = h
-        self._keep = None
-
-    def close(self):
-        """release the plan's vectors, state block and ring (synchronises); also done when the object goes away"""
-        if self.h and self.ctx.h:
-            lib().mgs_fgcr_plan_destroy(self.h)
-        self.h = None
-        self._keep = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
 
     def solve(self, x, b, max_iter=1000, tol=1e-6, ahead=0):
         """mgs_fgcr's contract → (status, iterations, achieved_tol), the tuple fgcr() returns.  ahead = 0 by default, not the other plans' 1: an iteration
         with a K-cycle is long, and the one that ahead = 1 runs frozen cost 2–3 % of a solve where the look it hides cost nothing measurable
         (profiles/r14_fgcr_plan.md)"""
-        mi, t, st = C.c_int(max_iter), C.c_double(tol), C.c_int(-1)
-        check(lib().mgs_fgcr_plan_solve(self.h, x.h, b.h, int(ahead), C.byref(mi), C.byref(t), C.byref(st)), self.ctx.h)
-        return st.value, mi.value, t.value
+        return super().solve(x, b, max_iter, tol, ahead)
 
     def enqueue(self, x, b, iters, tol):
         """INIT, `iters` iterations with their scheduled window closes and FINAL on the context's stream; no host wait.  x and b are kept referenced until result()"""
-        check(lib().mgs_fgcr_plan_enqueue(self.h, x.h, b.h, int(iters), float(tol)), self.ctx.h)
-        self._keep = (self._keep, x, b)
-        return self
+        return super().enqueue(x, b, iters, tol)
 
     def result(self, recursive=False):
         """of the last enqueue (synchronises) → (status, iterations done, true relative residual); recursive=True appends the recursion's residual"""
-        it, r, rec, st = C.c_int(), C.c_double(), C.c_double(), C.c_int(-1)
-        check(lib().mgs_fgcr_plan_result(self.h, C.byref(it), C.byref(r), C.byref(rec) if recursive else None, C.byref(st)), self.ctx.h)
-        self._keep = None
-        return (st.value, it.value, r.value, rec.value) if recursive else (st.value, it.value, r.value)
+        return super().result(recursive)
 
     def info(self):
         """[0] device bytes, [1] solves + enqueues, [2] iterations enqueued by the last call, [3] of those run frozen, [4] host waits, [5] restarts from the true residual"""
-        out = (C.c_int64 * 6)(); check(lib().mgs_fgcr_plan_info(self.h, out), self.ctx.h)
-        return [int(v) for v in out]
+        return super().info()
 
 
 def bicgstab(A, x, b, hier=None, max_iter=10000, tol=1e-6):

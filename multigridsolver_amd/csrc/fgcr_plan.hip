@@ -22,19 +22,12 @@
 // mgs_fgcr_plan_solve looks at one slot per iteration, `ahead` iterations behind the queue, and orchestrates every restart from the true residual
 // itself (mgs_fgcr's restart_now); mgs_fgcr_plan_enqueue never looks and its windows are fixed.
 #include <algorithm>
-#include <chrono>
-#include <cmath>
-#include <deque>
-#include <time.h>
 
-#include "mgs_internal.hpp"
+#include "krylov_plan.hpp"
 
 namespace {
-constexpr int PTB = 256;                 // lanes per workgroup of the vector passes (the BLAS-1 kernels' TB)
-constexpr int RING = 1024;               // posted slots; at most RING − 1 posts are outstanding, so no slot is rewritten before the host has read it
-constexpr int RED = MGS_DOT_BLOCKS;      // red_dev[RED], red_dev[RED + 1]: what the last fold left
+using namespace krylov;
 constexpr int FW = 16;                   // the widest window: one multi-vector pass holds 16 vectors (kernels_aux.hip: MDOT_MAX), a hierarchy caches 16 graphs
-typedef double fd2 __attribute__((ext_vector_type(2)));
 
 // why a solve froze
 enum { WHY_NONE = 0, WHY_RECURSION = 1, WHY_BREAKDOWN = 2, WHY_INIT = 3, WHY_TRUE = 4 };
@@ -53,31 +46,11 @@ struct FgState {
   int m_open;    // directions of the open window that x has not received yet
   int wasted;    // iterations that ran frozen
 };
-struct FgSlot {    // 64 bytes of mapped host memory
-  unsigned long long ticket;
-  double resid, normb;
-  int it, status, frozen, wasted, why, m_open;
-  unsigned long long pad[2];
-};
-static_assert(sizeof(FgSlot) == 64, "one slot per 64 bytes");
-
 enum { STEP_NORMB = 0, STEP_INIT, STEP_COEF, STEP_RHOK, STEP_RES, STEP_YSOLVE, STEP_WIN, STEP_RESUME, STEP_FINAL };
-
-__device__ __forceinline__ void post_slot(FgSlot *s, const FgState *st, unsigned long long ticket) {
-  __hip_atomic_store(&s->resid, st->resid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  __hip_atomic_store(&s->normb, st->normb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  __hip_atomic_store(&s->it, st->it, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  __hip_atomic_store(&s->status, st->status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  __hip_atomic_store(&s->frozen, st->frozen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  __hip_atomic_store(&s->wasted, st->wasted, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  __hip_atomic_store(&s->why, st->why, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  __hip_atomic_store(&s->m_open, st->m_open, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  __hip_atomic_store(&s->ticket, ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
 
 // The scalar steps: one wave, lane 0 works.  red = ctx->red_dev + RED.  k: the window slot (COEF, RHOK); `it`: the iteration the step belongs to
 // (FINAL: the iterations enqueued); `tol`: the tolerance (INIT, RES, WIN, FINAL); slot = NULL: nothing is posted.  Line numbers: mgs_api.hip, mgs_fgcr.
-__global__ void fgp_step_kernel(int step, FgState *__restrict__ st, const double *__restrict__ red, int k, int it, double tol, FgSlot *slot, unsigned long long ticket) {
+__global__ void fgp_step_kernel(int step, FgState *__restrict__ st, const double *__restrict__ red, int k, int it, double tol, Slot *slot, unsigned long long ticket) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   switch (step) {
     case STEP_NORMB: {                      // ‖b‖ (‖Πb‖), 0 replaced by 1; a fresh state
@@ -93,7 +66,7 @@ __global__ void fgp_step_kernel(int step, FgState *__restrict__ st, const double
       const double nr = sqrt(red[0]);
       st->resid = nr / st->normb;
       if (st->resid <= tol) { st->frozen = 1; st->status = ST_OK; st->why = WHY_INIT; }
-      if (slot) post_slot(slot, st, ticket);
+      if (slot) post_slot(slot, st, ticket, &st->why, &st->m_open);
       break;
     }
     case STEP_COEF: {                       // U_jk = ρ_j != 0 ? h_j/ρ_j : 0
@@ -116,7 +89,7 @@ __global__ void fgp_step_kernel(int step, FgState *__restrict__ st, const double
         st->resid = sqrt(red[0]) / st->normb;
         if (st->resid < tol) { st->frozen = 1; st->status = ST_RECURSION; st->why = WHY_RECURSION; }
       }
-      if (slot) post_slot(slot, st, ticket);
+      if (slot) post_slot(slot, st, ticket, &st->why, &st->m_open);
       break;
     }
     case STEP_YSOLVE: {                     // close_window: (I + U)·y = α over the m_open directions, cf_j = −y_j
@@ -138,7 +111,7 @@ __global__ void fgp_step_kernel(int step, FgState *__restrict__ st, const double
       } else if (st->why == WHY_RECURSION) { st->resid = t; st->status = t < tol ? ST_OK : ST_DRIFTED; }
       else if (st->why == WHY_BREAKDOWN) { st->resid = t; st->status = t < tol ? ST_OK : ST_BREAKDOWN; }
       st->m_open = 0;
-      if (slot) post_slot(slot, st, ticket);
+      if (slot) post_slot(slot, st, ticket, &st->why, &st->m_open);
       break;
     }
     case STEP_RESUME: {                     // the host has seen "drifted": go on from the true residual with an empty window
@@ -158,11 +131,6 @@ __global__ void fgp_step_kernel(int step, FgState *__restrict__ st, const double
   }
 }
 
-__device__ __forceinline__ void fst2(fd2 *p, fd2 v, bool nt) {      // streaming store, as st2 in kernels_aux.hip
-  if (nt) asm volatile("global_store_dwordx4 %0, %1, off nt" : : "v"(p), "v"(v) : "memory");
-  else *p = v;
-}
-
 struct FgVecs { const double *w[FW]; };
 
 // Orthogonalisation pass: v ← v − Σ_{j<K} U_jK·w_j with the partial pairs (v·v, v·u), maxpy_dot2_kernel's expression (its z = x = v, u2 = NULL),
@@ -179,16 +147,16 @@ __global__ __launch_bounds__(PTB) void fgp_orth_kernel(int64_t n, int K, const F
   const int64_t stride = (int64_t)gridDim.x * PTB;
   if (VEC) {
     const int64_t n2 = n >> 1;
-    fd2 *vv = reinterpret_cast<fd2 *>(v);
-    const fd2 *__restrict__ uv = reinterpret_cast<const fd2 *>(u);
+    kd2 *vv = reinterpret_cast<kd2 *>(v);
+    const kd2 *__restrict__ uv = reinterpret_cast<const kd2 *>(u);
     for (int64_t i = (int64_t)blockIdx.x * PTB + threadIdx.x; i < n2; i += stride) {
-      fd2 zi = vv[i];
+      kd2 zi = vv[i];
 #pragma unroll
       for (int k = 0; k < FW; ++k)
-        if (k < K) { const fd2 wi = reinterpret_cast<const fd2 *>(W.w[k])[i]; zi.x -= cf[k] * wi.x; zi.y -= cf[k] * wi.y; }
+        if (k < K) { const kd2 wi = reinterpret_cast<const kd2 *>(W.w[k])[i]; zi.x -= cf[k] * wi.x; zi.y -= cf[k] * wi.y; }
       vv[i] = zi;
       s0 += zi.x * zi.x; s0 += zi.y * zi.y;
-      const fd2 q = uv[i]; s1 += zi.x * q.x; s1 += zi.y * q.y;
+      const kd2 q = uv[i]; s1 += zi.x * q.x; s1 += zi.y * q.y;
     }
     if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
       double zi = v[n - 1];
@@ -208,14 +176,7 @@ __global__ __launch_bounds__(PTB) void fgp_orth_kernel(int64_t n, int K, const F
       s1 += zi * u[i];
     }
   }
-  for (int off = 32; off > 0; off >>= 1) { s0 += __shfl_down(s0, off); s1 += __shfl_down(s1, off); }
-  if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = s0; sh[1][threadIdx.x >> 6] = s1; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t0 = 0.0, t1 = 0.0;
-    for (int q = 0; q < PTB / 64; ++q) { t0 += sh[0][q]; t1 += sh[1][q]; }
-    part[blockIdx.x] = t0; part[gridDim.x + blockIdx.x] = t1;
-  }
+  KRYLOV_FOLD2(s0, s1, sh, part);
 }
 
 // x-pass of a window close: x ← x − Σ_{j<m_open} cf_j·c_j, maxpy_dot2_kernel's expression without sums; m_open and cf from the state block.
@@ -230,12 +191,12 @@ __global__ __launch_bounds__(PTB) void fgp_x_kernel(int64_t n, const FgState *__
   const int64_t stride = (int64_t)gridDim.x * PTB;
   if (VEC) {
     const int64_t n2 = n >> 1;
-    fd2 *xv = reinterpret_cast<fd2 *>(x);
+    kd2 *xv = reinterpret_cast<kd2 *>(x);
     for (int64_t i = (int64_t)blockIdx.x * PTB + threadIdx.x; i < n2; i += stride) {
-      fd2 zi = xv[i];
+      kd2 zi = xv[i];
 #pragma unroll
       for (int k = 0; k < FW; ++k)
-        if (k < K) { const fd2 wi = reinterpret_cast<const fd2 *>(W.w[k])[i]; zi.x -= cf[k] * wi.x; zi.y -= cf[k] * wi.y; }
+        if (k < K) { const kd2 wi = reinterpret_cast<const kd2 *>(W.w[k])[i]; zi.x -= cf[k] * wi.x; zi.y -= cf[k] * wi.y; }
       xv[i] = zi;
     }
     if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
@@ -262,28 +223,21 @@ __global__ __launch_bounds__(PTB) void fgp_resid_vec_kernel(int64_t n, int k, co
   const double a = 1.0, b = -st->alpha[k];
   __shared__ double sh[2][PTB / 64];
   const int64_t n2 = n >> 1;
-  fd2 *rv = reinterpret_cast<fd2 *>(r);
-  const fd2 *__restrict__ yv = reinterpret_cast<const fd2 *>(v);
+  kd2 *rv = reinterpret_cast<kd2 *>(r);
+  const kd2 *__restrict__ yv = reinterpret_cast<const kd2 *>(v);
   double s0 = 0.0, s1 = 0.0;
   const int64_t stride = (int64_t)gridDim.x * PTB;
   for (int64_t i = (int64_t)blockIdx.x * PTB + threadIdx.x; i < n2; i += stride) {
-    const fd2 p = rv[i], o = yv[i]; fd2 q;
+    const kd2 p = rv[i], o = yv[i]; kd2 q;
     q.x = a * p.x + b * o.x; q.y = a * p.y + b * o.y;
-    fst2(rv + i, q, nts != 0);
+    kst2(rv + i, q, nts != 0);
     s0 += q.x * q.x; s0 += q.y * q.y;
   }
   if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
     const double zi = a * r[n - 1] + b * v[n - 1];
     r[n - 1] = zi; s0 += zi * zi;
   }
-  for (int off = 32; off > 0; off >>= 1) { s0 += __shfl_down(s0, off); s1 += __shfl_down(s1, off); }
-  if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = s0; sh[1][threadIdx.x >> 6] = s1; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t0 = 0.0, t1 = 0.0;
-    for (int q = 0; q < PTB / 64; ++q) { t0 += sh[0][q]; t1 += sh[1][q]; }
-    part[blockIdx.x] = t0; part[gridDim.x + blockIdx.x] = t1;
-  }
+  KRYLOV_FOLD2(s0, s1, sh, part);
 }
 __global__ __launch_bounds__(PTB) void fgp_resid_kernel(int64_t n, int k, const FgState *__restrict__ st, double *r, const double *__restrict__ v, double *__restrict__ part) {
   if (st->frozen) return;
@@ -297,53 +251,28 @@ __global__ __launch_bounds__(PTB) void fgp_resid_kernel(int64_t n, int k, const 
     r[i] = zi;
     s0 += zi * zi;
   }
-  for (int off = 32; off > 0; off >>= 1) { s0 += __shfl_down(s0, off); s1 += __shfl_down(s1, off); }
-  if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = s0; sh[1][threadIdx.x >> 6] = s1; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t0 = 0.0, t1 = 0.0;
-    for (int q = 0; q < PTB / 64; ++q) { t0 += sh[0][q]; t1 += sh[1][q]; }
-    part[blockIdx.x] = t0; part[gridDim.x + blockIdx.x] = t1;
-  }
+  KRYLOV_FOLD2(s0, s1, sh, part);
 }
 
-inline bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 // workgroups of maxpy_dot2_kernel (k_maxpy_dot2) and of mdot_partial_kernel (k_mdot)
 inline int maxpy_grid(int64_t n) { return (int)std::min<int64_t>(std::max<int64_t>((n + (int64_t)PTB * 4 - 1) / ((int64_t)PTB * 4), 1), 1 << 20); }
 inline int mdot_grid(int64_t n) { return (int)std::min<int64_t>(std::max<int64_t>((n / 2 + (int64_t)PTB * 4 - 1) / ((int64_t)PTB * 4), 1), 2048); }
 }   // namespace
 
-struct mgs_fgcr_plan {
-  mgs_ctx *ctx = nullptr;
-  const mgs_csr *A = nullptr;
-  mgs_hier *h = nullptr;
-  bool ns = false;
-  int n = 0, restart = 0;
-  double *block = nullptr;            // r, C[0..restart), V[0..restart) (stride doubles each), then the state
-  int64_t stride = 0, bytes = 0;
-  mgs_vec r, C[FW], V[FW];            // views into block
-  FgState *st = nullptr;
-  FgSlot *ring = nullptr, *ring_dev = nullptr;        // RING slots, then one FgState the result is copied into (mapped, coherent host memory)
-  FgState *snap = nullptr;
-  unsigned long long seq = 0;         // ticket of the last posting step enqueued
-  // what info and result report
-  int64_t calls = 0, enq_iters = 0, wasted = 0, waits = 0, restarts = 0;
-  bool unread = false;                // an enqueue whose result has not been read yet
-  int res_it = 0, res_status = 1; double res_resid = 0.0, res_rec = 0.0;
+struct mgs_fgcr_plan : krylov::Plan<FgState> {
+  mgs_fgcr_plan() { name = "mgs_fgcr_plan"; }
+  int restart = 0;
+  mgs_vec r, C[FW], V[FW];            // r, C[0..restart), V[0..restart): views into block, in this order
 };
 
 namespace {
-struct Look { int it, status, frozen, wasted, why; double resid; };
-
 int step(mgs_fgcr_plan *P, int which, int k, int it, double tol, bool post) {
   mgs_ctx *ctx = P->ctx;
-  FgSlot *slot = nullptr;
-  if (post) { ++P->seq; slot = P->ring_dev + (P->seq % RING); }
+  Slot *slot = P->next_slot(post);
   hipLaunchKernelGGL(fgp_step_kernel, dim3(1), dim3(64), 0, ctx->stream, which, P->st, ctx->red_dev + RED, k, it, tol, slot, P->seq);
   MGS_HIP(ctx, hipGetLastError());
   return MGS_OK;
 }
-inline int nts_of(const mgs_ctx *ctx, int64_t n) { return ctx->opt_nt_store > 0 && n >= ctx->opt_nt_store; }
 
 // the grid, the arms, the partial buffer and the fold of k_maxpy_dot2 with sums (the plan's vectors are 256-byte aligned: the 16-byte arm whenever n >= 2)
 int launch_orth(mgs_fgcr_plan *P, int k) {
@@ -426,47 +355,11 @@ int enqueue_close(mgs_fgcr_plan *P, mgs_vec *xv, const mgs_vec *bv, bool project
   MGS_TRY(true_residual(P, xv, bv));
   return step(P, last ? STEP_FINAL : STEP_WIN, 0, it, tol, post);
 }
-// wait until the post with ticket `want` is visible (no slot is rewritten before it has been read: see RING)
-int wait_post(mgs_fgcr_plan *P, unsigned long long want, Look *out) {
-  mgs_ctx *ctx = P->ctx;
-  FgSlot *s = P->ring + (want % RING);
-  P->waits++;
-  const auto t0 = std::chrono::steady_clock::now();
-  double next_query = 2e-3;
-  for (;;) {
-    if (__atomic_load_n(&s->ticket, __ATOMIC_ACQUIRE) == want) break;
-    const double waited = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (waited < 300e-6) { for (int k = 0; k < 8; ++k) __builtin_ia32_pause(); continue; }
-    if (waited > next_query) {           // a queue that has drained (or failed) without the ticket will never deliver it
-      next_query = waited + 2e-3;
-      const hipError_t e = hipStreamQuery(ctx->stream);
-      if (e == hipSuccess) {
-        if (__atomic_load_n(&s->ticket, __ATOMIC_ACQUIRE) == want) break;
-        return mgs_fail(ctx, MGS_ERR_HIP, "mgs_fgcr_plan: posted results never reached the host ring");
-      }
-      if (e != hipErrorNotReady) return mgs_fail(ctx, MGS_ERR_HIP, "mgs_fgcr_plan: %s", hipGetErrorString(e));
-    }
-    struct timespec ts = {0, 25000}; nanosleep(&ts, nullptr);
-  }
-  out->it = s->it; out->status = s->status; out->frozen = s->frozen; out->wasted = s->wasted; out->why = s->why; out->resid = s->resid;
-  return MGS_OK;
-}
-int check_call(mgs_fgcr_plan *P, const mgs_vec *x, const mgs_vec *b, const char *who) {
-  mgs_ctx *ctx = P->ctx;
-  MGS_CHECK(ctx, x->n >= P->n && b->n >= P->n, MGS_ERR_INVALID, "%s: vectors of %lld and %lld entries, the operator has %d rows", who, (long long)x->n, (long long)b->n, P->n);
-  MGS_CHECK(ctx, x->d != b->d, MGS_ERR_INVALID, "%s: x must not alias b", who);
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  MGS_HIP(ctx, hipStreamIsCapturing(ctx->stream, &cs));
-  MGS_CHECK(ctx, cs == hipStreamCaptureStatusNone, MGS_ERR_STATE, "%s: the context's stream is being captured", who);
-  return MGS_OK;
-}
 }   // namespace
 
 int mgs_fgcr_plan_destroy(mgs_fgcr_plan *P) {
   if (!P) return MGS_OK;
-  if (P->block || P->ring) hipStreamSynchronize(P->ctx->stream);
-  if (P->block) mgs_hip_free(P->block);
-  if (P->ring) hipHostFree(P->ring);
+  P->release();
   delete P;
   return MGS_OK;
 }
@@ -475,43 +368,13 @@ int mgs_fgcr_plan_create(const mgs_csr *A, mgs_hier *h, int restart, mgs_fgcr_pl
   mgs_ctx *ctx = A ? A->ctx : (h ? h->ctx : nullptr);
   MGS_CHECK(ctx, A && out, MGS_ERR_INVALID, "mgs_fgcr_plan_create: NULL argument");
   MGS_CHECK(ctx, restart >= 1 && restart <= FW, MGS_ERR_INVALID, "mgs_fgcr_plan_create: restart = %d outside 1..%d (wider windows are served by mgs_fgcr)", restart, FW);
-  MGS_CHECK(ctx, A->rows == A->cols && !ctx->ncomm && !ctx->allreduce, MGS_ERR_INVALID, "mgs_fgcr_plan_create: the matrix is %d x %d%s (a square unsharded operator is required)",
-            A->rows, A->cols, A->cols > A->rows ? ", halo columns: a row shard" : (A->rows == A->cols ? ", on a context that sums over ranks" : ", not square"));
-  MGS_CHECK(ctx, A->rows > 0, MGS_ERR_INVALID, "mgs_fgcr_plan_create: the matrix has no rows");
-  if (h) {
-    bool shard = h->halo || h->halo_begin || h->halo_end || h->halo_fused || h->coarse || h->native || h->ntail;
-    for (const mgs_level &L : h->lev) shard = shard || L.nx || (L.A && L.A->cols > L.A->rows);
-    MGS_CHECK(ctx, !shard, MGS_ERR_INVALID, "mgs_fgcr_plan_create: the hierarchy has halo columns, exchange callbacks, native plans or a tail (a square unsharded operator is required)");
-    MGS_CHECK(ctx, h->ctx == ctx && !h->lev.empty() && h->lev[0].n == A->rows, MGS_ERR_INVALID, "mgs_fgcr_plan_create: the hierarchy's fine level has %d rows, A has %d",
-              h->lev.empty() ? 0 : h->lev[0].n, A->rows);
-    MGS_CHECK(ctx, h->finalized, MGS_ERR_STATE, "mgs_fgcr_plan_create: call mgs_hier_finalize first");
-  }
-  bool ns = false;
-  MGS_TRY(mgs_krylov_nullspace(A, h, "mgs_fgcr_plan_create", &ns));
-  MGS_TRY(mgs_csr_optimize(const_cast<mgs_csr *>(A)));
   mgs_fgcr_plan *P = new mgs_fgcr_plan();
-  P->ctx = ctx; P->A = A; P->h = h; P->ns = ns; P->n = A->rows; P->restart = restart;
-  P->stride = (((int64_t)P->n + 31) / 32) * 32;                                          // every vector 256-byte aligned
-  const int nvec = 1 + 2 * restart;
-  const size_t nstate = (sizeof(FgState) + 255) / 256 * 32;                              // doubles
-  const size_t ndoubles = (size_t)nvec * P->stride + nstate;
-  int rc = mgs_dev_alloc(ctx, &P->block, ndoubles);
-  if (rc == MGS_OK && hipMemsetAsync(P->block, 0, sizeof(double) * ndoubles, ctx->stream) != hipSuccess) rc = mgs_fail(ctx, MGS_ERR_HIP, "mgs_fgcr_plan_create: hipMemsetAsync failed");
-  if (rc == MGS_OK) {
-    const size_t hb = sizeof(FgSlot) * RING + (sizeof(FgState) + 255) / 256 * 256;
-    if (hipHostMalloc((void **)&P->ring, hb, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) { P->ring = nullptr; rc = mgs_fail(ctx, MGS_ERR_ALLOC, "mgs_fgcr_plan_create: mapped host ring"); }
-    else {
-      memset(P->ring, 0, hb);
-      P->snap = reinterpret_cast<FgState *>(P->ring + RING);
-      if (hipHostGetDevicePointer((void **)&P->ring_dev, P->ring, 0) != hipSuccess) rc = mgs_fail(ctx, MGS_ERR_HIP, "mgs_fgcr_plan_create: the host ring is not mappable into the device");
-    }
-  }
+  int rc = P->validate(A, h, "mgs_fgcr_plan_create", "a square unsharded operator is required");
+  if (rc == MGS_OK) rc = P->allocate("mgs_fgcr_plan_create", 1 + 2 * restart);
   if (rc != MGS_OK) { mgs_fgcr_plan_destroy(P); return rc; }
-  auto view = [&](mgs_vec &v, int64_t k) { v.ctx = ctx; v.n = P->n; v.d = P->block + k * P->stride; v.owns = false; };
-  view(P->r, 0);
-  for (int k = 0; k < restart; ++k) { view(P->C[k], 1 + k); view(P->V[k], 1 + restart + k); }
-  P->st = reinterpret_cast<FgState *>(P->block + (int64_t)nvec * P->stride);
-  P->bytes = (int64_t)(sizeof(double) * ndoubles);
+  P->restart = restart;
+  P->r = P->view(0);
+  for (int k = 0; k < restart; ++k) { P->C[k] = P->view(1 + k); P->V[k] = P->view(1 + restart + k); }
   // the partial sums of every reduction a solve launches, and the hierarchy's operands and one captured cycle r → C[k] per slot: no later call allocates
   int64_t np = 2 * std::max<int64_t>(std::max<int64_t>(mgs_row_blocks(A), mgs_blas1_grid(ctx, ((int64_t)P->n + 1) / 2)), maxpy_grid(P->n));
   np = std::max<int64_t>(np, (int64_t)restart * mdot_grid(P->n));
@@ -527,10 +390,9 @@ int mgs_fgcr_plan_enqueue(mgs_fgcr_plan *P, mgs_vec *x, const mgs_vec *b, int it
   MGS_CHECK(P ? P->ctx : nullptr, P && x && b, MGS_ERR_INVALID, "mgs_fgcr_plan_enqueue: NULL argument");
   mgs_ctx *ctx = P->ctx;
   MGS_CHECK(ctx, iters >= 0, MGS_ERR_INVALID, "mgs_fgcr_plan_enqueue: iters = %d < 0", iters);
-  MGS_TRY(check_call(P, x, b, "mgs_fgcr_plan_enqueue"));
+  MGS_TRY(P->check_call(x, b, "mgs_fgcr_plan_enqueue"));
   mgs_vec xv, bv;
-  xv.ctx = bv.ctx = ctx; xv.n = bv.n = P->n; xv.d = x->d; bv.d = b->d; xv.owns = bv.owns = false;
-  P->calls++; P->enq_iters = 0; P->wasted = 0; P->waits = 0; P->restarts = 0; P->unread = true;
+  P->begin_call(x, b, &xv, &bv, true);
   MGS_TRY(enqueue_init(P, &xv, &bv, tol, false));
   int k = 0;
   for (int i = 1; i <= iters; ++i) {
@@ -539,29 +401,17 @@ int mgs_fgcr_plan_enqueue(mgs_fgcr_plan *P, mgs_vec *x, const mgs_vec *b, int it
   }
   // FINAL: the open window, the projection of x (an x that no iteration followed was projected by INIT), the true residual, the status
   MGS_TRY(enqueue_close(P, &xv, &bv, iters > 0, iters, tol, false, true));
-  MGS_HIP(ctx, hipMemcpyAsync(P->snap, P->st, sizeof(FgState), hipMemcpyDeviceToHost, ctx->stream));
-  return MGS_OK;
+  return P->snapshot();
 }
 
 int mgs_fgcr_plan_result(mgs_fgcr_plan *P, int *iters_done, double *resid, double *recursive_resid, int *status) {
   MGS_CHECK(P ? P->ctx : nullptr, P, MGS_ERR_INVALID, "mgs_fgcr_plan_result: NULL plan");
-  mgs_ctx *ctx = P->ctx;
-  MGS_CHECK(ctx, P->calls > 0, MGS_ERR_STATE, "mgs_fgcr_plan_result: nothing has been solved or enqueued");
-  if (P->unread) {
-    MGS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    P->res_it = P->snap->it; P->res_status = P->snap->status; P->res_resid = P->snap->true_resid; P->res_rec = P->snap->resid; P->wasted = P->snap->wasted;
-    P->unread = false;
-  }
-  if (iters_done) *iters_done = P->res_it;
-  if (resid) *resid = P->res_resid;
-  if (recursive_resid) *recursive_resid = P->res_rec;
-  if (status) *status = P->res_status;
-  return MGS_OK;
+  return P->result("mgs_fgcr_plan_result", iters_done, resid, recursive_resid, status);
 }
 
 int mgs_fgcr_plan_info(const mgs_fgcr_plan *P, int64_t out[6]) {
   MGS_CHECK(P ? P->ctx : nullptr, P && out, MGS_ERR_INVALID, "mgs_fgcr_plan_info: NULL argument");
-  out[0] = P->bytes; out[1] = P->calls; out[2] = P->enq_iters; out[3] = P->wasted; out[4] = P->waits; out[5] = P->restarts;
+  P->info(out);
   return MGS_OK;
 }
 
@@ -569,73 +419,61 @@ int mgs_fgcr_plan_solve(mgs_fgcr_plan *P, mgs_vec *x, const mgs_vec *b, int ahea
   MGS_CHECK(P ? P->ctx : nullptr, P && x && b && max_iter && tol && status, MGS_ERR_INVALID, "mgs_fgcr_plan_solve: NULL argument");
   mgs_ctx *ctx = P->ctx;
   MGS_CHECK(ctx, ahead >= 0, MGS_ERR_INVALID, "mgs_fgcr_plan_solve: ahead = %d < 0", ahead);
-  MGS_TRY(check_call(P, x, b, "mgs_fgcr_plan_solve"));
+  MGS_TRY(P->check_call(x, b, "mgs_fgcr_plan_solve"));
   const int n = P->n, R = P->restart;
   mgs_vec xv, bv;
-  xv.ctx = bv.ctx = ctx; xv.n = bv.n = n; xv.d = x->d; bv.d = b->d; xv.owns = bv.owns = false;
-  P->calls++; P->enq_iters = 0; P->wasted = 0; P->waits = 0; P->restarts = 0; P->unread = false;
+  P->begin_call(x, b, &xv, &bv, false);
   const int maxit = *max_iter;
   const double tl = *tol;
-  const int win = std::min(ahead, RING - 2);          // at most win + 1 posts of iterations are outstanding
-  struct Out { int it; unsigned long long seq; };
-  std::deque<Out> outq;                               // enqueued, outcome not seen yet
-  Look L = {0, ST_RUNNING, 0, 0, WHY_NONE, 0.0};
+  Lookahead la(maxit, ahead);
+  Look L = {0, ST_RUNNING, 0, 0, WHY_NONE, 0, 0.0, 0.0};      // aux0: why the solve froze
   int r_it = 0, r_status = 1; double r_resid = 0.0;   // what the call returns
   MGS_TRY(enqueue_init(P, &xv, &bv, tl, true));
-  outq.push_back({0, P->seq});
-  {
-    int next = 1, k = 0, seen = -1;                   // next iteration to enqueue and its window slot; outcomes are known through iteration `seen` (0: INIT)
-    for (;;) {
-      while (next <= maxit && next - 1 - win <= seen) {
-        // the iteration that fills its window closes it and posts from WIN; the last iteration of all posts from RES and the host closes behind
-        // its look: that close projects x, which no iteration run on speculation may do twice
-        const bool closing = k == R - 1 && next < maxit;
-        MGS_TRY(enqueue_iteration(P, k, next, tl, !closing));
-        if (closing) MGS_TRY(enqueue_close(P, &xv, &bv, false, next, tl, true, false));
-        outq.push_back({next, P->seq});
-        ++next; k = closing ? 0 : k + 1;
-      }
-      // the outcome the next enqueue waits for; with nothing left to enqueue, the last one (a freeze is sticky: every later post shows it)
-      const int need = next <= maxit ? std::max(next - 1 - win, outq.front().it) : outq.back().it;
-      while (outq.front().it < need) outq.pop_front();
-      MGS_TRY(wait_post(P, outq.front().seq, &L));
-      outq.pop_front();
-      seen = need;
-      if (!L.frozen) {
-        if (seen < maxit) continue;
-        if (seen == 0) { r_it = 0; r_resid = L.resid; r_status = 1; break; }      // *max_iter <= 0: nothing has touched x since INIT projected it
-        // the iterations are used up: x catches up (projected), the true residual decides between 0 and 1
-        MGS_TRY(enqueue_close(P, &xv, &bv, true, maxit, tl, true, false));
-        MGS_TRY(wait_post(P, P->seq, &L));
-        r_it = maxit; r_resid = L.resid; r_status = (L.frozen && L.status == ST_OK) ? 0 : 1;
-        break;
-      }
-      // frozen at iteration L.it: nothing enqueued behind it has changed x, r or the open window
-      outq.clear();
-      r_it = L.it;
-      if (L.why == WHY_INIT) { r_resid = L.resid; r_status = 0; break; }      // `<=` at iteration 0: x (projected by INIT) stays as it is
-      if (L.why == WHY_TRUE) {                       // a full window's true residual is below tol: x ← Πx behind it, as fin() does
-        if (P->ns) MGS_TRY(k_project_const(ctx, n, xv.d));
-        r_resid = L.resid; r_status = 0;
-        break;
-      }
-      // the recursion says converged, or a breakdown: close (a no-op if a scheduled close has run already), x ← Πx, the true residual decides
-      const int why = L.why;
-      MGS_TRY(enqueue_close(P, &xv, &bv, true, L.it, tl, true, false));
-      MGS_TRY(wait_post(P, P->seq, &L));
-      r_resid = L.resid;
-      if (why == WHY_BREAKDOWN) { r_status = L.status == ST_OK ? 0 : 2; break; }
-      if (L.status == ST_OK) { r_status = 0; break; }
-      // the recursion had drifted: r holds the true residual, go on from it with an empty window (mgs_fgcr's restart_now)
-      P->restarts++;
-      r_status = 1;
-      if (r_it >= maxit) break;
-      MGS_TRY(step(P, STEP_RESUME, 0, r_it, 0.0, false));
-      next = r_it + 1; seen = r_it; k = 0;
-      L.frozen = 0;
+  la.enqueued(P->seq);
+  for (int k = 0;;) {                                 // k: the window slot of the next iteration to enqueue
+    while (la.may_enqueue()) {
+      // the iteration that fills its window closes it and posts from WIN; the last iteration of all posts from RES and the host closes behind
+      // its look: that close projects x, which no iteration run on speculation may do twice
+      const bool closing = k == R - 1 && la.next < maxit;
+      MGS_TRY(enqueue_iteration(P, k, la.next, tl, !closing));
+      if (closing) MGS_TRY(enqueue_close(P, &xv, &bv, false, la.next, tl, true, false));
+      la.enqueued(P->seq);
+      k = closing ? 0 : k + 1;
     }
+    MGS_TRY(P->wait_post(la.take(), &L));
+    if (!L.frozen) {
+      if (la.seen < maxit) continue;
+      if (la.seen == 0) { r_it = 0; r_resid = L.resid; r_status = 1; break; }      // *max_iter <= 0: nothing has touched x since INIT projected it
+      // the iterations are used up: x catches up (projected), the true residual decides between 0 and 1
+      MGS_TRY(enqueue_close(P, &xv, &bv, true, maxit, tl, true, false));
+      MGS_TRY(P->wait_post(P->seq, &L));
+      r_it = maxit; r_resid = L.resid; r_status = (L.frozen && L.status == ST_OK) ? 0 : 1;
+      break;
+    }
+    // frozen at iteration L.it: nothing enqueued behind it has changed x, r or the open window
+    r_it = L.it;
+    if (L.aux0 == WHY_INIT) { r_resid = L.resid; r_status = 0; break; }      // `<=` at iteration 0: x (projected by INIT) stays as it is
+    if (L.aux0 == WHY_TRUE) {                        // a full window's true residual is below tol: x ← Πx behind it, as fin() does
+      if (P->ns) MGS_TRY(k_project_const(ctx, n, xv.d));
+      r_resid = L.resid; r_status = 0;
+      break;
+    }
+    // the recursion says converged, or a breakdown: close (a no-op if a scheduled close has run already), x ← Πx, the true residual decides
+    const int why = L.aux0;
+    MGS_TRY(enqueue_close(P, &xv, &bv, true, L.it, tl, true, false));
+    MGS_TRY(P->wait_post(P->seq, &L));
+    r_resid = L.resid;
+    if (why == WHY_BREAKDOWN) { r_status = L.status == ST_OK ? 0 : 2; break; }
+    if (L.status == ST_OK) { r_status = 0; break; }
+    // the recursion had drifted: r holds the true residual, go on from it with an empty window (mgs_fgcr's restart_now)
+    P->restarts++;
+    r_status = 1;
+    if (r_it >= maxit) break;
+    MGS_TRY(step(P, STEP_RESUME, 0, r_it, 0.0, false));
+    la.restart(r_it); k = 0;
+    L.frozen = 0;
   }
-  MGS_HIP(ctx, hipMemcpyAsync(P->snap, P->st, sizeof(FgState), hipMemcpyDeviceToHost, ctx->stream));
+  MGS_TRY(P->snapshot());
   MGS_TRY(mgs_sync(ctx));
   P->wasted = P->snap->wasted;
   *max_iter = r_it; *tol = r_resid; *status = r_status;

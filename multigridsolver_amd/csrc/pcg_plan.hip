@@ -19,18 +19,12 @@
 // the mechanism of begin_post / fetch_results with the plan's own sequence number as the ticket.  mgs_pcg_plan_solve looks at one slot per
 // iteration, `ahead` iterations behind the queue; mgs_pcg_plan_enqueue never looks.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
-#include <deque>
-#include <time.h>
 
-#include "mgs_internal.hpp"
+#include "krylov_plan.hpp"
 
 namespace {
-constexpr int PTB = 256;                 // lanes per workgroup of the vector passes (the BLAS-1 kernels' TB)
-constexpr int RING = 1024;               // posted slots; at most RING − 1 posts are outstanding, so no slot is rewritten before the host has read it
-constexpr int RED = MGS_DOT_BLOCKS;      // red_dev[RED], red_dev[RED + 1]: what the last fold left
-typedef double pd2 __attribute__((ext_vector_type(2)));
+using namespace krylov;
 
 // the state block.  status: −1 running, 0 the recursion says converged (the true residual still decides), 2 r·z not positive, 3 p·q not
 // positive; after FINAL: mgs_pcg's status
@@ -43,29 +37,11 @@ struct PcgState {
   int pending;   // x lags by alpha·p
   int wasted;    // iterations that ran frozen
 };
-struct PcgSlot {   // 64 bytes of mapped host memory
-  unsigned long long ticket;
-  double resid, normb;
-  int it, status, frozen, wasted;
-  unsigned long long pad[3];
-};
-static_assert(sizeof(PcgSlot) == 64, "one slot per 64 bytes");
-
 enum { STEP_NORMB = 0, STEP_INIT, STEP_RHO, STEP_PQ, STEP_RES, STEP_FLUSHED, STEP_RESTART, STEP_FINAL };
-
-__device__ __forceinline__ void post_slot(PcgSlot *s, const PcgState *st, unsigned long long ticket) {
-  __hip_atomic_store(&s->resid, st->resid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  __hip_atomic_store(&s->normb, st->normb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  __hip_atomic_store(&s->it, st->it, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  __hip_atomic_store(&s->status, st->status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  __hip_atomic_store(&s->frozen, st->frozen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  __hip_atomic_store(&s->wasted, st->wasted, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  __hip_atomic_store(&s->ticket, ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
 
 // The scalar steps: one wave, lane 0 works.  red = ctx->red_dev + RED.  `it`: the iteration the step belongs to (FINAL: the iterations
 // enqueued); `val`: the tolerance (INIT, RES, FINAL) or the true residual the host found (RESTART); slot = NULL: nothing is posted.
-__global__ void pcgp_step_kernel(int step, PcgState *__restrict__ st, const double *__restrict__ red, int it, double val, int flexible, PcgSlot *slot,
+__global__ void pcgp_step_kernel(int step, PcgState *__restrict__ st, const double *__restrict__ red, int it, double val, int flexible, Slot *slot,
                                  unsigned long long ticket) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   switch (step) {
@@ -124,11 +100,6 @@ __global__ void pcgp_step_kernel(int step, PcgState *__restrict__ st, const doub
   }
 }
 
-__device__ __forceinline__ void pst2(pd2 *p, pd2 v, bool nt) {      // streaming store, as st2 in kernels_aux.hip
-  if (nt) asm volatile("global_store_dwordx4 %0, %1, off nt" : : "v"(p), "v"(v) : "memory");
-  else *p = v;
-}
-
 // Direction pass, pcg_dir_vec_kernel / pcg_dir_kernel with the scalars from the state block: first: p ← z (p not read, x not touched);
 // else x ← x + a·p, p ← z + beta·p.  The state is read once per workgroup through uniform loads; a frozen workgroup returns at once.
 __global__ __launch_bounds__(PTB) void pcgp_dir_vec_kernel(int64_t n, const PcgState *__restrict__ st, double *__restrict__ x, double *__restrict__ p,
@@ -137,19 +108,19 @@ __global__ __launch_bounds__(PTB) void pcgp_dir_vec_kernel(int64_t n, const PcgS
   const bool first = st->first != 0;
   const double a = st->alpha, beta = st->beta;
   const int64_t n2 = n >> 1;
-  pd2 *__restrict__ xv = reinterpret_cast<pd2 *>(x);
-  pd2 *__restrict__ pv = reinterpret_cast<pd2 *>(p);
-  const pd2 *__restrict__ zv = reinterpret_cast<const pd2 *>(z);
+  kd2 *__restrict__ xv = reinterpret_cast<kd2 *>(x);
+  kd2 *__restrict__ pv = reinterpret_cast<kd2 *>(p);
+  const kd2 *__restrict__ zv = reinterpret_cast<const kd2 *>(z);
   const int64_t stride = (int64_t)gridDim.x * PTB;
   for (int64_t i = (int64_t)blockIdx.x * PTB + threadIdx.x; i < n2; i += stride) {
-    const pd2 zi = zv[i];
-    if (first) pst2(pv + i, zi, nts != 0);
+    const kd2 zi = zv[i];
+    if (first) kst2(pv + i, zi, nts != 0);
     else {
-      const pd2 pi = pv[i], xi = xv[i]; pd2 xo, po;
+      const kd2 pi = pv[i], xi = xv[i]; kd2 xo, po;
       xo.x = xi.x + a * pi.x; xo.y = xi.y + a * pi.y;
       po.x = zi.x + beta * pi.x; po.y = zi.y + beta * pi.y;
-      pst2(xv + i, xo, nts != 0);
-      pst2(pv + i, po, nts != 0);
+      kst2(xv + i, xo, nts != 0);
+      kst2(pv + i, po, nts != 0);
     }
   }
   if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
@@ -177,14 +148,14 @@ __global__ __launch_bounds__(PTB) void pcgp_resid_vec_kernel(int64_t n, const Pc
   const double a = st->alpha;
   __shared__ double sh[PTB / 64];
   const int64_t n2 = n >> 1;
-  pd2 *__restrict__ rv = reinterpret_cast<pd2 *>(r);
-  const pd2 *__restrict__ qv = reinterpret_cast<const pd2 *>(q);
+  kd2 *__restrict__ rv = reinterpret_cast<kd2 *>(r);
+  const kd2 *__restrict__ qv = reinterpret_cast<const kd2 *>(q);
   double s0 = 0.0;
   const int64_t stride = (int64_t)gridDim.x * PTB;
   for (int64_t i = (int64_t)blockIdx.x * PTB + threadIdx.x; i < n2; i += stride) {
-    const pd2 ri = rv[i], qi = qv[i]; pd2 o;
+    const kd2 ri = rv[i], qi = qv[i]; kd2 o;
     o.x = ri.x - a * qi.x; o.y = ri.y - a * qi.y;
-    pst2(rv + i, o, nts != 0);
+    kst2(rv + i, o, nts != 0);
     s0 += o.x * o.x; s0 += o.y * o.y;
   }
   if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) { const double ri = r[n - 1] - a * q[n - 1]; r[n - 1] = ri; s0 += ri * ri; }
@@ -221,13 +192,13 @@ __global__ __launch_bounds__(PTB) void pcgp_flush_vec_kernel(int64_t n, const Pc
   if (!st->pending) return;
   const double a = st->alpha;
   const int64_t n2 = n >> 1;
-  pd2 *__restrict__ xv = reinterpret_cast<pd2 *>(x);
-  const pd2 *__restrict__ pv = reinterpret_cast<const pd2 *>(p);
+  kd2 *__restrict__ xv = reinterpret_cast<kd2 *>(x);
+  const kd2 *__restrict__ pv = reinterpret_cast<const kd2 *>(p);
   const int64_t stride = (int64_t)gridDim.x * PTB;
   for (int64_t i = (int64_t)blockIdx.x * PTB + threadIdx.x; i < n2; i += stride) {
-    const pd2 pi = pv[i], xi = xv[i]; pd2 xo;
+    const kd2 pi = pv[i], xi = xv[i]; kd2 xo;
     xo.x = a * pi.x + xi.x; xo.y = a * pi.y + xi.y;
-    pst2(xv + i, xo, nts != 0);
+    kst2(xv + i, xo, nts != 0);
   }
   if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) x[n - 1] = a * p[n - 1] + x[n - 1];
 }
@@ -239,41 +210,22 @@ __global__ __launch_bounds__(PTB) void pcgp_flush_kernel(int64_t n, const PcgSta
   for (; i < n; i += stride) x[i] = a * p[i] + x[i];
 }
 
-inline bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 }   // namespace
 
-struct mgs_pcg_plan {
-  mgs_ctx *ctx = nullptr;
-  const mgs_csr *A = nullptr;
-  mgs_hier *h = nullptr;
+struct mgs_pcg_plan : krylov::Plan<PcgState> {
+  mgs_pcg_plan() { name = "mgs_pcg_plan"; }
   int flexible = 0;
-  bool ns = false;
-  int n = 0;
-  double *block = nullptr;            // r, z, p, q (stride doubles each), then the state
-  int64_t stride = 0, bytes = 0;
-  mgs_vec r, z, p, q;                 // views into block
-  PcgState *st = nullptr;
-  PcgSlot *ring = nullptr, *ring_dev = nullptr;       // RING slots, then one PcgState the result is copied into (mapped, coherent host memory)
-  PcgState *snap = nullptr;
-  unsigned long long seq = 0;         // ticket of the last posting step enqueued
-  // what info and result report
-  int64_t calls = 0, enq_iters = 0, wasted = 0, waits = 0, restarts = 0;
-  bool unread = false;                // an enqueue whose result has not been read yet
-  int res_it = 0, res_status = 1; double res_resid = 0.0;
+  mgs_vec r, z, p, q;                 // views into block, in this order
 };
 
 namespace {
-struct Look { int it, status, frozen, wasted; double resid, normb; };
-
 int step(mgs_pcg_plan *P, int which, int it, double val, bool post) {
   mgs_ctx *ctx = P->ctx;
-  PcgSlot *slot = nullptr;
-  if (post) { ++P->seq; slot = P->ring_dev + (P->seq % RING); }
+  Slot *slot = P->next_slot(post);
   hipLaunchKernelGGL(pcgp_step_kernel, dim3(1), dim3(64), 0, ctx->stream, which, P->st, ctx->red_dev + RED, it, val, P->flexible, slot, P->seq);
   MGS_HIP(ctx, hipGetLastError());
   return MGS_OK;
 }
-inline int nts_of(const mgs_ctx *ctx, int64_t n) { return ctx->opt_nt_store > 0 && n >= ctx->opt_nt_store; }
 
 int launch_direction(mgs_pcg_plan *P, double *x) {
   mgs_ctx *ctx = P->ctx; const int64_t n = P->n;
@@ -342,47 +294,11 @@ int enqueue_iteration(mgs_pcg_plan *P, mgs_vec *xv, int it, double tol, bool fir
   P->enq_iters++;
   return step(P, STEP_RES, it, tol, post);
 }
-// wait until the post with ticket `want` is visible (no slot is rewritten before it has been read: see RING)
-int wait_post(mgs_pcg_plan *P, unsigned long long want, Look *out) {
-  mgs_ctx *ctx = P->ctx;
-  PcgSlot *s = P->ring + (want % RING);
-  P->waits++;
-  const auto t0 = std::chrono::steady_clock::now();
-  double next_query = 2e-3;
-  for (;;) {
-    if (__atomic_load_n(&s->ticket, __ATOMIC_ACQUIRE) == want) break;
-    const double waited = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (waited < 300e-6) { for (int k = 0; k < 8; ++k) __builtin_ia32_pause(); continue; }
-    if (waited > next_query) {           // a queue that has drained (or failed) without the ticket will never deliver it
-      next_query = waited + 2e-3;
-      const hipError_t e = hipStreamQuery(ctx->stream);
-      if (e == hipSuccess) {
-        if (__atomic_load_n(&s->ticket, __ATOMIC_ACQUIRE) == want) break;
-        return mgs_fail(ctx, MGS_ERR_HIP, "mgs_pcg_plan: posted results never reached the host ring");
-      }
-      if (e != hipErrorNotReady) return mgs_fail(ctx, MGS_ERR_HIP, "mgs_pcg_plan: %s", hipGetErrorString(e));
-    }
-    struct timespec ts = {0, 25000}; nanosleep(&ts, nullptr);
-  }
-  out->it = s->it; out->status = s->status; out->frozen = s->frozen; out->wasted = s->wasted; out->resid = s->resid; out->normb = s->normb;
-  return MGS_OK;
-}
-int check_call(mgs_pcg_plan *P, const mgs_vec *x, const mgs_vec *b, const char *who) {
-  mgs_ctx *ctx = P->ctx;
-  MGS_CHECK(ctx, x->n >= P->n && b->n >= P->n, MGS_ERR_INVALID, "%s: vectors of %lld and %lld entries, the operator has %d rows", who, (long long)x->n, (long long)b->n, P->n);
-  MGS_CHECK(ctx, x->d != b->d, MGS_ERR_INVALID, "%s: x must not alias b", who);
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  MGS_HIP(ctx, hipStreamIsCapturing(ctx->stream, &cs));
-  MGS_CHECK(ctx, cs == hipStreamCaptureStatusNone, MGS_ERR_STATE, "%s: the context's stream is being captured", who);
-  return MGS_OK;
-}
 }   // namespace
 
 int mgs_pcg_plan_destroy(mgs_pcg_plan *P) {
   if (!P) return MGS_OK;
-  if (P->block || P->ring) hipStreamSynchronize(P->ctx->stream);
-  if (P->block) mgs_hip_free(P->block);
-  if (P->ring) hipHostFree(P->ring);
+  P->release();
   delete P;
   return MGS_OK;
 }
@@ -390,43 +306,14 @@ int mgs_pcg_plan_destroy(mgs_pcg_plan *P) {
 int mgs_pcg_plan_create(const mgs_csr *A, mgs_hier *h, int flexible, mgs_pcg_plan **out) {
   mgs_ctx *ctx = A ? A->ctx : (h ? h->ctx : nullptr);
   MGS_CHECK(ctx, A && out, MGS_ERR_INVALID, "mgs_pcg_plan_create: NULL argument");
-  MGS_CHECK(ctx, A->rows == A->cols && !ctx->ncomm && !ctx->allreduce, MGS_ERR_INVALID, "mgs_pcg_plan_create: the matrix is %d x %d%s (row shards are served by mgs_pcg)",
-            A->rows, A->cols, A->cols > A->rows ? ", halo columns: a row shard" : (A->rows == A->cols ? ", on a context that sums over ranks" : ", not square"));
-  MGS_CHECK(ctx, A->rows > 0, MGS_ERR_INVALID, "mgs_pcg_plan_create: the matrix has no rows");
-  if (h) {
-    bool shard = h->halo || h->halo_begin || h->halo_end || h->halo_fused || h->coarse || h->native || h->ntail;
-    for (const mgs_level &L : h->lev) shard = shard || L.nx || (L.A && L.A->cols > L.A->rows);
-    MGS_CHECK(ctx, !shard, MGS_ERR_INVALID, "mgs_pcg_plan_create: the hierarchy has halo columns, exchange callbacks, native plans or a tail (row shards are served by mgs_pcg)");
-    MGS_CHECK(ctx, h->ctx == ctx && !h->lev.empty() && h->lev[0].n == A->rows, MGS_ERR_INVALID, "mgs_pcg_plan_create: the hierarchy's fine level has %d rows, A has %d",
-              h->lev.empty() ? 0 : h->lev[0].n, A->rows);
-    MGS_CHECK(ctx, h->finalized, MGS_ERR_STATE, "mgs_pcg_plan_create: call mgs_hier_finalize first");
-  }
-  MGS_CHECK(ctx, flexible || !h || (h->nu1 == h->nu2 && h->kcycle_levels <= 0 && !h->kcycle_entry), MGS_ERR_INVALID,
-            "mgs_pcg_plan_create: flexible = 0 needs a fixed symmetric preconditioner (nu1 == nu2, no K-cycle); pass flexible = 1");
-  bool ns = false;
-  MGS_TRY(mgs_krylov_nullspace(A, h, "mgs_pcg_plan_create", &ns));
-  MGS_TRY(mgs_csr_optimize(const_cast<mgs_csr *>(A)));
   mgs_pcg_plan *P = new mgs_pcg_plan();
-  P->ctx = ctx; P->A = A; P->h = h; P->flexible = flexible ? 1 : 0; P->ns = ns; P->n = A->rows;
-  P->stride = (((int64_t)P->n + 31) / 32) * 32; if (P->stride == 0) P->stride = 32;      // every vector 256-byte aligned
-  const size_t nstate = (sizeof(PcgState) + 255) / 256 * 32;                             // doubles
-  const size_t ndoubles = (size_t)4 * P->stride + nstate;
-  int rc = mgs_dev_alloc(ctx, &P->block, ndoubles);
-  if (rc == MGS_OK && hipMemsetAsync(P->block, 0, sizeof(double) * ndoubles, ctx->stream) != hipSuccess) rc = mgs_fail(ctx, MGS_ERR_HIP, "mgs_pcg_plan_create: hipMemsetAsync failed");
-  if (rc == MGS_OK) {
-    const size_t hb = sizeof(PcgSlot) * RING + 256;
-    if (hipHostMalloc((void **)&P->ring, hb, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) { P->ring = nullptr; rc = mgs_fail(ctx, MGS_ERR_ALLOC, "mgs_pcg_plan_create: mapped host ring"); }
-    else {
-      memset(P->ring, 0, hb);
-      P->snap = reinterpret_cast<PcgState *>(P->ring + RING);
-      if (hipHostGetDevicePointer((void **)&P->ring_dev, P->ring, 0) != hipSuccess) rc = mgs_fail(ctx, MGS_ERR_HIP, "mgs_pcg_plan_create: the host ring is not mappable into the device");
-    }
-  }
+  int rc = P->validate(A, h, "mgs_pcg_plan_create", "row shards are served by mgs_pcg");
+  if (rc == MGS_OK && !(flexible || !h || (h->nu1 == h->nu2 && h->kcycle_levels <= 0 && !h->kcycle_entry)))
+    rc = mgs_fail(ctx, MGS_ERR_INVALID, "mgs_pcg_plan_create: flexible = 0 needs a fixed symmetric preconditioner (nu1 == nu2, no K-cycle); pass flexible = 1");
+  if (rc == MGS_OK) rc = P->allocate("mgs_pcg_plan_create", 4);
   if (rc != MGS_OK) { mgs_pcg_plan_destroy(P); return rc; }
-  mgs_vec *vs[4] = {&P->r, &P->z, &P->p, &P->q};
-  for (int k = 0; k < 4; ++k) { vs[k]->ctx = ctx; vs[k]->n = P->n; vs[k]->d = P->block + (int64_t)k * P->stride; vs[k]->owns = false; }
-  P->st = reinterpret_cast<PcgState *>(P->block + 4 * P->stride);
-  P->bytes = (int64_t)(sizeof(double) * ndoubles);
+  P->flexible = flexible ? 1 : 0;
+  P->r = P->view(0); P->z = P->view(1); P->p = P->view(2); P->q = P->view(3);
   // the partial sums of every reduction a solve launches, and the hierarchy's operands and captured cycle (one cycle on r = 1): no later call allocates
   const int64_t nb = std::max<int64_t>(mgs_row_blocks(A), mgs_blas1_grid(ctx, ((int64_t)P->n + 1) / 2));
   rc = mgs_ensure_dot_part(ctx, 2 * std::max<int64_t>(nb, 1));
@@ -441,10 +328,9 @@ int mgs_pcg_plan_enqueue(mgs_pcg_plan *P, mgs_vec *x, const mgs_vec *b, int iter
   MGS_CHECK(P ? P->ctx : nullptr, P && x && b, MGS_ERR_INVALID, "mgs_pcg_plan_enqueue: NULL argument");
   mgs_ctx *ctx = P->ctx;
   MGS_CHECK(ctx, iters >= 0, MGS_ERR_INVALID, "mgs_pcg_plan_enqueue: iters = %d < 0", iters);
-  MGS_TRY(check_call(P, x, b, "mgs_pcg_plan_enqueue"));
+  MGS_TRY(P->check_call(x, b, "mgs_pcg_plan_enqueue"));
   mgs_vec xv, bv;
-  xv.ctx = bv.ctx = ctx; xv.n = bv.n = P->n; xv.d = x->d; bv.d = b->d; xv.owns = bv.owns = false;
-  P->calls++; P->enq_iters = 0; P->wasted = 0; P->waits = 0; P->restarts = 0; P->unread = true;
+  P->begin_call(x, b, &xv, &bv, true);
   MGS_TRY(enqueue_init(P, &xv, &bv, tol, false));
   for (int i = 1; i <= iters; ++i) MGS_TRY(enqueue_iteration(P, &xv, i, tol, i == 1, false));
   // FINAL: the predicated flush, the projection, the true residual, the status
@@ -452,28 +338,17 @@ int mgs_pcg_plan_enqueue(mgs_pcg_plan *P, mgs_vec *x, const mgs_vec *b, int iter
   if (P->ns) MGS_TRY(k_project_const(ctx, P->n, xv.d));
   MGS_TRY(launch_true_residual(P, &xv, &bv));
   MGS_TRY(step(P, STEP_FINAL, iters, tol, false));
-  MGS_HIP(ctx, hipMemcpyAsync(P->snap, P->st, sizeof(PcgState), hipMemcpyDeviceToHost, ctx->stream));
-  return MGS_OK;
+  return P->snapshot();
 }
 
 int mgs_pcg_plan_result(mgs_pcg_plan *P, int *iters_done, double *resid, int *status) {
   MGS_CHECK(P ? P->ctx : nullptr, P, MGS_ERR_INVALID, "mgs_pcg_plan_result: NULL plan");
-  mgs_ctx *ctx = P->ctx;
-  MGS_CHECK(ctx, P->calls > 0, MGS_ERR_STATE, "mgs_pcg_plan_result: nothing has been solved or enqueued");
-  if (P->unread) {
-    MGS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    P->res_it = P->snap->it; P->res_status = P->snap->status; P->res_resid = P->snap->true_resid; P->wasted = P->snap->wasted;
-    P->unread = false;
-  }
-  if (iters_done) *iters_done = P->res_it;
-  if (resid) *resid = P->res_resid;
-  if (status) *status = P->res_status;
-  return MGS_OK;
+  return P->result("mgs_pcg_plan_result", iters_done, resid, nullptr, status);
 }
 
 int mgs_pcg_plan_info(const mgs_pcg_plan *P, int64_t out[6]) {
   MGS_CHECK(P ? P->ctx : nullptr, P && out, MGS_ERR_INVALID, "mgs_pcg_plan_info: NULL argument");
-  out[0] = P->bytes; out[1] = P->calls; out[2] = P->enq_iters; out[3] = P->wasted; out[4] = P->waits; out[5] = P->restarts;
+  P->info(out);
   return MGS_OK;
 }
 
@@ -481,21 +356,18 @@ int mgs_pcg_plan_solve(mgs_pcg_plan *P, mgs_vec *x, const mgs_vec *b, int ahead,
   MGS_CHECK(P ? P->ctx : nullptr, P && x && b && max_iter && tol && status, MGS_ERR_INVALID, "mgs_pcg_plan_solve: NULL argument");
   mgs_ctx *ctx = P->ctx;
   MGS_CHECK(ctx, ahead >= 0, MGS_ERR_INVALID, "mgs_pcg_plan_solve: ahead = %d < 0", ahead);
-  MGS_TRY(check_call(P, x, b, "mgs_pcg_plan_solve"));
+  MGS_TRY(P->check_call(x, b, "mgs_pcg_plan_solve"));
   const int n = P->n;
   mgs_vec xv, bv;
-  xv.ctx = bv.ctx = ctx; xv.n = bv.n = n; xv.d = x->d; bv.d = b->d; xv.owns = bv.owns = false;
-  P->calls++; P->enq_iters = 0; P->wasted = 0; P->waits = 0; P->restarts = 0; P->unread = false;
+  P->begin_call(x, b, &xv, &bv, false);
   const int maxit = *max_iter;
   const double tl = *tol;
-  const int win = std::min(ahead, RING - 2);          // at most win + 1 posts are outstanding
-  struct Out { int it; unsigned long long seq; };
-  std::deque<Out> outq;                               // enqueued, outcome not seen yet
+  Lookahead la(maxit, ahead);
   int proj_it = -1;                                   // x was projected after this iteration's update (−1: never)
   // mgs_pcg's `done`: x is flushed by the caller; x ← Πx unless no update has touched it since the last projection
   auto done = [&](int it, int st, double resid, bool updated) -> int {
     if (P->ns && (updated || proj_it < 0)) MGS_TRY(k_project_const(ctx, n, xv.d));
-    MGS_HIP(ctx, hipMemcpyAsync(P->snap, P->st, sizeof(PcgState), hipMemcpyDeviceToHost, ctx->stream));
+    MGS_TRY(P->snapshot());
     MGS_TRY(mgs_sync(ctx));
     P->wasted = P->snap->wasted;
     P->res_it = it; P->res_status = st; P->res_resid = resid;
@@ -503,24 +375,17 @@ int mgs_pcg_plan_solve(mgs_pcg_plan *P, mgs_vec *x, const mgs_vec *b, int ahead,
     return MGS_OK;
   };
   MGS_TRY(enqueue_init(P, &xv, &bv, tl, true));
-  outq.push_back({0, P->seq});
-  int next = 1, seen = -1;                            // next iteration to enqueue; outcomes are known through iteration `seen` (0: INIT)
+  la.enqueued(P->seq);
   bool first = true;
-  Look L = {0, -1, 0, 0, 0.0, 1.0};
+  Look L = {0, -1, 0, 0, 0, 0, 0.0, 1.0};
   for (;;) {
-    while (next <= maxit && next - 1 - win <= seen) {
-      MGS_TRY(enqueue_iteration(P, &xv, next, tl, first, true));
+    while (la.may_enqueue()) {
+      MGS_TRY(enqueue_iteration(P, &xv, la.next, tl, first, true));
       first = false;
-      outq.push_back({next, P->seq});
-      ++next;
+      la.enqueued(P->seq);
     }
-    if (outq.empty()) break;                          // every iteration up to maxit has been seen and none froze
-    // the outcome the next enqueue waits for; with nothing left to enqueue, the last one
-    const int need = next <= maxit ? std::max(next - 1 - win, outq.front().it) : outq.back().it;
-    while (outq.front().it < need) outq.pop_front();
-    MGS_TRY(wait_post(P, outq.front().seq, &L));
-    outq.pop_front();
-    seen = need;
+    if (la.idle()) break;                             // every iteration up to maxit has been seen and none froze
+    MGS_TRY(P->wait_post(la.take(), &L));
     if (!L.frozen) continue;
     const int i = L.it;
     if (L.status == 2 || L.status == 3) {             // x holds every completed update: flush what the iteration before left pending
@@ -542,7 +407,7 @@ int mgs_pcg_plan_solve(mgs_pcg_plan *P, mgs_vec *x, const mgs_vec *b, int ahead,
     // the recursion had drifted: r holds the true residual, start over from it.  The iterations enqueued past i ran frozen and are enqueued again.
     MGS_TRY(step(P, STEP_RESTART, i, resid, false));
     P->restarts++;
-    first = true; next = i + 1; seen = i; outq.clear();
+    first = true; la.restart(i);
     L.frozen = 0; L.resid = resid; L.it = i;
   }
   // the iterations are used up (maxit = 0: INIT alone, nothing pending)

@@ -361,3 +361,20 @@ def test_determinism(ctx, mg, p31):
         x = ctx.vec(n); r = plan.enqueue(x, p31.b, 30, 1e-10).result()
         runs.append((r, x.numpy(), plan.info()[2:4]))
     assert runs[0][0] == runs[1][0] and np.array_equal(runs[0][1], runs[1][1]) and runs[0][2] == runs[1][2]
+
+
+def test_close(ctx, mg):
+    """10. close() twice, then letting the object go, raises nothing; a fresh plan on the same matrix solves to the same bits as before"""
+    A = ctx.poisson3d(8); n = 8 ** 3
+    b = ctx.vec(n).rand(seed=0)
+    plan = mg.PcgPlan(A)
+    x = ctx.vec(n); want = plan.solve(x, b, 200, 1e-10); xw = x.numpy()
+    assert want[0] == 0 and want[1] > 1
+    plan.close()
+    plan.close()
+    assert not plan.h
+    del plan
+    fresh = mg.PcgPlan(A)
+    y = ctx.vec(n); got = fresh.solve(y, b, 200, 1e-10)
+    same(got, y.numpy(), want, xw, "fresh plan")
+    fresh.close()

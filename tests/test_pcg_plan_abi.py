@@ -29,7 +29,7 @@ def test_declared_exported_prototyped():
     assert PROTOTYPES["mgs_pcg_plan_enqueue"][1][4] is C.c_double and PROTOTYPES["mgs_pcg_plan_solve"][1][3] is C.c_int
     # the handle type counts as the seventh name of the section
     assert callable(mg.PcgPlan)
-    for meth in ("solve", "enqueue", "result", "info"):
+    for meth in ("solve", "enqueue", "result", "info", "close"):
         assert callable(getattr(mg.PcgPlan, meth))
 
 

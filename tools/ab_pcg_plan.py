@@ -33,6 +33,7 @@ def child(method, size):
     b = ctx.vec(n).rand(seed=0)
     x = ctx.vec(n)
     out = {"method": method, "size": size, "rows": n, "levels": h.nlev}
+    plan = None
     if method == "pcg":
         mg.pcg(A, x, b, h, MAXIT, TOL)                                 # warm-up
         x.fill(0.0); ctx.sync(); t0 = time.perf_counter()
@@ -62,6 +63,8 @@ def child(method, size):
     true = A.residual(x, b).nrm2() / b.nrm2()
     out.update(status=st, it=it, s=round(dt, 5), reported=res, true_res=true)
     print(json.dumps(out), flush=True)
+    if plan is not None:
+        plan.close()
     ctx.close()
     return 0 if st == 0 else 3
 
