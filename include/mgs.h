@@ -211,6 +211,48 @@ int mgs_csr_galerkin(const mgs_csr *A, const mgs_xfer *P, mgs_csr **out);
 int mgs_csr_spgemm(const mgs_csr *A, const mgs_csr *B, mgs_csr **C);
 int mgs_csr_spgemm_numeric(const mgs_csr *A, const mgs_csr *B, mgs_csr *C, int64_t *misses);
 int mgs_csr_spgemm_info(const mgs_csr *C, int64_t out[4]);
+/* ---- sums and scalings of device matrices ----
+ * Nearest reference line: none — the reference multiplies matrices (bicg.cpp:32-33) and reads its operators from files
+ * (MatrixIO.cpp:12-37); sums such as M/Δt + K, A + σI or AᵀA + λI and the D⁻¹ of B·D⁻¹·Bᵀ are assembled by its callers before that.
+ * mgs_csr_add — C = α·A + β·B for A and B of one shape and one context (A == B, the same handle, is allowed).  C is an ordinary matrix,
+ * indistinguishable from an uploaded one (launch plan, mgs_csr_optimize, hierarchies, the Krylov solvers, mgs_csr_update_values*, a factor
+ * of mgs_csr_spgemm or of another sum); it carries no null-space declaration and no origin.  The pattern is structural: the union of the
+ * two stored patterns, columns ascending inside a row; an entry whose sum cancels or whose value is 0 stays an entry (the pattern is what
+ * mgs_hier_refresh keys on).  The work is enqueued on the context's stream and the call synchronises before it returns, as
+ * mgs_csr_upload and mgs_csr_spgemm do (it needs counts on the host).
+ * Arithmetic, which makes the result bit-reproducible and restatable on a host: every product and every sum is rounded separately (no
+ * fused multiply-add).  An entry stored only in A is fl(α·a), one stored only in B is fl(β·b), one stored in both is
+ * fl(fl(α·a) + fl(β·b)); a lone -0.0 stays -0.0.  No atomics on values: two identical calls give identical bits.
+ * Rows are binned by u_i = len_A(i) + len_B(i): u_i <= 64 is merged by one lane, a longer row by one wave in chunks of 64 entries
+ * without staging it anywhere, so there is no limit on the length of a row.
+ * MGS_ERR_INVALID, with a message: a NULL argument; different contexts; different shapes (the message gives both); a row shard as either
+ * operand (see mgs_csr_spgemm); a union of 2^31 - 1 entries or more.  On failure nothing is written to *C and everything the call
+ * allocated is released.
+ * mgs_csr_add_numeric — the values of C again, in place, from the current values of A and B (mgs_csr_update_values*) and the α, β given
+ * here, which may differ from the ones C was built with (a changed Δt).  Precondition: A and B have the patterns they had when C was
+ * built.  It runs the fill pass's own merge and writes values only, so the bits are those of a fresh mgs_csr_add; C's arrays do not
+ * move, so hierarchies built on C and their cached graphs stay valid (follow with mgs_hier_refresh); no allocation, no scan, at most two
+ * launches.  misses == NULL: enqueued on the context's stream with no host wait.  misses given: the call synchronises and writes the
+ * number of entries of A or B whose column is not at the computed place in C; MGS_ERR_STATE when that number is not 0 (C's values are
+ * then unspecified; nothing is written outside C's rows).  MGS_ERR_INVALID: a NULL matrix; different contexts; shapes that do not fit
+ * C; a C that mgs_csr_add did not build; a value-carrying pattern code on C (option "valcode").
+ * mgs_csr_add_info — diagnostics: out[0] rows merged by one lane, out[1] rows merged by one wave, out[2] longest row of C, out[3]
+ * entries stored in both A and B.  All four are 0 for a matrix that is not a sum.  MGS_ERR_INVALID: NULL argument.
+ * mgs_csr_scale — a_ij <- fl(fl(dl_i·a_ij)·dr_j) in place.  Either vector may be NULL: that factor is skipped (one rounding then, none
+ * and no launch if both are NULL).  One entry-parallel launch on the context's stream, no host wait.  The pattern, the launch plan and
+ * the pattern code stay: follow with mgs_hier_refresh on hierarchies built on A.  MGS_ERR_INVALID: A NULL; a vector of another context;
+ * dl shorter than rows or dr shorter than cols; a row shard; a value-carrying pattern code on A (option "valcode").
+ * mgs_csr_diag — d_i = a_ii for i < min(rows, cols), +0.0 where row i stores no diagonal entry; any shape; d holds at least
+ * min(rows, cols) entries; enqueued, no host wait.  MGS_ERR_INVALID: a NULL argument, another context, a shorter d.
+ * mgs_csr_from_diag — the n × n matrix with d_i stored at (i, i) for every i, zeros included, n = mgs_vec_size(d); an ordinary matrix
+ * (synchronises like mgs_csr_upload).  A + σI is mgs_csr_add with the diagonal matrix of a filled vector, M/Δt + K with a lumped mass
+ * vector likewise.  MGS_ERR_INVALID: a NULL argument, a vector of another context, n >= 2^31 - 1. */
+int mgs_csr_add(double alpha, const mgs_csr *A, double beta, const mgs_csr *B, mgs_csr **C);
+int mgs_csr_add_numeric(double alpha, const mgs_csr *A, double beta, const mgs_csr *B, mgs_csr *C, int64_t *misses);
+int mgs_csr_add_info(const mgs_csr *C, int64_t out[4]);
+int mgs_csr_scale(mgs_csr *A, const mgs_vec *dl, const mgs_vec *dr);
+int mgs_csr_diag(const mgs_csr *A, mgs_vec *d);
+int mgs_csr_from_diag(mgs_ctx *ctx, const mgs_vec *d, mgs_csr **out);
 
 /* -------------------------------------------------------------------- device vectors */
 /* Eigen::VectorXd on the device (bicg.cpp:153-162).                                    */

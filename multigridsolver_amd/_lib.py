@@ -93,6 +93,12 @@ PROTOTYPES = {
     "mgs_csr_spgemm": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "mgs_csr_spgemm_numeric": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_i64_p]),
     "mgs_csr_spgemm_info": (C.c_int, [C.c_void_p, c_i64_p]),
+    "mgs_csr_add": (C.c_int, [C.c_double, C.c_void_p, C.c_double, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "mgs_csr_add_numeric": (C.c_int, [C.c_double, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, c_i64_p]),
+    "mgs_csr_add_info": (C.c_int, [C.c_void_p, c_i64_p]),
+    "mgs_csr_scale": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mgs_csr_diag": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mgs_csr_from_diag": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "mgs_vec_create": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]),
     "mgs_vec_wrap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]),
     "mgs_vec_destroy": (C.c_int, [C.c_void_p]),

@@ -336,6 +336,54 @@ class Csr:
         out = (C.c_int64 * 4)(); check(lib().mgs_csr_spgemm_info(self.h, out), self.ctx.h)
         return dict(zip(["lane_rows", "workgroup_rows", "max_row_len", "max_row_products"], [int(v) for v in out]))
 
+    def add(self, B, alpha=1.0, beta=1.0):
+        """C = alpha·self + beta·B on the device (mgs_csr_add): the union of the two patterns, ascending columns, every product and sum
+        rounded on its own"""
+        if not isinstance(B, Csr):
+            raise TypeError(f"add: a Csr expected, got {type(B).__name__}")
+        h = C.c_void_p(); check(lib().mgs_csr_add(float(alpha), self.h, float(beta), B.h, C.byref(h)), self.ctx.h); return Csr(self.ctx, h)
+
+    def __add__(self, B):
+        return self.add(B) if isinstance(B, Csr) else NotImplemented
+
+    def __sub__(self, B):
+        return self.add(B, 1.0, -1.0) if isinstance(B, Csr) else NotImplemented
+
+    def add_update(self, A, B, alpha=1.0, beta=1.0, check=False):
+        """this matrix = A.add(B, ...) built earlier: its values again, in place, from the current values of A and B with their patterns
+        unchanged and the alpha, beta given here (mgs_csr_add_numeric); returns self.  check=False: enqueued, no host wait.  check=True:
+        synchronises and raises MgsError (MGS_ERR_STATE, .misses set) when entries are not at their place in this matrix's pattern.
+        Follow with Hierarchy.refresh()."""
+        if not check:
+            _check(lib().mgs_csr_add_numeric(float(alpha), A.h, float(beta), B.h, self.h, None), self.ctx.h); return self
+        m = C.c_int64(-1)
+        try:
+            _check(lib().mgs_csr_add_numeric(float(alpha), A.h, float(beta), B.h, self.h, C.byref(m)), self.ctx.h)
+        except MgsError as e:
+            e.misses = int(m.value)
+            raise
+        return self
+
+    def add_info(self):
+        out = (C.c_int64 * 4)(); check(lib().mgs_csr_add_info(self.h, out), self.ctx.h)
+        return dict(zip(["lane_rows", "wave_rows", "max_row_len", "common_entries"], [int(v) for v in out]))
+
+    def scale(self, left=None, right=None):
+        """a_ij ← (left_i·a_ij)·right_j in place (mgs_csr_scale; either Vec may be None: that factor is skipped); enqueued, returns self.
+        Follow with Hierarchy.refresh() on hierarchies built on this matrix."""
+        check(lib().mgs_csr_scale(self.h, left.h if left is not None else None, right.h if right is not None else None), self.ctx.h); return self
+
+    def diagonal(self):
+        """Vec of min(rows, cols) entries: a_ii, 0.0 where row i stores no diagonal entry (mgs_csr_diag)"""
+        d = Vec(self.ctx, min(self.shape)); check(lib().mgs_csr_diag(self.h, d.h), self.ctx.h); return d
+
+    @staticmethod
+    def from_diag(ctx, vec):
+        """the n × n matrix with vec_i stored at (i, i), zeros included (mgs_csr_from_diag)"""
+        if not isinstance(vec, Vec):
+            raise TypeError(f"from_diag: a Vec expected, got {type(vec).__name__}")
+        h = C.c_void_p(); check(lib().mgs_csr_from_diag(ctx.h, vec.h, C.byref(h)), ctx.h); return Csr(ctx, h)
+
     def spmv(self, x, y=None):
         y = y or Vec(self.ctx, self.shape[0])
         check(lib().mgs_spmv(self.h, x.h, y.h), self.ctx.h); return y

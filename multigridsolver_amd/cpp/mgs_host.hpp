@@ -184,6 +184,30 @@ class DeviceMatrix {
   void multiplyUpdate(const DeviceMatrix &A, const DeviceMatrix &B, int64_t *misses = nullptr) {
     check(mgs_csr_spgemm_numeric(A.a_.get(), B.a_.get(), a_.get(), misses), context());
   }
+  // C = alpha·(*this) + beta·B on the device (mgs.h: mgs_csr_add; no reference counterpart): the union of the two patterns, ascending
+  // columns, every product and sum rounded on its own.  addUpdate: this matrix is A.add(B, ...) built earlier — its values again, in
+  // place, from the current values of A and B with their patterns unchanged and the scalars given here (mgs_csr_add_numeric); `misses`
+  // as in multiplyUpdate.  scale: a_ij ← (dl_i·a_ij)·dr_j in place, either vector may be NULL (mgs_csr_scale; enqueued).  diagonal /
+  // fromDiagonal: the diagonal as a vector (0 where none is stored) and a vector as a diagonal matrix (mgs_csr_diag, mgs_csr_from_diag).
+  DeviceMatrix add(const DeviceMatrix &B, double alpha = 1.0, double beta = 1.0) const {
+    mgs_csr *p = nullptr;
+    check(mgs_csr_add(alpha, a_.get(), beta, B.a_.get(), &p), context());
+    return adopt(p, rows_, cols_);
+  }
+  void addUpdate(const DeviceMatrix &A, const DeviceMatrix &B, double alpha = 1.0, double beta = 1.0, int64_t *misses = nullptr) {
+    check(mgs_csr_add_numeric(alpha, A.a_.get(), beta, B.a_.get(), a_.get(), misses), context());
+  }
+  void scale(const Vector *dl, const Vector *dr) {
+    check(mgs_csr_scale(a_.get(), dl ? dl->handle() : nullptr, dr ? dr->handle() : nullptr), context());
+  }
+  Vector diagonal() const {
+    Vector d(rows_ < cols_ ? rows_ : cols_); check(mgs_csr_diag(a_.get(), d.out()), context()); return d;
+  }
+  static DeviceMatrix fromDiagonal(const Vector &d) {
+    mgs_csr *p = nullptr;
+    check(mgs_csr_from_diag(context(), d.handle(), &p), context());
+    return adopt(p, (int)d.size(), (int)d.size());
+  }
   Vector operator*(const Vector &x) const {            // bicg.cpp:57,82,107,117
     Vector y(rows_); check(mgs_spmv(a_.get(), x.handle(), y.out()), context()); return y;
   }

@@ -422,6 +422,7 @@ int mgs_csr_destroy(mgs_csr *A) {
   if (A->origin) mgs_hip_free(A->origin);
   mgs_free_rowcode(A->code);
   mgs_free_spgemm(A->spg);
+  mgs_free_add(A->addp);
   delete A;
   return MGS_OK;
 }
@@ -501,6 +502,15 @@ int mgs_csr_galerkin(const mgs_csr *A, const mgs_xfer *T, mgs_csr **out) {
 int mgs_csr_spgemm(const mgs_csr *A, const mgs_csr *B, mgs_csr **C) { return k_spgemm(A, B, C); }
 int mgs_csr_spgemm_numeric(const mgs_csr *A, const mgs_csr *B, mgs_csr *C, int64_t *misses) { return k_spgemm_numeric(A, B, C, misses); }
 int mgs_csr_spgemm_info(const mgs_csr *C, int64_t out[4]) { return k_spgemm_info(C, out); }
+// sums and scalings on the device (csr_algebra.hip)
+int mgs_csr_add(double alpha, const mgs_csr *A, double beta, const mgs_csr *B, mgs_csr **C) { return k_csr_add(alpha, A, beta, B, C); }
+int mgs_csr_add_numeric(double alpha, const mgs_csr *A, double beta, const mgs_csr *B, mgs_csr *C, int64_t *misses) {
+  return k_csr_add_numeric(alpha, A, beta, B, C, misses);
+}
+int mgs_csr_add_info(const mgs_csr *C, int64_t out[4]) { return k_csr_add_info(C, out); }
+int mgs_csr_scale(mgs_csr *A, const mgs_vec *dl, const mgs_vec *dr) { return k_csr_scale(A, dl, dr); }
+int mgs_csr_diag(const mgs_csr *A, mgs_vec *d) { return k_csr_diag(A, d); }
+int mgs_csr_from_diag(mgs_ctx *ctx, const mgs_vec *d, mgs_csr **out) { return k_csr_from_diag(ctx, d, out); }
 
 // ------------------------------------------------------------------ vectors
 int mgs_vec_create(mgs_ctx *ctx, int64_t n, mgs_vec **out) {

@@ -164,6 +164,7 @@ struct mgs_csr {
   int coo_max_row = 0;      // most triples one row received
   int nullspace = MGS_NULLSPACE_NONE;   // mgs_csr_set_nullspace: what the caller declared (hierarchies and Krylov solvers act on it)
   struct mgs_spgemm_plan *spg = nullptr;   // matrices built by mgs_csr_spgemm (spgemm.hip; owned): the row bins its numeric pass launches over
+  struct mgs_add_plan *addp = nullptr;     // matrices built by mgs_csr_add (csr_algebra.hip; owned): the row bins mgs_csr_add_numeric launches over
   bool halo_cols = false;   // generated as a row shard (mgs_csr_poisson3d on a plane range): the columns beyond the rows are halo columns
 };
 // a row shard as far as the library can tell: more columns than rows AND generated as a shard or living in a context that sums over ranks
@@ -492,6 +493,14 @@ int k_spgemm(const mgs_csr *A, const mgs_csr *B, mgs_csr **out);
 int k_spgemm_numeric(const mgs_csr *A, const mgs_csr *B, mgs_csr *C, int64_t *misses);
 int k_spgemm_info(const mgs_csr *C, int64_t out[4]);
 void mgs_free_spgemm(struct mgs_spgemm_plan *p);
+// (csr_algebra.hip) C = α·A + β·B with the union pattern, its values again in place, diagonal scalings, the diagonal as a vector and back
+int k_csr_add(double alpha, const mgs_csr *A, double beta, const mgs_csr *B, mgs_csr **out);
+int k_csr_add_numeric(double alpha, const mgs_csr *A, double beta, const mgs_csr *B, mgs_csr *C, int64_t *misses);
+int k_csr_add_info(const mgs_csr *C, int64_t out[4]);
+int k_csr_scale(mgs_csr *A, const mgs_vec *dl, const mgs_vec *dr);
+int k_csr_diag(const mgs_csr *A, mgs_vec *d);
+int k_csr_from_diag(mgs_ctx *ctx, const mgs_vec *d, mgs_csr **out);
+void mgs_free_add(struct mgs_add_plan *p);
 
 // helpers (mgs_api.hip)
 int mgs_csr_alloc(mgs_ctx *ctx, int rows, int cols, int64_t nnz, mgs_csr **out);
