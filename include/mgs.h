@@ -425,6 +425,10 @@ int mgs_hier_level_shape(const mgs_hier *h, int level, int *rows, int64_t *nnz);
 /* borrowed handles of level operators / transfer (valid while h lives)                */
 const mgs_csr *mgs_hier_level_A(const mgs_hier *h, int level);
 const mgs_xfer *mgs_hier_level_P(const mgs_hier *h, int level);
+/* A·P of `level`, the fused post pass's operand under option merge_ap (rows of A, one column per aggregate, built by the first cycle
+ * and kept current by mgs_hier_refresh): borrowed and read-only like the two above; NULL while it has not been built (no cycle yet,
+ * merge_ap off, a general P, the coarsest level) and on out-of-range levels                                                      */
+const mgs_csr *mgs_hier_level_AP(const mgs_hier *h, int level);
 /* aggregate id of every fine row of `level` (−1 = not aggregated, G0) to host         */
 int mgs_xfer_download_agg(const mgs_xfer *T, int *agg);
 /* algorithmic HBM bytes of one V-cycle application (DESIGN.md §5 formula)             */

@@ -138,6 +138,7 @@ PROTOTYPES = {
     "mgs_hier_level_shape": (C.c_int, [C.c_void_p, C.c_int, c_int_p, c_i64_p]),
     "mgs_hier_level_A": (C.c_void_p, [C.c_void_p, C.c_int]),
     "mgs_hier_level_P": (C.c_void_p, [C.c_void_p, C.c_int]),
+    "mgs_hier_level_AP": (C.c_void_p, [C.c_void_p, C.c_int]),
     "mgs_hier_vcycle_bytes": (C.c_int64, [C.c_void_p]),
     "mgs_vcycle": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "mgs_bicgstab": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_int_p, c_dbl_p, c_int_p]),

@@ -580,6 +580,16 @@ class Hierarchy:
         M._hier = self      # a view into this hierarchy: it keeps the hierarchy alive, so h.level_A(l) may outlive the name h
         return M
 
+    def level_AP(self, l):
+        """A·P of level l, the fused post pass's operand (mgs_hier_level_AP): a read-only view like level_A, or None while it has
+        not been built (no cycle yet, option merge_ap off, the coarsest level)"""
+        p = lib().mgs_hier_level_AP(self.h, l)
+        if not p:
+            return None
+        M = Csr(self.ctx, C.c_void_p(p), owned=False)
+        M._hier = self
+        return M
+
     def level_P(self, l):
         T = Xfer(self.ctx, C.c_void_p(lib().mgs_hier_level_P(self.h, l)), owned=False)
         T._hier = self      # as level_A: Hierarchy(...).coarsen(...).level_P(0).agg() must not read a destroyed hierarchy

@@ -1062,6 +1062,7 @@ int mgs_hier_level_shape(const mgs_hier *h, int l, int *rows, int64_t *nnz) {
 }
 const mgs_csr *mgs_hier_level_A(const mgs_hier *h, int l) { return (l >= 0 && l < (int)h->lev.size()) ? h->lev[l].A : nullptr; }
 const mgs_xfer *mgs_hier_level_P(const mgs_hier *h, int l) { return (l >= 0 && l < (int)h->lev.size()) ? h->lev[l].T : nullptr; }
+const mgs_csr *mgs_hier_level_AP(const mgs_hier *h, int l) { return (h && l >= 0 && l < (int)h->lev.size()) ? h->lev[l].AP : nullptr; }
 
 static int push_level(mgs_hier *h, mgs_xfer *T, mgs_csr *Ac) {
   h->lev.back().T = T;

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import agmg_ref
+import galerkin_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -1154,6 +1155,10 @@ def test_random_aggregations_and_graph_laplacians(ctx, mg, orc):
         Ac = A.galerkin(T); rp, ci, v = Ac.download(); Aco = Ao.galerkin(Po)
         assert np.array_equal(rp, Aco.rowptr) and np.array_equal(ci, Aco.col)
         assert np.max(np.abs(v - Aco.val)) <= 1e-13 * max(1.0, np.abs(Aco.val).max())
+        # ... and bit for bit against the restatement of the product's own order (tests/galerkin_ref.py)
+        cptr, members = galerkin_ref.member_lists(agg, nc)
+        want = galerkin_ref.galerkin_agg(Ao.rowptr, Ao.col, Ao.val, agg, members, cptr, nc)
+        assert np.array_equal(rp, want[0]) and np.array_equal(ci, want[1]) and galerkin_ref.same_bits(v, want[2]), trial
         # device-built hierarchy and cycle vs the oracle cycle on the downloaded hierarchy
         h = mg.Hierarchy(A, 0.6, 1, 1).coarsen(10.0, 2, 8.0, coarse_rows=40, max_levels=8).finalize()
         Ps = []
@@ -1192,6 +1197,9 @@ def test_galerkin_and_merged_operand_with_long_rows(ctx, mg, orc):
     assert np.diff(rp).max() > 64                                    # the spill path ran
     assert np.array_equal(rp, Aco.rowptr) and np.array_equal(ci, Aco.col)
     assert np.max(np.abs(v - Aco.val)) <= 1e-13 * max(1.0, np.abs(Aco.val).max())
+    cptr, members = galerkin_ref.member_lists(agg, nc)     # bit for bit against the restatement of the product's own order
+    want = galerkin_ref.galerkin_agg(Ao.rowptr, Ao.col, Ao.val, agg, members, cptr, nc)
+    assert np.array_equal(rp, want[0]) and np.array_equal(ci, want[1]) and galerkin_ref.same_bits(v, want[2])
     h = mg.Hierarchy(A, 0.6, 1, 1).push_P(dev(ctx, Po)).finalize()
     b_np = rng.standard_normal(n)
     ho = orc.Hier(Ao, [Po], omega=0.6, nu1=1, nu2=1)

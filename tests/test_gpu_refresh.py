@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import scipy.sparse as sps
 
+from galerkin_ref import galerkin_restated
+
 pytestmark = pytest.mark.gpu
 
 OK, INVALID, NUMERIC, STATE = 0, -1, -5, -6
@@ -78,26 +80,6 @@ def built(ctx, mg, n, rp, ci, v, omega=0.6):
     b = ctx.vec(n).rand(seed=11)
     h.vcycle(b)
     return A, h, b
-
-
-def galerkin_restated(rp, ci, v, g, nc):
-    """level-1 values: every (coarse row, coarse column) group summed sequentially, member rows ascending, entries in storage order"""
-    rows = np.repeat(np.arange(len(rp) - 1, dtype=np.int64), np.diff(rp))
-    I, J = g[rows].astype(np.int64), g[ci].astype(np.int64)
-    keep = (I >= 0) & (J >= 0)
-    I, J, val = I[keep], J[keep], v[keep]
-    key = I * nc + J
-    order = np.argsort(key, kind="stable")          # stable: fine row ascending, then storage order, inside one group
-    key, val = key[order], val[order]
-    first = np.flatnonzero(np.r_[True, key[1:] != key[:-1]])
-    size = np.diff(np.r_[first, len(key)])
-    acc = val[first].copy()
-    for j in range(1, int(size.max())):
-        m = size > j
-        acc[m] = acc[m] + val[first[m] + j]
-    M = sps.csr_matrix((acc, (key[first] // nc, key[first] % nc)), shape=(nc, nc))
-    M.sort_indices()
-    return M
 
 
 def test_refresh_is_the_twin_bit_for_bit(ctx, mg, pair24):
