@@ -253,6 +253,53 @@ int mgs_csr_add_info(const mgs_csr *C, int64_t out[4]);
 int mgs_csr_scale(mgs_csr *A, const mgs_vec *dl, const mgs_vec *dr);
 int mgs_csr_diag(const mgs_csr *A, mgs_vec *d);
 int mgs_csr_from_diag(mgs_ctx *ctx, const mgs_vec *d, mgs_csr **out);
+/* ---- blocks of a device matrix, gather and scatter of a vector by an index list ----
+ * Nearest reference line: none — the reference reads whole operators from files (MatrixIO.cpp:12-37); the blocks of a reduced system
+ * A_ff·x_f = b_f - A_fc·g (essential boundary conditions), of a Schur complement A_cc - A_cf·D_ff⁻¹·A_fc or of a field split are cut out by
+ * its callers before that.
+ * mgs_csr_extract — S = A(rows, cols): row k of S is row rows[k] of A restricted to the listed columns, column cols[q] renumbered to q;
+ * S is nr × nc.  The lists are arrays in device memory (make them visible first) of index_bits = 32 or 64 bits per entry, one width for
+ * both, as in mgs_csr_from_device.  rows_dev == NULL: every row in order, nr is ignored and S has A's rows.  A given row list may be
+ * in any order and may repeat rows.  cols_dev == NULL: every column, nc is ignored and S has A's columns.  A given column list must be
+ * strictly ascending: that keeps every row of S ascending without a sort and makes the list free of duplicates; a general column
+ * permutation is out of scope.  No kernel uses a list entry as an address before it has compared it with its bounds; 64-bit entries
+ * are compared as 64-bit values before they are narrowed.  Value bits are copied unchanged: -0.0 stays -0.0 and a NaN keeps its payload.
+ * The pattern is structural: stored zeros stay entries (the pattern is what mgs_hier_refresh keys on).  S is an ordinary matrix,
+ * indistinguishable from an uploaded one (launch plan, mgs_csr_optimize, hierarchies, the Krylov solvers, a factor of mgs_csr_spgemm or
+ * mgs_csr_add); it carries no null-space declaration and no origin.  The work is enqueued on the context's stream and the call
+ * synchronises before it returns, as mgs_csr_add does (it needs counts on the host).  Without a column list an output entry finds
+ * its row by bisection and is copied, entry-parallel; with one, an output row whose source row holds at most 64 entries is served by
+ * one lane and a longer one by one wave in chunks of 64 entries without staging it anywhere, so there is no limit on the length of a
+ * row.  Every place is computed from the row alone, no atomics on values or places: two identical calls give identical arrays.
+ * MGS_ERR_INVALID, with a message: a NULL A or S; index_bits neither 32 nor 64; a negative nr or nc; a row index outside [0, A->rows)
+ * (the message names the lowest offending position in the list and its value); a column index outside [0, A->cols), named likewise; a
+ * column list that is not strictly ascending (the message names the lowest position k with cols[k] <= cols[k-1]; of several column
+ * violations the one at the lowest position is reported, a row violation before any of them); a row shard as A (see mgs_csr_spgemm);
+ * a result of 2^31 - 1 entries or more (repeated rows can cause it: the total is kept in 64 bits).  On failure nothing is written to
+ * *S and everything the call allocated is released.
+ * keep_map != 0: S keeps the position in A's arrays of every entry (4 B per entry of S, freed by mgs_csr_destroy) and records A's rows,
+ * columns and number of entries.
+ * mgs_csr_extract_numeric — S.val[k] = A.val[src[k]] through the kept map, for an A whose values changed and whose pattern did not
+ * (mgs_csr_update_values*, *_numeric): one entry-parallel launch on the context's stream, no host wait, no allocation, no scan; the bits
+ * are those of a fresh mgs_csr_extract.  S's arrays do not move, so hierarchies built on S and their cached graphs stay valid (follow with
+ * mgs_hier_refresh).  MGS_ERR_STATE: S keeps no map.  MGS_ERR_INVALID: a NULL handle; different contexts; an A whose rows, columns or
+ * number of entries differ from those recorded; a value-carrying pattern code on S (option "valcode").
+ * mgs_csr_extract_info — diagnostics: out[0] rows counted by one lane, out[1] rows counted by one wave, out[2] longest row of S, out[3]
+ * bytes of the kept map.  All four are 0 for a matrix that mgs_csr_extract did not build; out[0] and out[1] are 0 for cols_dev == NULL
+ * (no pass over columns).  MGS_ERR_INVALID: NULL argument.
+ * mgs_vec_gather — y[k] = x[idx[k]] for k < n; indices may repeat.  mgs_vec_scatter — x[idx[k]] = y[k] for k < n; the indices must be
+ * distinct: with repeats the entry holds one of the values, unspecified which.  Each is one launch on the context's stream.  Every index
+ * is compared with [0, mgs_vec_size(x)) in the kernel, as a 64-bit value, and an index outside is never used: gather stores +0.0 at
+ * that place of y, scatter skips it.  bad == NULL: the call is enqueued with no host wait.  bad given: the call synchronises and writes
+ * the number of indices outside the range; MGS_ERR_INVALID when that number is not 0.  MGS_ERR_INVALID also: a NULL argument; vectors
+ * of different contexts; n < 0 or n above the length of y (the compact side in both calls); index_bits neither 32 nor 64; x and y the
+ * same array. */
+int mgs_csr_extract(const mgs_csr *A, const void *rows_dev, int64_t nr, const void *cols_dev, int64_t nc,
+                    int index_bits, int keep_map, mgs_csr **S);
+int mgs_csr_extract_numeric(const mgs_csr *A, mgs_csr *S);
+int mgs_csr_extract_info(const mgs_csr *S, int64_t out[4]);
+int mgs_vec_gather(const mgs_vec *x, const void *idx_dev, int64_t n, int index_bits, mgs_vec *y, int64_t *bad);
+int mgs_vec_scatter(const mgs_vec *y, const void *idx_dev, int64_t n, int index_bits, mgs_vec *x, int64_t *bad);
 
 /* -------------------------------------------------------------------- device vectors */
 /* Eigen::VectorXd on the device (bicg.cpp:153-162).                                    */

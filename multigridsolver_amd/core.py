@@ -384,6 +384,31 @@ class Csr:
             raise TypeError(f"from_diag: a Vec expected, got {type(vec).__name__}")
         h = C.c_void_p(); check(lib().mgs_csr_from_diag(ctx.h, vec.h, C.byref(h)), ctx.h); return Csr(ctx, h)
 
+    def extract(self, rows=None, cols=None, keep_map=False):
+        """S = self[rows][:, cols] on the device (mgs_csr_extract): index lists on the context's device (torch tensors or objects with
+        __cuda_array_interface__, int32 or int64, one width for both; make them visible first); None: every row / every column.  rows
+        in any order, repeats allowed; cols strictly ascending, column cols[q] becomes q.  Value bits are copied unchanged.
+        keep_map=True keeps what extract_update needs."""
+        ptr, n, bits = [None, None], [0, 0], [0, 0]
+        for k, (name, a) in enumerate((("rows", rows), ("cols", cols))):
+            if a is not None:
+                p, n[k], bits[k] = _dev_array(self.ctx, a, name, True)
+                ptr[k] = C.c_void_p(p or self.device_ptrs()[0])      # an empty list has no address of its own: any device address, never read
+        if bits[0] and bits[1] and bits[0] != bits[1]:
+            raise TypeError(f"rows holds {bits[0]}-bit indices, cols {bits[1]}-bit ones")
+        h = C.c_void_p()
+        check(lib().mgs_csr_extract(self.h, ptr[0], n[0], ptr[1], n[1], bits[0] or bits[1] or 32, int(bool(keep_map)), C.byref(h)), self.ctx.h)
+        return Csr(self.ctx, h)
+
+    def extract_update(self, A):
+        """this matrix = A.extract(..., keep_map=True) built earlier: its values again, in place, from the current values of A with its
+        pattern unchanged (mgs_csr_extract_numeric; enqueued, no host wait); returns self.  Follow with Hierarchy.refresh()."""
+        check(lib().mgs_csr_extract_numeric(A.h, self.h), A.ctx.h); return self      # the call reports on A's context
+
+    def extract_info(self):
+        out = (C.c_int64 * 4)(); check(lib().mgs_csr_extract_info(self.h, out), self.ctx.h)
+        return dict(zip(["lane_rows", "wave_rows", "max_row_len", "map_bytes"], [int(v) for v in out]))
+
     def spmv(self, x, y=None):
         y = y or Vec(self.ctx, self.shape[0])
         check(lib().mgs_spmv(self.h, x.h, y.h), self.ctx.h); return y
@@ -448,6 +473,30 @@ class Vec:
 
     def copy_from(self, src):
         check(lib().mgs_vec_copy(src.h, self.h), self.ctx.h); return self
+
+    def _indexed(self, fn, a, idx, b, check):
+        p, n, bits = _dev_array(self.ctx, idx, "idx", True)
+        if not check:
+            _check(fn(a.h, C.c_void_p(p), n, bits, b.h, None), a.ctx.h); return      # the calls report on their first vector's context
+        bad = C.c_int64(-1)
+        try:
+            _check(fn(a.h, C.c_void_p(p), n, bits, b.h, C.byref(bad)), a.ctx.h)
+        except MgsError as e:
+            e.bad = int(bad.value)
+            raise
+
+    def gather(self, idx, out=None, check=False):
+        """out[k] = self[idx[k]] (mgs_vec_gather): idx an int32 or int64 index list on the context's device, repeats allowed; an index
+        outside the vector is never used, out holds +0.0 there.  check=False: enqueued, no host wait.  check=True: synchronises and
+        raises MgsError (MGS_ERR_INVALID, .bad = the number of such indices).  Returns out (a new Vec of len(idx) entries if None)."""
+        if out is None:
+            out = Vec(self.ctx, _dev_array(self.ctx, idx, "idx", True)[1])
+        self._indexed(lib().mgs_vec_gather, self, idx, out, check); return out
+
+    def scatter(self, idx, src, check=False):
+        """self[idx[k]] = src[k] (mgs_vec_scatter): the indices must be distinct (with repeats the entry holds one of the values); an
+        index outside the vector is skipped; check as in gather.  Returns self."""
+        self._indexed(lib().mgs_vec_scatter, src, idx, self, check); return self
 
     def dot(self, other):
         out = C.c_double(); check(lib().mgs_dot(self.h, other.h, C.byref(out)), self.ctx.h); return out.value

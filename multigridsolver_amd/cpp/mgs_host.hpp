@@ -106,6 +106,16 @@ class Vector {
   void setZero() { check(mgs_vec_fill(out(), 0.0), context()); }
   void upload(const std::vector<double> &h) { check(mgs_vec_upload(out(), h.data(), (int64_t)h.size()), context()); }
   std::vector<double> download() const { std::vector<double> h((size_t)size()); check(mgs_vec_download(handle(), h.data(), size()), context()); return h; }
+  // y[k] = (*this)[idx[k]] and x[idx[k]] = (*this)[k] for k < n (mgs.h: mgs_vec_gather, mgs_vec_scatter, in the C argument order): idx in
+  // device memory, index_bits 32 or 64; an index outside the indexed vector is never used (gather stores +0.0, scatter skips it).
+  // Without `bad` the call is enqueued only; with it the call synchronises, writes the number of such indices and throws
+  // Error(MGS_ERR_INVALID) when that is not 0.
+  void gather(const void *idx_dev, int64_t n, int index_bits, Vector &y, int64_t *bad = nullptr) const {
+    check(mgs_vec_gather(handle(), idx_dev, n, index_bits, y.out(), bad), context());
+  }
+  void scatter(const void *idx_dev, int64_t n, int index_bits, Vector &x, int64_t *bad = nullptr) const {
+    check(mgs_vec_scatter(handle(), idx_dev, n, index_bits, x.out(), bad), context());
+  }
   double dot(const Vector &o) const { double s; check(mgs_dot(handle(), o.handle(), &s), context()); return s; }
   double norm() const { double s; check(mgs_nrm2(handle(), &s), context()); return s; }
   Vector &operator+=(const Vector &o) { check(mgs_axpby(1.0, o.handle(), 1.0, out()), context()); return *this; }
@@ -208,6 +218,17 @@ class DeviceMatrix {
     check(mgs_csr_from_diag(context(), d.handle(), &p), context());
     return adopt(p, (int)d.size(), (int)d.size());
   }
+  // S = (*this)(rows, cols) on the device (mgs.h: mgs_csr_extract; no reference counterpart): index lists in device memory, index_bits 32
+  // or 64 for both; a NULL list means every row / every column (its length is then ignored).  Rows in any order, repeats allowed;
+  // columns strictly ascending, column cols[q] becomes q; value bits are copied unchanged.  keepMap keeps what extractUpdate needs.
+  // extractUpdate: this matrix is A.extract(..., keepMap = true) built earlier — its values again, in place, from the current values
+  // of A with its pattern unchanged (mgs_csr_extract_numeric; enqueued, no host wait).
+  DeviceMatrix extract(const void *rows_dev, int64_t nr, const void *cols_dev, int64_t nc, int index_bits = 32, bool keepMap = false) const {
+    mgs_csr *p = nullptr;
+    check(mgs_csr_extract(a_.get(), rows_dev, nr, cols_dev, nc, index_bits, keepMap ? 1 : 0, &p), context());
+    return adopt(p, rows_dev ? (int)nr : rows_, cols_dev ? (int)nc : cols_);
+  }
+  void extractUpdate(const DeviceMatrix &A) { check(mgs_csr_extract_numeric(A.a_.get(), a_.get()), context()); }
   Vector operator*(const Vector &x) const {            // bicg.cpp:57,82,107,117
     Vector y(rows_); check(mgs_spmv(a_.get(), x.handle(), y.out()), context()); return y;
   }

@@ -423,6 +423,7 @@ int mgs_csr_destroy(mgs_csr *A) {
   mgs_free_rowcode(A->code);
   mgs_free_spgemm(A->spg);
   mgs_free_add(A->addp);
+  mgs_free_extract(A->extp);
   delete A;
   return MGS_OK;
 }
@@ -511,6 +512,14 @@ int mgs_csr_add_info(const mgs_csr *C, int64_t out[4]) { return k_csr_add_info(C
 int mgs_csr_scale(mgs_csr *A, const mgs_vec *dl, const mgs_vec *dr) { return k_csr_scale(A, dl, dr); }
 int mgs_csr_diag(const mgs_csr *A, mgs_vec *d) { return k_csr_diag(A, d); }
 int mgs_csr_from_diag(mgs_ctx *ctx, const mgs_vec *d, mgs_csr **out) { return k_csr_from_diag(ctx, d, out); }
+// blocks of a device matrix, gather / scatter of a vector by an index list (extract.hip)
+int mgs_csr_extract(const mgs_csr *A, const void *rows_dev, int64_t nr, const void *cols_dev, int64_t nc, int index_bits, int keep_map, mgs_csr **S) {
+  return k_csr_extract(A, rows_dev, nr, cols_dev, nc, index_bits, keep_map, S);
+}
+int mgs_csr_extract_numeric(const mgs_csr *A, mgs_csr *S) { return k_csr_extract_numeric(A, S); }
+int mgs_csr_extract_info(const mgs_csr *S, int64_t out[4]) { return k_csr_extract_info(S, out); }
+int mgs_vec_gather(const mgs_vec *x, const void *idx_dev, int64_t n, int index_bits, mgs_vec *y, int64_t *bad) { return k_vec_gather(x, idx_dev, n, index_bits, y, bad); }
+int mgs_vec_scatter(const mgs_vec *y, const void *idx_dev, int64_t n, int index_bits, mgs_vec *x, int64_t *bad) { return k_vec_scatter(y, idx_dev, n, index_bits, x, bad); }
 
 // ------------------------------------------------------------------ vectors
 int mgs_vec_create(mgs_ctx *ctx, int64_t n, mgs_vec **out) {

@@ -165,6 +165,7 @@ struct mgs_csr {
   int nullspace = MGS_NULLSPACE_NONE;   // mgs_csr_set_nullspace: what the caller declared (hierarchies and Krylov solvers act on it)
   struct mgs_spgemm_plan *spg = nullptr;   // matrices built by mgs_csr_spgemm (spgemm.hip; owned): the row bins its numeric pass launches over
   struct mgs_add_plan *addp = nullptr;     // matrices built by mgs_csr_add (csr_algebra.hip; owned): the row bins mgs_csr_add_numeric launches over
+  struct mgs_extract_plan *extp = nullptr; // matrices built by mgs_csr_extract (extract.hip; owned): the bins it counted and, with keep_map, the source position of every entry
   bool halo_cols = false;   // generated as a row shard (mgs_csr_poisson3d on a plane range): the columns beyond the rows are halo columns
 };
 // a row shard as far as the library can tell: more columns than rows AND generated as a shard or living in a context that sums over ranks
@@ -501,6 +502,13 @@ int k_csr_scale(mgs_csr *A, const mgs_vec *dl, const mgs_vec *dr);
 int k_csr_diag(const mgs_csr *A, mgs_vec *d);
 int k_csr_from_diag(mgs_ctx *ctx, const mgs_vec *d, mgs_csr **out);
 void mgs_free_add(struct mgs_add_plan *p);
+// (extract.hip) S = A(rows, cols) from index lists in device memory, its values again through the kept map, gather / scatter of a vector by an index list
+int k_csr_extract(const mgs_csr *A, const void *rows_dev, int64_t nr, const void *cols_dev, int64_t nc, int index_bits, int keep_map, mgs_csr **out);
+int k_csr_extract_numeric(const mgs_csr *A, mgs_csr *S);
+int k_csr_extract_info(const mgs_csr *S, int64_t out[4]);
+int k_vec_gather(const mgs_vec *x, const void *idx_dev, int64_t n, int index_bits, mgs_vec *y, int64_t *bad);
+int k_vec_scatter(const mgs_vec *y, const void *idx_dev, int64_t n, int index_bits, mgs_vec *x, int64_t *bad);
+void mgs_free_extract(struct mgs_extract_plan *p);
 
 // helpers (mgs_api.hip)
 int mgs_csr_alloc(mgs_ctx *ctx, int rows, int cols, int64_t nnz, mgs_csr **out);
