@@ -457,6 +457,19 @@ int mgs_hier_set_kcycle(mgs_hier *h, int levels);
 /* K iteration on level 0 itself when the hierarchy is applied from x = 0: for the replicated tail of a row-sharded hierarchy whose
  * K-cycle reaches the last sharded level (that level is the tail's level 0; no rank reduction needed: the tail is replicated). */
 int mgs_hier_set_kcycle_entry(mgs_hier *h, int on);
+/* diagnostics: the five scalars of the last K step of `level` (levels 1..levels of mgs_hier_set_kcycle; level 0 under
+ * mgs_hier_set_kcycle_entry), copied from the device after waiting for the context's stream — read-only, the step is not run.  With
+ * c1 = B·rhs, v1 = A·c1, r' = rhs − (α1/ρ1)·v1, c2 = B·r', v2 = A·c2, g = γ/ρ1, c2' = c2 − g·c1, v2' = v2 − g·v1 (B = the cycle below):
+ *   out[0] ρ1   GCR form v1·v1     energy form (option kcycle_energy) c1·v1
+ *   out[1] α1            v1·rhs                                       c1·rhs
+ *   out[2] γ             v2·v1                                        c2·v1
+ *   out[3] ρ2            v2'·v2'                                      c2'·v2'
+ *   out[4] α2            v2'·r'                                       c2'·r'
+ * and the step returns x = k1·c1 + k2·c2 with k2 = α2/ρ2 where ρ2 > 0 (else 0) and k1 = α1/ρ1 − g·k2; ρ1 = 0 gives x = 0.  A quotient by
+ * ρ1 = 0 counts as 0 throughout.  All zero between the first cycle that prepared the level and its first K step.
+ * MGS_ERR_INVALID: NULL argument, level out of range.  MGS_ERR_STATE: the level holds no K-step state yet (no cycle has run with the
+ * K step switched on for it).  Not summed over the ranks of a row-sharded run: every rank already holds the reduced values. */
+int mgs_hier_kcycle_scalars(mgs_hier *h, int level, double out[5]);
 /* the additive switch of MultiGridPrecond::solve (reference src/common/bicg.cpp:59, `multiplicative_precond = false`; dead in the
  * reference — the constructor fixes it to true, :42): with on != 0 a zero-guess cycle returns, level by level,
  * P·cycle(Pᵀ v) + M2(v) with M2 = ωD⁻¹ instead of the multiplicative form.  The other switch, `use_preconditioner = false`

@@ -136,6 +136,7 @@ PROTOTYPES = {
     "mgs_hier_set_smoother": (C.c_int, [C.c_void_p, C.c_double, C.c_int, C.c_int]),
     "mgs_hier_set_kcycle": (C.c_int, [C.c_void_p, C.c_int]),
     "mgs_hier_set_kcycle_entry": (C.c_int, [C.c_void_p, C.c_int]),
+    "mgs_hier_kcycle_scalars": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double)]),
     "mgs_hier_set_additive": (C.c_int, [C.c_void_p, C.c_int]),
     "mgs_hier_set_correction_scale": (C.c_int, [C.c_void_p, C.c_double]),
     "mgs_hier_destroy": (C.c_int, [C.c_void_p]),

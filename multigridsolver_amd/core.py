@@ -608,6 +608,15 @@ class Hierarchy:
     def set_kcycle(self, levels):
         check(lib().mgs_hier_set_kcycle(self.h, levels), self.ctx.h); return self
 
+    def set_kcycle_entry(self, on=True):
+        """K step on level 0 itself when the cycle starts from x = 0 (mgs_hier_set_kcycle_entry)"""
+        check(lib().mgs_hier_set_kcycle_entry(self.h, int(bool(on))), self.ctx.h); return self
+
+    def kcycle_scalars(self, level):
+        """[ρ1, α1, γ, ρ2, α2] of the last K step of `level` (mgs_hier_kcycle_scalars); waits for the stream"""
+        out = (C.c_double * 5)(); check(lib().mgs_hier_kcycle_scalars(self.h, int(level), out), self.ctx.h)
+        return [float(v) for v in out]
+
     def set_correction_scale(self, sigma):
         """over-correction x ← x + σ·P e_c on every level (σ = 1: the reference's form)"""
         check(lib().mgs_hier_set_correction_scale(self.h, float(sigma)), self.ctx.h); return self

@@ -1047,6 +1047,16 @@ int mgs_hier_set_kcycle(mgs_hier *h, int levels) {
   return MGS_OK;
 }
 int mgs_hier_set_kcycle_entry(mgs_hier *h, int on) { h->kcycle_entry = on != 0; drop_graph(h); return MGS_OK; }
+int mgs_hier_kcycle_scalars(mgs_hier *h, int level, double out[5]) {
+  MGS_CHECK(nullptr, h && out, MGS_ERR_INVALID, "mgs_hier_kcycle_scalars: NULL argument");
+  mgs_ctx *ctx = h->ctx;
+  MGS_CHECK(ctx, level >= 0 && level < (int)h->lev.size(), MGS_ERR_INVALID, "mgs_hier_kcycle_scalars: level %d out of range", level);
+  const mgs_level &L = h->lev[level];
+  MGS_CHECK(ctx, L.kscal, MGS_ERR_STATE, "mgs_hier_kcycle_scalars: level %d has run no K step", level);
+  MGS_HIP(ctx, hipMemcpyAsync(out, L.kscal, sizeof(double) * 5, hipMemcpyDeviceToHost, ctx->stream));
+  MGS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return MGS_OK;
+}
 int mgs_hier_set_correction_scale(mgs_hier *h, double sigma) {
   MGS_CHECK(h->ctx, sigma > 0.0 && sigma <= 4.0, MGS_ERR_INVALID, "mgs_hier_set_correction_scale: sigma must lie in (0, 4]");
   h->corr_scale = sigma; drop_graph(h);
@@ -1779,6 +1789,7 @@ static int prepare_fused(mgs_hier *h) {
     if (L.kscal) continue;
     for (mgs_vec **q : {&L.kc1, &L.kv1, &L.kc2, &L.kv2, &L.kr}) MGS_TRY(mgs_vec_create(ctx, L.n_ext, q));
     MGS_TRY(mgs_dev_alloc(ctx, &L.kscal, 8));
+    MGS_HIP(ctx, hipMemsetAsync(L.kscal, 0, 8 * sizeof(double), ctx->stream));      // defined before the first step (mgs_hier_kcycle_scalars)
     drop_graph(h);
   }
   const bool sharded = h->halo || h->halo_begin || h->native;

@@ -1,0 +1,267 @@
+"""Host restatement of the K-cycle's two Krylov steps (coarse_solve_inner, multigridsolver_amd/csrc/mgs_api.hip) and of the reductions and
+element-wise kernels they launch (multigridsolver_amd/csrc/kernels_aux.hip), numpy only.
+
+Every function takes a `dtype`.  In float64 the sums are formed in the kernels' own association — which lane adds which product in which
+order, the wave tree, the four wave sums, the layout of the partials, the one-workgroup fold — and products and sums round separately, as
+the library's -ffp-contract=off makes the device do: the results are meant to be compared BIT FOR BIT with the device's.  In np.longdouble
+the same code is the yardstick of tests/test_kcycle_ref_cpu.py.
+
+    mdot2       mdot_partial_kernel + mdot_final_kernel with K = 2 (k_mdot): ρ1, α1
+    dot_dev     dot_partial_kernel + dot_final_kernel (k_dot_dev): γ, and (ρ1, α1) where an operand is not 16-byte aligned
+    orth_dots   kc_orth_dots_kernel + dot2_final_kernel (k_kc_orth_dots): ρ2, α2
+    update_r    kc_update_r_kernel;   combine   kc_combine_kernel
+    kstep       coarse_solve_inner from caller-supplied B and A
+
+`defects` (a set of names from DEFECTS) plants one wrong step each; tests/test_kcycle_ref_cpu.py uses it to show that the comparison the GPU
+test makes would notice that step going wrong on the device.  Nothing else passes it."""
+import math
+
+import numpy as np
+
+TB = 256                    # lanes per workgroup
+WAVE = 64
+DOT_BLOCKS = 4096           # k_dot_dev's cap; the pair kernels use half of the slots per sum
+U = 2.0 ** -53
+U_LD = float(np.finfo(np.longdouble).eps) / 2
+
+DEFECTS = ("no_tail", "skip_partial", "no_g_in_v2o", "no_g_in_d2o", "swap_forms", "rho2_nonzero")
+
+
+def clamp(v, lo, hi):
+    return max(lo, min(int(v), hi))
+
+
+def mdot_grid(n):
+    return clamp(((n // 2) + TB * 4 - 1) // (TB * 4), 1, 2048)
+
+
+def dot_grid(n):
+    return clamp((n + TB - 1) // TB, 1, DOT_BLOCKS)
+
+
+def orth_grid(n):
+    return clamp((n + TB * 4 - 1) // (TB * 4), 1, DOT_BLOCKS // 2)
+
+
+# ------------------------------------------------------------------------------------------------------------------ the shared stages
+def _lanes(v, grid):
+    """v laid out [trip j][workgroup][lane]: element i = 256·B + t + j·256·grid is what lane t of workgroup B meets in its j-th trip.
+    Padded with +0.0: a lane's sum starts at +0.0 and can never be −0.0, so adding a zero product leaves it as it is."""
+    per = TB * grid
+    trips = max(1, -(-len(v) // per))
+    out = np.zeros(trips * per, dtype=v.dtype)
+    out[:len(v)] = v
+    return out.reshape(trips, grid, TB)
+
+
+def _workgroup(s):
+    """[grid][256] lane sums → [grid] partials: in every wave s += __shfl_down(s, off) for off = 32 … 1 (lane 0 ends with the tree
+    ((s0 + s32) + (s16 + s48)) + …), then lane 0 adds the four wave sums to 0.0 in order"""
+    w = s.reshape(s.shape[0], TB // WAVE, WAVE)
+    off = WAVE // 2
+    while off:
+        w = w[..., :off] + w[..., off:2 * off]
+        off //= 2
+    t = np.zeros(s.shape[0], dtype=s.dtype)
+    for q in range(TB // WAVE):
+        t = t + w[:, q, 0]
+    return t
+
+
+def _fold(part, skip=None):
+    """the one-workgroup fold of nb partials: lane t sums part[t], part[t + 256], … from 0.0, then sh[t] += sh[t + w] for w = 128 … 1.
+    skip: leave that slot out (a planted defect)"""
+    nb = len(part)
+    p = np.zeros(-(-nb // TB) * TB, dtype=part.dtype)
+    p[:nb] = part
+    if skip is not None:
+        p[skip] = 0
+    s = np.zeros(TB, dtype=part.dtype)
+    for row in p.reshape(-1, TB):
+        s = s + row
+    w = TB // 2
+    while w:
+        s = s[:w] + s[w:2 * w]
+        w //= 2
+    return s[0]
+
+
+# --------------------------------------------------------------------------------------------------------------------- the reductions
+def mdot2(a, b0, b1, dtype=np.float64, defects=()):
+    """(a·b0, a·b1) as k_mdot forms them with K = 2 on 16-byte aligned operands: pairs of elements per lane, `s += a.x·b.x; s += a.y·b.y`,
+    the odd last element on lane 0 of workgroup 0 behind its loop, partials [K][grid]"""
+    a = np.asarray(a, dtype=dtype)
+    n = len(a)
+    grid = mdot_grid(n)
+    n2 = n // 2
+    out = []
+    for b in (b0, b1):
+        b = np.asarray(b, dtype=dtype)
+        px = _lanes(a[0:2 * n2:2] * b[0:2 * n2:2], grid)
+        py = _lanes(a[1:2 * n2:2] * b[1:2 * n2:2], grid)
+        s = np.zeros((grid, TB), dtype=dtype)
+        for j in range(px.shape[0]):
+            s = s + px[j]
+            s = s + py[j]
+        if n & 1 and "no_tail" not in defects:
+            s[0, 0] = s[0, 0] + a[n - 1] * b[n - 1]
+        out.append(_fold(_workgroup(s), skip=(grid - 1) if "skip_partial" in defects else None))
+    return out[0], out[1]
+
+
+def dot_dev(x, y, dtype=np.float64, defects=()):
+    """x·y as k_dot_dev forms it: one element per lane and trip, grid-stride over at most 4096 workgroups"""
+    x = np.asarray(x, dtype=dtype); y = np.asarray(y, dtype=dtype)
+    grid = dot_grid(len(x))
+    p = _lanes(x * y, grid)
+    s = np.zeros((grid, TB), dtype=dtype)
+    for j in range(p.shape[0]):
+        s = s + p[j]
+    return _fold(_workgroup(s), skip=(grid - 1) if "skip_partial" in defects else None)
+
+
+def quotient(num, rho1):
+    """num/ρ1, 0 where ρ1 = 0: a = α1/ρ1 of kc_update_r_kernel, g = γ/ρ1 of kc_orth_dots_kernel"""
+    return num / rho1 if rho1 != 0 else type(rho1)(0)
+
+
+def orth_vectors(g, c1, c2, v1, v2, energy, dtype=np.float64, defects=()):
+    """(d2', v2') of kc_orth_dots_kernel: v2' = v2 − g·v1 and d2' = c2 − g·c1 (energy form) or v2' itself — a rounded product and a
+    rounded difference each"""
+    g = dtype(g)
+    c1, c2, v1, v2 = (np.asarray(q, dtype=dtype) for q in (c1, c2, v1, v2))
+    v2o = v2.copy() if "no_g_in_v2o" in defects else v2 - g * v1
+    if energy:
+        d2o = c2.copy() if "no_g_in_d2o" in defects else c2 - g * c1
+    else:
+        d2o = v2o
+    return d2o, v2o
+
+
+def orth_dots(g, c1, c2, v1, v2, rp, energy, dtype=np.float64, defects=()):
+    """(ρ2, α2) = (d2'·v2', d2'·r') as k_kc_orth_dots forms them: one element per lane and trip over at most 2048 workgroups, both sums
+    in one pass, folded by dot2_final_kernel"""
+    d2o, v2o = orth_vectors(g, c1, c2, v1, v2, energy, dtype, defects)
+    rp = np.asarray(rp, dtype=dtype)
+    grid = orth_grid(len(rp))
+    out = []
+    for p in (d2o * v2o, d2o * rp):
+        p = _lanes(p, grid)
+        s = np.zeros((grid, TB), dtype=dtype)
+        for j in range(p.shape[0]):
+            s = s + p[j]
+        out.append(_fold(_workgroup(s), skip=(grid - 1) if "skip_partial" in defects else None))
+    return out[0], out[1]
+
+
+# --------------------------------------------------------------------------------------------------------- the element-wise kernels
+def first_scalars(c1, v1, rhs, energy, aligned=True, dtype=np.float64, defects=()):
+    """(ρ1, α1) = (d1·v1, d1·rhs), d1 = c1 (energy form) or v1: one k_mdot pass, or — an operand off 16-byte alignment — two k_dot_dev"""
+    d1 = c1 if energy else v1
+    if aligned:
+        return mdot2(d1, v1, rhs, dtype, defects)
+    return dot_dev(d1, v1, dtype, defects), dot_dev(d1, rhs, dtype, defects)
+
+
+def update_r(rho1, alpha1, rhs, v1, dtype=np.float64):
+    """r' = rhs − a·v1 of kc_update_r_kernel"""
+    a = quotient(dtype(alpha1), dtype(rho1))
+    return np.asarray(rhs, dtype=dtype) - a * np.asarray(v1, dtype=dtype)
+
+
+def second_scalars(rho1, c1, c2, v1, v2, rp, energy, dtype=np.float64, defects=()):
+    """(γ, ρ2, α2): γ = d2·v1 by k_dot_dev, then the orthogonalised pair's products"""
+    d2 = c2 if energy else v2
+    gamma = dot_dev(d2, v1, dtype, defects)
+    rho2, alpha2 = orth_dots(quotient(gamma, dtype(rho1)), c1, c2, v1, v2, rp, energy, dtype, defects)
+    return gamma, rho2, alpha2
+
+
+def coefficients(scal, dtype=np.float64, defects=()):
+    """(k1, k2) of kc_combine_kernel"""
+    rho1, alpha1, gamma, rho2, alpha2 = (dtype(v) for v in scal)
+    k1, k2 = dtype(0), dtype(0)
+    if rho1 != 0:
+        k1 = alpha1 / rho1
+        if (rho2 != 0) if "rho2_nonzero" in defects else (rho2 > 0):
+            k2 = alpha2 / rho2
+            k1 = k1 - (gamma / rho1) * k2
+    return k1, k2
+
+
+def combine(scal, c1, c2, dtype=np.float64, defects=()):
+    """x = k1·c1 + k2·c2 of kc_combine_kernel"""
+    k1, k2 = coefficients(scal, dtype, defects)
+    return k1 * np.asarray(c1, dtype=dtype) + k2 * np.asarray(c2, dtype=dtype)
+
+
+# ---------------------------------------------------------------------------------------------------------------------- the K step
+def kstep(apply_B, apply_A, rhs, energy, aligned=True, dtype=np.float64, defects=()):
+    """coarse_solve_inner with B and A supplied by the caller (called on and returning arrays of `dtype`): every intermediate by name"""
+    if "swap_forms" in defects:
+        energy = not energy
+    rhs = np.asarray(rhs, dtype=dtype)
+    c1 = apply_B(rhs); v1 = apply_A(c1)
+    rho1, alpha1 = first_scalars(c1, v1, rhs, energy, aligned, dtype, defects)
+    rp = update_r(rho1, alpha1, rhs, v1, dtype)
+    c2 = apply_B(rp); v2 = apply_A(c2)
+    gamma, rho2, alpha2 = second_scalars(rho1, c1, c2, v1, v2, rp, energy, dtype, defects)
+    scal = [rho1, alpha1, gamma, rho2, alpha2]
+    return dict(c1=c1, v1=v1, scal=scal, rp=rp, c2=c2, v2=v2, x=combine(scal, c1, c2, dtype, defects))
+
+
+# ---------------------------------------------------------------------------------------------------------- yardstick and the bars
+def _split(x):
+    """x = hi + lo with 26 and 27 significant bits (Veltkamp): the product of two such halves is exact in float64"""
+    c = 134217729.0 * x
+    hi = c - (c - x)
+    return hi, x - hi
+
+
+def exact_dot(x, y, minus=None):
+    """(Σ x_i·y_i, Σ |x_i·y_i|) of float64 vectors: every product as four exact partial products, summed exactly by math.fsum and rounded
+    once (the helper of tests/test_gpu_krylov_scalars.py keeps 64 bits of a product; this one keeps all 106).  minus: a float64 or long
+    double value subtracted inside the exact sum — the error of a long double result is far below the rounding of Σ itself"""
+    x = np.asarray(x, dtype=np.float64); y = np.asarray(y, dtype=np.float64)
+    xh, xl = _split(x); yh, yl = _split(y)
+    terms = (xh * yh).tolist() + (xh * yl).tolist() + (xl * yh).tolist() + (xl * yl).tolist()
+    if minus is not None:
+        m = np.longdouble(minus)
+        hi = np.float64(m)
+        terms += [-float(hi), -float(np.float64(m - hi))]
+    return math.fsum(terms), float(np.abs(x.astype(np.longdouble) * y.astype(np.longdouble)).sum())
+
+
+def depth(kind, n):
+    """the longest chain of additions a product passes through in a reduction, read off the loops above: the additions of its lane
+    (mdot: two per trip and the odd tail; dot, orth: one per trip), 6 shuffle levels, 4 wave sums, the fold's strided additions
+    (one per 256 partials) and its 8 tree levels"""
+    if kind == "mdot":
+        grid = mdot_grid(n)
+        lane = 2 * max(1, -(-(n // 2) // (TB * grid))) + (n & 1)
+    elif kind == "dot":
+        grid = dot_grid(n)
+        lane = max(1, -(-n // (TB * grid)))
+    elif kind == "orth":
+        grid = orth_grid(n)
+        lane = max(1, -(-n // (TB * grid)))
+    else:
+        raise ValueError(kind)
+    return lane + 6 + 4 + -(-grid // TB) + 8
+
+
+def gamma_m(m, u=U):
+    return m * u / (1 - m * u)
+
+
+def bar(kind, n, sabs, u=U):
+    """γ_{D+1}·Σ|x_i·y_i|: D additions and the product's own rounding (Higham, Accuracy and Stability, §3.1)"""
+    return gamma_m(depth(kind, n) + 1, u) * sabs
+
+
+def bits(a):
+    return np.ascontiguousarray(np.asarray(a, dtype=np.float64)).view(np.int64)
+
+
+def same_bits(a, b):
+    return np.array_equal(bits(a), bits(b))
