@@ -1,6 +1,6 @@
 """Thin Python handles over the C-ABI (include/mgs.h).  Python here is plumbing for tests,
 bench.py and the torch.distributed launcher; the host-side solver logic lives in C++
-(multigridsolver_amd/csrc/mgs_api.hip, multigridsolver_amd/cpp/mgs_host.hpp)."""
+(multigridsolver_amd/csrc/mgs_api.hip, cycle.hip and krylov.hip; multigridsolver_amd/cpp/mgs_host.hpp)."""
 import ctypes as C
 
 import numpy as np

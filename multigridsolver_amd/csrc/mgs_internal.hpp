@@ -280,7 +280,7 @@ struct mgs_level {
   mgs_rowcode *code_hat = nullptr;   // option valcode: pattern code of (col, val_wd) for the pre pass on Â
   // operand precision (mgs_hier_set_operand_precision): FP32 copies of the two setup-time operands' values, rounded to nearest from the
   // FP64 arrays above (which stay the source of truth and stay allocated: switching back is free and bit-identical)
-  int op_bits = 64;                  // what the level was switched to; whether a cycle really runs on the copies: level_runs_f32 (mgs_api.hip)
+  int op_bits = 64;                  // what the level was switched to; whether a cycle really runs on the copies: mgs_level_runs_f32 (mgs_api.hip)
   float *val_wd32 = nullptr;         // nnz + 8 floats
   float *ap_val32 = nullptr;         // nnz(A·P) + 8 floats
   unsigned char *dpos = nullptr;     // position of the diagonal entry inside each row (255: none / beyond 254), see mgs_csr::dpos
@@ -432,6 +432,7 @@ int k_agg_pre(const mgs_csr *A, const double *valhat, const double *b, const dou
 int k_round_vals(mgs_ctx *ctx, const double *in, float *out, int64_t n);   // out_k = (float)in_k, round to nearest: the FP32 operand copies
 int k_prolong_agg(mgs_ctx *ctx, int n, const int *agg, const double *ec, double *x, int add);
 int k_fill(mgs_ctx *ctx, double *d, int64_t n, double v);
+int k_jacobi_zero(mgs_ctx *ctx, int n, double omega, const double *dinv, const double *b, double *x);   // x = (ωD⁻¹)b: the first sweep from x = 0
 int k_rand(mgs_ctx *ctx, double *d, int64_t n, uint64_t seed, int64_t off);
 int k_axpby(mgs_ctx *ctx, int64_t n, double a, const double *x, double b, double *y);
 int k_axpbypcz(mgs_ctx *ctx, int64_t n, double a, const double *x, double b, const double *y, double c, double *z);
@@ -512,9 +513,13 @@ void mgs_free_extract(struct mgs_extract_plan *p);
 
 // helpers (mgs_api.hip)
 int mgs_csr_alloc(mgs_ctx *ctx, int rows, int cols, int64_t nnz, mgs_csr **out);
-// the context's pool of work vectors (the Krylov solvers' ws_get / ws_put) for the other translation units: a vector of n entries, written before
-// it is read by whoever takes it; mgs_ws_put(NULL) does nothing
-// the Krylov solvers' null-space rule (krylov_nullspace) for the other translation units
+int mgs_prepare_fused(mgs_hier *h);      // operands, work vectors and codes a hierarchy's cycle needs, built outside any stream capture
+void mgs_drop_graph(mgs_hier *h);        // the cached cycle graphs (whatever they recorded has changed)
+bool mgs_level_runs_f32(const mgs_hier *h, int l);
+// (cycle.hip) halo slots dst of a level-l vector (or payload buffer) from the owners' src, complete on the stream, through the hierarchy's ONE transport rule
+int mgs_halo_exchange(mgs_hier *h, int l, const double *src, double *dst, bool fused_pass = false);
+// (krylov.hip) the context's pool of work vectors for the other translation units: a vector of n entries, written before
+// it is read by whoever takes it; mgs_ws_put(NULL) does nothing — and the Krylov solvers' null-space rule
 int mgs_krylov_nullspace(const mgs_csr *A, const mgs_hier *h, const char *who, bool *ns_out);
 int mgs_ws_get(mgs_ctx *ctx, int64_t n, int64_t owned, mgs_vec **out);
 void mgs_ws_put(mgs_ctx *ctx, mgs_vec *v);

@@ -1,6 +1,6 @@
 """Two things for the BiCGSTAB-plan tests, both plain float64 numpy:
 
-bicgstab_ref   a restatement of mgs_bicgstab (multigridsolver_amd/csrc/mgs_api.hip; reference BiCGSTABiml, src/common/bicg.cpp:74-136) with the
+bicgstab_ref   a restatement of mgs_bicgstab (multigridsolver_amd/csrc/krylov.hip; reference BiCGSTABiml, src/common/bicg.cpp:74-136) with the
                same statement order, the same `1.0*r + (−α)*v` forms and the same write-back.  → (status, iterations, resid, x), where
                `iterations` is what *max_iter holds on return (untouched on statuses 2 and 3).
 

@@ -1,4 +1,4 @@
-"""fgcr_ref: a restatement of mgs_fgcr's host loop (multigridsolver_amd/csrc/mgs_api.hip) in plain float64 numpy, with the scalar operations in
+"""fgcr_ref: a restatement of mgs_fgcr's host loop (multigridsolver_amd/csrc/krylov.hip) in plain float64 numpy, with the scalar operations in
 the host's order: the window of directions c_k = M·r, v_k = A·c_k orthogonalised against the v_j of the window with U_jk = h_j/ρ_j (0 where ρ_j is
 0), α_k = t/ρ_k, r ← 1.0·r + (−α_k)·v_k, the back substitution (I + U)·y = α and x ← x − Σ (−y_j)·c_j when a window closes, the true residual at
 every close, status 0 only on the true residual, the restart of the window from the true residual when the recursion had drifted, `<=` at

@@ -1,4 +1,4 @@
-"""Host restatement of the K-cycle's two Krylov steps (coarse_solve_inner, multigridsolver_amd/csrc/mgs_api.hip) and of the reductions and
+"""Host restatement of the K-cycle's two Krylov steps (coarse_solve_inner, multigridsolver_amd/csrc/cycle.hip) and of the reductions and
 element-wise kernels they launch (multigridsolver_amd/csrc/kernels_aux.hip), numpy only.
 
 Every function takes a `dtype`.  In float64 the sums are formed in the kernels' own association — which lane adds which product in which

@@ -1,5 +1,5 @@
 """Extended-precision yardsticks of the Krylov solvers' scalars: restatements of mgs_bicgstab, mgs_pcg and mgs_fgcr
-(multigridsolver_amd/csrc/mgs_api.hip) for a FIXED number of steps, in any numpy float type (np.longdouble: the reference;
+(multigridsolver_amd/csrc/krylov.hip) for a FIXED number of steps, in any numpy float type (np.longdouble: the reference;
 np.float64: the distance a correct FP64 implementation may have from it), plus a banded test operator whose product is a few
 shifted numpy slices, so that applying it in long double needs no sparse library.
 

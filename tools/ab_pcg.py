@@ -15,7 +15,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
 METHODS = ["bicgstab_v", "pcg_v", "fgcr_k4", "fpcg_k4"]
-# work vectors of the operator's size a solve holds (mgs_api.hip): BiCGSTAB p p̂ s ŝ t v r r̃; FGCR(10) r + 10 × (c, v); PCG r z p q
+# work vectors of the operator's size a solve holds (krylov.hip): BiCGSTAB p p̂ s ŝ t v r r̃; FGCR(10) r + 10 × (c, v); PCG r z p q
 VECTORS = {"bicgstab_v": 8, "pcg_v": 4, "fgcr_k4": 21, "fpcg_k4": 4}
 # cycle applications per iteration
 CYCLES = {"bicgstab_v": 2, "pcg_v": 1, "fgcr_k4": 1, "fpcg_k4": 1}
