@@ -1470,7 +1470,7 @@ dim3 plan_block_map(const mgs_csr *A, int blk_lo, int blk_hi, int gap_at, int ga
   return plan_map(ctx, bm, blk_lo, blk_hi - blk_lo, (A->far_band + RB - 1) / RB, 512, ctx->opt_strip > 0 ? ctx->opt_strip : 64);
 }
 
-// A/B-only launchers (variants 2–4 here, 6 and 7 below launch_slice): kept as they were, run by no test
+// A/B-only launchers (variants 2–4 here, 6 and 7 below launch_slice): kept as they were; held arm by arm by tests/test_gpu_operator_kernels.py
 template <int OP, bool NT, int CHUNK>
 int launch_lanes(const mgs_csr *A, int lanes, dim3 grid, size_t lds, const double *x, const double *b,
                  const double *dinv, double omega, double *out, int cap, BlockMap bm) {
@@ -2056,7 +2056,10 @@ int mgs_launch_csr_op_range(const mgs_csr *A, int op, const double *x, const dou
   // FP32 level: pre pass on the float copy of Â's values, whatever the SpMV variant options say (the float forms take no ω)
   if (A->val32) return launch_coded(A, A->code, op, A->col, x, b, dinv, 0.0, nullptr, nullptr, out, grid, bm);
   const int cap = ctx->opt_spmv_variant == 1 ? -1 : A->lds_cap;
-  if (ctx->opt_spmv_variant == 6 && A->max_block_nnz <= 2048 && A->max_block_nnz == A->lds_cap) return launch_pipe(A, op, x, b, dinv, omega, out, cap, bm);
+  // pipe: ITER·RB = 1024 sixteen-byte pairs per row block.  A block of cnt entries from entry lo on needs (cnt + (lo & 1) + 1) >> 1 pairs
+  // (its slice starts at lo & ~1): 1024 for cnt = 2047 at either parity of lo, 1025 for cnt = 2048 at an odd lo — so 2047 is the bound
+  // (tests/spmv_ref.py pairs_needed, tests/test_spmv_ref_cpu.py); heavier matrices run the slice kernel
+  if (ctx->opt_spmv_variant == 6 && A->max_block_nnz <= 2047 && A->max_block_nnz == A->lds_cap) return launch_pipe(A, op, x, b, dinv, omega, out, cap, bm);
   if (ctx->opt_spmv_variant == 7 && A->max_wave_nnz <= 4096) return launch_wave(A, op, x, b, dinv, omega, out, grid, bm);
   if (ctx->opt_spmv_variant == 0 && !ctx->opt_nontemporal && use_rowcode(A, A->code))
     return launch_coded(A, A->code, op, A->col, x, b, dinv, omega, nullptr, nullptr, out, grid, bm);

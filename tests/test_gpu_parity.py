@@ -292,7 +292,8 @@ def test_ragged_and_long_rows(ctx, mg, orc):
     assert rel(A.spmv(x).numpy(), Ao.spmv(x_np)) <= 1e-13
     assert rel(A.residual(x, b).numpy(), Ao.residual(x_np, b_np)) <= 1e-13
     assert A.spmv(x).numpy()[17] == 0.0
-    # forced sub-wavefront variant on a short-row matrix must agree to rounding
+    # variant 1 stages nothing (cap = −1); this matrix has no row longer than 64 (max_row_len = 7), so its blocks take the slice kernel's
+    # sequential walk from global memory, not the sub-wavefront arm (that one: tests/test_gpu_operator_kernels.py, every LANES width)
     ctx.set_option("spmv_variant", 1)
     try:
         P = orc.poisson3d(12); Pd = dev(ctx, P)
