@@ -119,19 +119,19 @@ __global__ __launch_bounds__(PTB) void bcgp_p_vec_kernel(int64_t n, const BcgSta
   const bool first = st->first != 0;
   const double b = st->nbo, c = st->beta;
   const int64_t n2 = n >> 1;
-  const kd2 *__restrict__ rv = reinterpret_cast<const kd2 *>(r);
-  const kd2 *__restrict__ vv = reinterpret_cast<const kd2 *>(v);
-  kd2 *__restrict__ pv = reinterpret_cast<kd2 *>(p);
+  const vd2 *__restrict__ rv = reinterpret_cast<const vd2 *>(r);
+  const vd2 *__restrict__ vv = reinterpret_cast<const vd2 *>(v);
+  vd2 *__restrict__ pv = reinterpret_cast<vd2 *>(p);
   const int64_t stride = (int64_t)gridDim.x * PTB;
   for (int64_t i = (int64_t)blockIdx.x * PTB + threadIdx.x; i < n2; i += stride) {
-    const kd2 ri = rv[i]; kd2 q;
+    const vd2 ri = rv[i]; vd2 q;
     if (first) q = ri;
     else {
-      const kd2 o = vv[i];
+      const vd2 o = vv[i];
       if (c == 0.0) { q.x = 1.0 * ri.x + b * o.x; q.y = 1.0 * ri.y + b * o.y; }
-      else { const kd2 w = pv[i]; q.x = 1.0 * ri.x + b * o.x + c * w.x; q.y = 1.0 * ri.y + b * o.y + c * w.y; }
+      else { const vd2 w = pv[i]; q.x = 1.0 * ri.x + b * o.x + c * w.x; q.y = 1.0 * ri.y + b * o.y + c * w.y; }
     }
-    kst2(pv + i, q, nts != 0);
+    st2(pv + i, q, nts != 0);
   }
   if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
     const int64_t k = n - 1;
@@ -160,15 +160,15 @@ __global__ __launch_bounds__(PTB) void bcgp_x_vec_kernel(int64_t n, const BcgSta
   if (frozen && !st->half) return;
   const double a = st->alpha, b = st->omega;
   const int64_t n2 = n >> 1;
-  const kd2 *__restrict__ pv = reinterpret_cast<const kd2 *>(ph);
-  const kd2 *__restrict__ sv = reinterpret_cast<const kd2 *>(sh);
-  kd2 *__restrict__ xv = reinterpret_cast<kd2 *>(x);
+  const vd2 *__restrict__ pv = reinterpret_cast<const vd2 *>(ph);
+  const vd2 *__restrict__ sv = reinterpret_cast<const vd2 *>(sh);
+  vd2 *__restrict__ xv = reinterpret_cast<vd2 *>(x);
   const int64_t stride = (int64_t)gridDim.x * PTB;
   for (int64_t i = (int64_t)blockIdx.x * PTB + threadIdx.x; i < n2; i += stride) {
-    const kd2 pi = pv[i], xi = xv[i]; kd2 q;
+    const vd2 pi = pv[i], xi = xv[i]; vd2 q;
     if (frozen) { q.x = a * pi.x + 1.0 * xi.x; q.y = a * pi.y + 1.0 * xi.y; }
-    else { const kd2 si = sv[i]; q.x = a * pi.x + b * si.x + 1.0 * xi.x; q.y = a * pi.y + b * si.y + 1.0 * xi.y; }
-    kst2(xv + i, q, nts != 0);
+    else { const vd2 si = sv[i]; q.x = a * pi.x + b * si.x + 1.0 * xi.x; q.y = a * pi.y + b * si.y + 1.0 * xi.y; }
+    st2(xv + i, q, nts != 0);
   }
   if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
     const int64_t k = n - 1;
@@ -196,25 +196,25 @@ __global__ __launch_bounds__(PTB) void bcgp_upd_vec_kernel(int64_t n, const BcgS
   const double a = 1.0, b = OMEGA ? -st->omega : -st->alpha;
   __shared__ double sh[2][PTB / 64];
   const int64_t n2 = n >> 1;
-  const kd2 *__restrict__ xv = reinterpret_cast<const kd2 *>(x);
-  const kd2 *__restrict__ yv = reinterpret_cast<const kd2 *>(y);
-  const kd2 *__restrict__ wv = reinterpret_cast<const kd2 *>(w);
-  kd2 *__restrict__ zv = reinterpret_cast<kd2 *>(z);
+  const vd2 *__restrict__ xv = reinterpret_cast<const vd2 *>(x);
+  const vd2 *__restrict__ yv = reinterpret_cast<const vd2 *>(y);
+  const vd2 *__restrict__ wv = reinterpret_cast<const vd2 *>(w);
+  vd2 *__restrict__ zv = reinterpret_cast<vd2 *>(z);
   double s0 = 0.0, s1 = 0.0;
   const int64_t stride = (int64_t)gridDim.x * PTB;
   for (int64_t i = (int64_t)blockIdx.x * PTB + threadIdx.x; i < n2; i += stride) {
-    const kd2 p = xv[i], o = yv[i]; kd2 q;
+    const vd2 p = xv[i], o = yv[i]; vd2 q;
     q.x = a * p.x + b * o.x; q.y = a * p.y + b * o.y;
-    kst2(zv + i, q, nts != 0);
+    st2(zv + i, q, nts != 0);
     s0 += q.x * q.x; s0 += q.y * q.y;
-    if (OMEGA) { const kd2 ww = wv[i]; s1 += ww.x * q.x; s1 += ww.y * q.y; }
+    if (OMEGA) { const vd2 ww = wv[i]; s1 += ww.x * q.x; s1 += ww.y * q.y; }
   }
   if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
     const double zi = a * x[n - 1] + b * y[n - 1];
     z[n - 1] = zi; s0 += zi * zi;
     if (OMEGA) s1 += w[n - 1] * zi;
   }
-  KRYLOV_FOLD2(s0, s1, sh, part);
+  BLAS1_FOLD2(s0, s1, sh, part);
 }
 template <bool OMEGA>
 __global__ __launch_bounds__(PTB) void bcgp_upd_kernel(int64_t n, const BcgState *__restrict__ st, const double *__restrict__ x, const double *__restrict__ y,
@@ -231,7 +231,7 @@ __global__ __launch_bounds__(PTB) void bcgp_upd_kernel(int64_t n, const BcgState
     s0 += zi * zi;
     if (OMEGA) s1 += w[i] * zi;
   }
-  KRYLOV_FOLD2(s0, s1, sh, part);
+  BLAS1_FOLD2(s0, s1, sh, part);
 }
 }   // namespace
 

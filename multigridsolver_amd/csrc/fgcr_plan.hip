@@ -27,7 +27,7 @@
 
 namespace {
 using namespace krylov;
-constexpr int FW = 16;                   // the widest window: one multi-vector pass holds 16 vectors (kernels_aux.hip: MDOT_MAX), a hierarchy caches 16 graphs
+constexpr int FW = 16;                   // the widest window: one multi-vector pass holds 16 vectors (blas1.hip: MDOT_MAX), a hierarchy caches 16 graphs
 
 // why a solve froze
 enum { WHY_NONE = 0, WHY_RECURSION = 1, WHY_BREAKDOWN = 2, WHY_INIT = 3, WHY_TRUE = 4 };
@@ -147,16 +147,16 @@ __global__ __launch_bounds__(PTB) void fgp_orth_kernel(int64_t n, int K, const F
   const int64_t stride = (int64_t)gridDim.x * PTB;
   if (VEC) {
     const int64_t n2 = n >> 1;
-    kd2 *vv = reinterpret_cast<kd2 *>(v);
-    const kd2 *__restrict__ uv = reinterpret_cast<const kd2 *>(u);
+    vd2 *vv = reinterpret_cast<vd2 *>(v);
+    const vd2 *__restrict__ uv = reinterpret_cast<const vd2 *>(u);
     for (int64_t i = (int64_t)blockIdx.x * PTB + threadIdx.x; i < n2; i += stride) {
-      kd2 zi = vv[i];
+      vd2 zi = vv[i];
 #pragma unroll
       for (int k = 0; k < FW; ++k)
-        if (k < K) { const kd2 wi = reinterpret_cast<const kd2 *>(W.w[k])[i]; zi.x -= cf[k] * wi.x; zi.y -= cf[k] * wi.y; }
+        if (k < K) { const vd2 wi = reinterpret_cast<const vd2 *>(W.w[k])[i]; zi.x -= cf[k] * wi.x; zi.y -= cf[k] * wi.y; }
       vv[i] = zi;
       s0 += zi.x * zi.x; s0 += zi.y * zi.y;
-      const kd2 q = uv[i]; s1 += zi.x * q.x; s1 += zi.y * q.y;
+      const vd2 q = uv[i]; s1 += zi.x * q.x; s1 += zi.y * q.y;
     }
     if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
       double zi = v[n - 1];
@@ -176,7 +176,7 @@ __global__ __launch_bounds__(PTB) void fgp_orth_kernel(int64_t n, int K, const F
       s1 += zi * u[i];
     }
   }
-  KRYLOV_FOLD2(s0, s1, sh, part);
+  BLAS1_FOLD2(s0, s1, sh, part);
 }
 
 // x-pass of a window close: x ← x − Σ_{j<m_open} cf_j·c_j, maxpy_dot2_kernel's expression without sums; m_open and cf from the state block.
@@ -191,12 +191,12 @@ __global__ __launch_bounds__(PTB) void fgp_x_kernel(int64_t n, const FgState *__
   const int64_t stride = (int64_t)gridDim.x * PTB;
   if (VEC) {
     const int64_t n2 = n >> 1;
-    kd2 *xv = reinterpret_cast<kd2 *>(x);
+    vd2 *xv = reinterpret_cast<vd2 *>(x);
     for (int64_t i = (int64_t)blockIdx.x * PTB + threadIdx.x; i < n2; i += stride) {
-      kd2 zi = xv[i];
+      vd2 zi = xv[i];
 #pragma unroll
       for (int k = 0; k < FW; ++k)
-        if (k < K) { const kd2 wi = reinterpret_cast<const kd2 *>(W.w[k])[i]; zi.x -= cf[k] * wi.x; zi.y -= cf[k] * wi.y; }
+        if (k < K) { const vd2 wi = reinterpret_cast<const vd2 *>(W.w[k])[i]; zi.x -= cf[k] * wi.x; zi.y -= cf[k] * wi.y; }
       xv[i] = zi;
     }
     if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
@@ -223,21 +223,21 @@ __global__ __launch_bounds__(PTB) void fgp_resid_vec_kernel(int64_t n, int k, co
   const double a = 1.0, b = -st->alpha[k];
   __shared__ double sh[2][PTB / 64];
   const int64_t n2 = n >> 1;
-  kd2 *rv = reinterpret_cast<kd2 *>(r);
-  const kd2 *__restrict__ yv = reinterpret_cast<const kd2 *>(v);
+  vd2 *rv = reinterpret_cast<vd2 *>(r);
+  const vd2 *__restrict__ yv = reinterpret_cast<const vd2 *>(v);
   double s0 = 0.0, s1 = 0.0;
   const int64_t stride = (int64_t)gridDim.x * PTB;
   for (int64_t i = (int64_t)blockIdx.x * PTB + threadIdx.x; i < n2; i += stride) {
-    const kd2 p = rv[i], o = yv[i]; kd2 q;
+    const vd2 p = rv[i], o = yv[i]; vd2 q;
     q.x = a * p.x + b * o.x; q.y = a * p.y + b * o.y;
-    kst2(rv + i, q, nts != 0);
+    st2(rv + i, q, nts != 0);
     s0 += q.x * q.x; s0 += q.y * q.y;
   }
   if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
     const double zi = a * r[n - 1] + b * v[n - 1];
     r[n - 1] = zi; s0 += zi * zi;
   }
-  KRYLOV_FOLD2(s0, s1, sh, part);
+  BLAS1_FOLD2(s0, s1, sh, part);
 }
 __global__ __launch_bounds__(PTB) void fgp_resid_kernel(int64_t n, int k, const FgState *__restrict__ st, double *r, const double *__restrict__ v, double *__restrict__ part) {
   if (st->frozen) return;
@@ -251,7 +251,7 @@ __global__ __launch_bounds__(PTB) void fgp_resid_kernel(int64_t n, int k, const 
     r[i] = zi;
     s0 += zi * zi;
   }
-  KRYLOV_FOLD2(s0, s1, sh, part);
+  BLAS1_FOLD2(s0, s1, sh, part);
 }
 
 // workgroups of maxpy_dot2_kernel (k_maxpy_dot2) and of mdot_partial_kernel (k_mdot)

@@ -15,7 +15,7 @@
 #include <algorithm>
 #include <cmath>
 
-#include "mgs_internal.hpp"
+#include "blas1.hpp"
 
 namespace {
 constexpr int GTB = 256;        // lanes per workgroup; a workgroup owns 2·GTB consecutive entries
@@ -32,20 +32,20 @@ constexpr int S_GRAM = 4 * GBLK;     // one column of mgs_guess_gram
 constexpr int S_DEC = 5 * GBLK;      // [0] 1.0 = candidate accepted, [1] s = 1/√ν2²
 constexpr int S_TOTAL = 5 * GBLK + 4;
 
-typedef double gd2 __attribute__((ext_vector_type(2)));
+using blas1::vd2; using blas1::al16;
 
 // the lane's pair at i0 (two = both entries exist; else .y = 0): one 16-byte load where the operand allows it
-__device__ __forceinline__ gd2 ld2(const double *p, int64_t i0, bool two, bool vec) {
-  gd2 r;
+__device__ __forceinline__ vd2 ld2(const double *p, int64_t i0, bool two, bool vec) {
+  vd2 r;
   if (two) {
-    if (vec) r = *reinterpret_cast<const gd2 *>(p + i0);
+    if (vec) r = *reinterpret_cast<const vd2 *>(p + i0);
     else { r.x = p[i0]; r.y = p[i0 + 1]; }
   } else { r.x = p[i0]; r.y = 0.0; }
   return r;
 }
-__device__ __forceinline__ void st2(double *p, int64_t i0, bool two, bool vec, gd2 v) {
+__device__ __forceinline__ void st2(double *p, int64_t i0, bool two, bool vec, vd2 v) {
   if (two) {
-    if (vec) *reinterpret_cast<gd2 *>(p + i0) = v;
+    if (vec) *reinterpret_cast<vd2 *>(p + i0) = v;
     else { p[i0] = v.x; p[i0 + 1] = v.y; }
   } else p[i0] = v.x;
 }
@@ -77,12 +77,12 @@ __global__ __launch_bounds__(GTB) void guess_dots_kernel(int64_t n, int K, const
   const int64_t i0 = 2 * ((int64_t)blockIdx.x * GTB + threadIdx.x);
   if (i0 < n) {
     const bool two = i0 + 1 < n;
-    const gd2 vi = ld2(v, i0, two, vec != 0);
+    const vd2 vi = ld2(v, i0, two, vec != 0);
 #pragma unroll
     for (int k = 0; k < GK; ++k)
-      if (k < K) { const gd2 q = ld2(Q + (int64_t)k * stride, i0, two, true); s[k] = q.x * vi.x; s[k] += q.y * vi.y; }
+      if (k < K) { const vd2 q = ld2(Q + (int64_t)k * stride, i0, two, true); s[k] = q.x * vi.x; s[k] += q.y * vi.y; }
     if (e) {
-      const gd2 ei = (e == v) ? vi : ld2(e, i0, two, vec != 0);
+      const vd2 ei = (e == v) ? vi : ld2(e, i0, two, vec != 0);
 #pragma unroll
       for (int k = 0; k < GROWS; ++k) if (k == K) { s[k] = ei.x * vi.x; s[k] += ei.y * vi.y; }
     }
@@ -100,24 +100,24 @@ __global__ __launch_bounds__(GTB) void guess_combine_kernel(int64_t n, int K, co
   const int64_t i0 = 2 * ((int64_t)blockIdx.x * GTB + threadIdx.x);
   if (i0 < n) {
     const bool two = i0 + 1 < n;
-    gd2 tx = {0.0, 0.0}, ty = {0.0, 0.0};
+    vd2 tx = {0.0, 0.0}, ty = {0.0, 0.0};
 #pragma unroll
     for (int k = 0; k < GK; ++k) {
       if (k < K) {
         const double a = alpha[k];
-        const gd2 xk = ld2(X + (int64_t)k * stride, i0, two, true);
-        gd2 p; p.x = a * xk.x; p.y = a * xk.y;
+        const vd2 xk = ld2(X + (int64_t)k * stride, i0, two, true);
+        vd2 p; p.x = a * xk.x; p.y = a * xk.y;
         if (k == 0) tx = p; else { tx.x += p.x; tx.y += p.y; }
         if (part) {
-          const gd2 yk = ld2(Y + (int64_t)k * stride, i0, two, true);
-          gd2 r; r.x = a * yk.x; r.y = a * yk.y;
+          const vd2 yk = ld2(Y + (int64_t)k * stride, i0, two, true);
+          vd2 r; r.x = a * yk.x; r.y = a * yk.y;
           if (k == 0) ty = r; else { ty.x += r.x; ty.y += r.y; }
         }
       }
     }
     st2(x0, i0, two, vec != 0, tx);
     if (part) {
-      const gd2 bi = ld2(b, i0, two, vec != 0);
+      const vd2 bi = ld2(b, i0, two, vec != 0);
       const double rx = bi.x - ty.x, ry = two ? bi.y - ty.y : 0.0;
       s[0] = rx * rx; s[0] += ry * ry;
     }
@@ -138,21 +138,21 @@ __global__ __launch_bounds__(GTB) void guess_pair_kernel(int64_t n, int K, const
   const int64_t i0 = 2 * ((int64_t)blockIdx.x * GTB + threadIdx.x);
   if (i0 < n) {
     const bool two = i0 + 1 < n;
-    gd2 q[GK];
-    gd2 tx = {0.0, 0.0}, tw = {0.0, 0.0};
+    vd2 q[GK];
+    vd2 tx = {0.0, 0.0}, tw = {0.0, 0.0};
 #pragma unroll
     for (int k = 0; k < GK; ++k) {
       if (k < K) {
         const double c = coef[k];
-        const gd2 xk = ld2(X + (int64_t)k * stride, i0, two, true), yk = ld2(Y + (int64_t)k * stride, i0, two, true);
-        gd2 p, r;
+        const vd2 xk = ld2(X + (int64_t)k * stride, i0, two, true), yk = ld2(Y + (int64_t)k * stride, i0, two, true);
+        vd2 p, r;
         p.x = c * xk.x; p.y = c * xk.y; r.x = c * yk.x; r.y = c * yk.y;
         if (k == 0) { tx = p; tw = r; } else { tx.x += p.x; tx.y += p.y; tw.x += r.x; tw.y += r.y; }
         q[k] = energy ? xk : yk;
       }
     }
-    const gd2 xi = ld2(xs, i0, two, vec != 0), wi = ld2(ws, i0, two, true);
-    gd2 xo, wo;
+    const vd2 xi = ld2(xs, i0, two, vec != 0), wi = ld2(ws, i0, two, true);
+    vd2 xo, wo;
     xo.x = xi.x - tx.x; xo.y = two ? xi.y - tx.y : 0.0;
     wo.x = wi.x - tw.x; wo.y = two ? wi.y - tw.y : 0.0;
     st2(xd, i0, two, true, xo);
@@ -161,7 +161,7 @@ __global__ __launch_bounds__(GTB) void guess_pair_kernel(int64_t n, int K, const
 #pragma unroll
       for (int k = 0; k < GK; ++k) if (k < K) { s[k] = q[k].x * wo.x; s[k] += q[k].y * wo.y; }
     }
-    const gd2 ev = energy ? xo : wo;
+    const vd2 ev = energy ? xo : wo;
 #pragma unroll
     for (int k = 0; k < GROWS; ++k) if (k == nrow) { s[k] = ev.x * wo.x; s[k] += ev.y * wo.y; }
   }
@@ -211,14 +211,12 @@ __global__ __launch_bounds__(GTB) void guess_store_kernel(int64_t n, const doubl
   const int64_t i0 = 2 * ((int64_t)blockIdx.x * GTB + threadIdx.x);
   if (i0 >= n) return;
   const bool two = i0 + 1 < n;
-  const gd2 xi = ld2(xs, i0, two, vec != 0), wi = ld2(ws, i0, two, true);
-  gd2 xo, wo;
+  const vd2 xi = ld2(xs, i0, two, vec != 0), wi = ld2(ws, i0, two, true);
+  vd2 xo, wo;
   xo.x = s * xi.x; xo.y = s * xi.y; wo.x = s * wi.x; wo.y = s * wi.y;
   st2(xd, i0, two, true, xo);
   st2(yd, i0, two, true, wo);
 }
-
-inline bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 }   // namespace
 
 struct mgs_guess {

@@ -1,10 +1,8 @@
-// kernels_aux.hip — grid transfer (restriction / prolongation), BLAS-1, coarsest dense solve,
-// on-device operator generators, halo pack.  gfx950 only.
+// kernels_aux.hip — grid transfer (restriction / prolongation), setup-time operand preparation, the K-cycle's two elementwise
+// kernels, coarsest dense solve, on-device operator generators, tail scatter.  gfx950 only.  BLAS-1 and reductions: blas1.hip.
 #include "mgs_internal.hpp"
 
 #include <cfloat>
-#include <chrono>
-#include <time.h>
 
 namespace {
 constexpr int TB = 256;
@@ -48,64 +46,6 @@ __global__ void rand_kernel(double *__restrict__ d, int64_t n, uint64_t seed, in
     d[i] = (double)(h >> 11) * (1.0 / 9007199254740992.0);
   }
 }
-
-__global__ void axpby_kernel(int64_t n, double a, const double *__restrict__ x, double b, double *__restrict__ y) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  if (b == 0.0) { for (; i < n; i += stride) y[i] = a * x[i]; }
-  else { for (; i < n; i += stride) y[i] = a * x[i] + b * y[i]; }
-}
-__global__ void axpbypcz_kernel(int64_t n, double a, const double *__restrict__ x, double b,
-                                const double *__restrict__ y, double c, double *__restrict__ z) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  if (c == 0.0) { for (; i < n; i += stride) z[i] = a * x[i] + b * y[i]; }
-  else { for (; i < n; i += stride) z[i] = a * x[i] + b * y[i] + c * z[i]; }
-}
-
-// 16-byte forms of the two update kernels (option blas1_vec, default on; used when every operand is 16-byte aligned): each lane
-// moves a pair of doubles per load/store and the loop is unrolled so that several loads per stream are in flight per wave — the
-// 8-byte grid-stride loops above stop at ≈ 4 TB/s on this part, a pure stream wants ≥ 16 B per lane (MI355X_MICROARCH.md, HBM:
-// 6.3 TB/s for a float4 copy).  Element i is computed by the same expression as above, so the results have the same bits.
-typedef double vd2 __attribute__((ext_vector_type(2)));
-// streaming store (the instruction spelled out: see st_stream in kernels_spmv.hip); nothing here reads back what it stored
-__device__ __forceinline__ void st2(vd2 *p, vd2 v, bool nt) {
-  if (nt) asm volatile("global_store_dwordx4 %0, %1, off nt" : : "v"(p), "v"(v) : "memory");
-  else *p = v;
-}
-template <bool HASB>
-__global__ __launch_bounds__(TB) void axpby_vec_kernel(int64_t n, double a, const double *__restrict__ x, double b, double *__restrict__ y, int nts) {
-  const int64_t n2 = n >> 1;
-  const vd2 *__restrict__ xv = reinterpret_cast<const vd2 *>(x);
-  vd2 *__restrict__ yv = reinterpret_cast<vd2 *>(y);
-  const int64_t stride = (int64_t)gridDim.x * TB;
-#pragma unroll 4
-  for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < n2; i += stride) {
-    const vd2 p = xv[i]; vd2 q;
-    if (HASB) { const vd2 o = yv[i]; q.x = a * p.x + b * o.x; q.y = a * p.y + b * o.y; }
-    else { q.x = a * p.x; q.y = a * p.y; }
-    st2(yv + i, q, nts != 0);
-  }
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) y[n - 1] = HASB ? a * x[n - 1] + b * y[n - 1] : a * x[n - 1];
-}
-template <bool HASC>
-__global__ __launch_bounds__(TB) void axpbypcz_vec_kernel(int64_t n, double a, const double *__restrict__ x, double b,
-                                                          const double *__restrict__ y, double c, double *__restrict__ z, int nts) {
-  const int64_t n2 = n >> 1;
-  const vd2 *__restrict__ xv = reinterpret_cast<const vd2 *>(x);
-  const vd2 *__restrict__ yv = reinterpret_cast<const vd2 *>(y);
-  vd2 *__restrict__ zv = reinterpret_cast<vd2 *>(z);
-  const int64_t stride = (int64_t)gridDim.x * TB;
-#pragma unroll 4
-  for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < n2; i += stride) {
-    const vd2 p = xv[i], o = yv[i]; vd2 q;
-    if (HASC) { const vd2 w = zv[i]; q.x = a * p.x + b * o.x + c * w.x; q.y = a * p.y + b * o.y + c * w.y; }
-    else { q.x = a * p.x + b * o.x; q.y = a * p.y + b * o.y; }
-    st2(zv + i, q, nts != 0);
-  }
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) z[n - 1] = HASC ? a * x[n - 1] + b * y[n - 1] + c * z[n - 1] : a * x[n - 1] + b * y[n - 1];
-}
-static inline bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // first damped-Jacobi sweep from x = 0: x = 0 + (ωD⁻¹)(b − A·0) = (ω·dinv_i)·b_i, bit-identical
 __global__ void jacobi_zero_kernel(int n, double omega, const double *__restrict__ dinv, const double *__restrict__ b, double *__restrict__ x) {
@@ -301,316 +241,6 @@ __global__ void concat_i32_kernel(const int *__restrict__ a, int na, const int *
   if (i < na) out[i] = a[i]; else if (i < na + nb) out[i] = b[i - na];
 }
 
-// ------------------------------------------------------------------ reductions
-// Two-stage deterministic dot: fixed grid of partials (independent of scheduling), then one
-// block folds them in index order.  reference bicg.cpp:64-72 (dot/norm helpers).
-// where the last stage of a reduction posts its results for the host (see fetch_results): mapped host buffer + ticket; hv = NULL: nowhere
-struct Post { double *hv; unsigned long long *ht; unsigned long long ticket; };
-__device__ __forceinline__ void post_to_host(const Post &pa, const double *vals, int cnt) {
-  for (int q = 0; q < cnt; ++q) __hip_atomic_store(pa.hv + q, vals[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  __hip_atomic_store(pa.ht, pa.ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-constexpr int DOT_BLOCKS = 4096;   // partial slots (a pair kernel uses half of them per sum): 8 workgroups per CU on 256 CUs
-__global__ __launch_bounds__(TB) void dot_partial_kernel(int64_t n, const double *__restrict__ x, const double *__restrict__ y, double *__restrict__ part) {
-  __shared__ double sh[TB / 64];
-  double s = 0.0;
-  int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
-  int64_t stride = (int64_t)gridDim.x * TB;
-  for (; i < n; i += stride) s += x[i] * y[i];
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) { double t = 0.0; for (int w = 0; w < TB / 64; ++w) t += sh[w]; part[blockIdx.x] = t; }
-}
-__global__ __launch_bounds__(TB) void dot_final_kernel(int nb, const double *__restrict__ part, double *__restrict__ out, Post pa) {
-  __shared__ double sh[TB];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < nb; i += TB) s += part[i];
-  sh[threadIdx.x] = s;
-  __syncthreads();
-  for (int w = TB / 2; w > 0; w >>= 1) { if (threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w]; __syncthreads(); }
-  if (threadIdx.x == 0) { const double r = sh[0]; out[0] = r; if (pa.hv) post_to_host(pa, &r, 1); }
-}
-
-// two inner products in one pass and one host round trip: (x·y, z·w) — BiCGSTAB's (t·s, t·t) and (r·r, r̃·r)
-__global__ __launch_bounds__(TB) void dot2_partial_kernel(int64_t n, const double *__restrict__ x, const double *__restrict__ y,
-                                                          const double *__restrict__ z, const double *__restrict__ w, double *__restrict__ part) {
-  __shared__ double sh[2][TB / 64];
-  double s0 = 0.0, s1 = 0.0;
-  int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
-  int64_t stride = (int64_t)gridDim.x * TB;
-  for (; i < n; i += stride) { s0 += x[i] * y[i]; s1 += z[i] * w[i]; }
-  for (int off = 32; off > 0; off >>= 1) { s0 += __shfl_down(s0, off); s1 += __shfl_down(s1, off); }
-  if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = s0; sh[1][threadIdx.x >> 6] = s1; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t0 = 0.0, t1 = 0.0;
-    for (int q = 0; q < TB / 64; ++q) { t0 += sh[0][q]; t1 += sh[1][q]; }
-    part[blockIdx.x] = t0; part[gridDim.x + blockIdx.x] = t1;
-  }
-}
-__global__ __launch_bounds__(TB) void dot2_final_kernel(int nb, const double *__restrict__ part, double *__restrict__ out, Post pa) {
-  __shared__ double sh[TB];
-  double res[2] = {0.0, 0.0};
-  for (int q = 0; q < 2; ++q) {
-    double s = 0.0;
-    for (int i = threadIdx.x; i < nb; i += TB) s += part[q * nb + i];
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = TB / 2; w > 0; w >>= 1) { if (threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w]; __syncthreads(); }
-    if (threadIdx.x == 0) { res[q] = sh[0]; out[q] = sh[0]; }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0 && pa.hv) post_to_host(pa, res, 2);
-}
-
-// z = a·x + b·y fused with (z·z, w·z): BiCGSTAB's s = r − αv with ‖s‖² and r = s − ωt with (‖r‖², r̃·r) in one pass each
-__global__ __launch_bounds__(TB) void update_dot2_partial_kernel(int64_t n, double a, const double *__restrict__ x, double b, const double *__restrict__ y,
-                                                                 double *__restrict__ z, const double *__restrict__ w, double *__restrict__ part) {
-  __shared__ double sh[2][TB / 64];
-  double s0 = 0.0, s1 = 0.0;
-  int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
-  int64_t stride = (int64_t)gridDim.x * TB;
-  for (; i < n; i += stride) {
-    const double zi = a * x[i] + b * y[i];
-    z[i] = zi;
-    s0 += zi * zi;
-    if (w) s1 += w[i] * zi;
-  }
-  for (int off = 32; off > 0; off >>= 1) { s0 += __shfl_down(s0, off); s1 += __shfl_down(s1, off); }
-  if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = s0; sh[1][threadIdx.x >> 6] = s1; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t0 = 0.0, t1 = 0.0;
-    for (int q = 0; q < TB / 64; ++q) { t0 += sh[0][q]; t1 += sh[1][q]; }
-    part[blockIdx.x] = t0; part[gridDim.x + blockIdx.x] = t1;
-  }
-}
-
-// 16-byte form of the kernel above (same per-element expression; the partial sums associate differently: lane t adds its pairs
-// x then y, a fixed order that does not depend on scheduling)
-template <bool HASW>
-__global__ __launch_bounds__(TB) void update_dot2_partial_vec_kernel(int64_t n, double a, const double *__restrict__ x, double b, const double *__restrict__ y,
-                                                                     double *__restrict__ z, const double *__restrict__ w, double *__restrict__ part, int nts) {
-  __shared__ double sh[2][TB / 64];
-  const int64_t n2 = n >> 1;
-  const vd2 *__restrict__ xv = reinterpret_cast<const vd2 *>(x);
-  const vd2 *__restrict__ yv = reinterpret_cast<const vd2 *>(y);
-  const vd2 *__restrict__ wv = reinterpret_cast<const vd2 *>(w);
-  vd2 *__restrict__ zv = reinterpret_cast<vd2 *>(z);
-  double s0 = 0.0, s1 = 0.0;
-  const int64_t stride = (int64_t)gridDim.x * TB;
-#pragma unroll 4
-  for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < n2; i += stride) {
-    const vd2 p = xv[i], o = yv[i]; vd2 q;
-    q.x = a * p.x + b * o.x; q.y = a * p.y + b * o.y;
-    st2(zv + i, q, nts != 0);
-    s0 += q.x * q.x; s0 += q.y * q.y;
-    if (HASW) { const vd2 ww = wv[i]; s1 += ww.x * q.x; s1 += ww.y * q.y; }
-  }
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-    const double zi = a * x[n - 1] + b * y[n - 1];
-    z[n - 1] = zi; s0 += zi * zi;
-    if (HASW) s1 += w[n - 1] * zi;
-  }
-  for (int off = 32; off > 0; off >>= 1) { s0 += __shfl_down(s0, off); s1 += __shfl_down(s1, off); }
-  if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = s0; sh[1][threadIdx.x >> 6] = s1; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t0 = 0.0, t1 = 0.0;
-    for (int q = 0; q < TB / 64; ++q) { t0 += sh[0][q]; t1 += sh[1][q]; }
-    part[blockIdx.x] = t0; part[gridDim.x + blockIdx.x] = t1;
-  }
-}
-
-// ------------------------------------------------------------------ preconditioned CG (mgs_pcg): the two passes beside dots, cycle and SpMV
-// Direction pass with the LAGGED x update: x ← x + a·p (the step the previous iteration decided; its p is read here anyway), then
-// p ← z + beta·p.  40 B per row (read x, p, z; write x, p) — applied eagerly the x update is a pass of its own (24 B per row more).
-// FIRST (first direction, and the one after a restart): p ← z only; p is NOT read (a pool vector may hold anything, 0·NaN = NaN)
-// and x is not touched (the caller has flushed every pending update before).
-template <bool FIRST>
-__global__ __launch_bounds__(TB) void pcg_dir_kernel(int64_t n, double a, double beta, double *__restrict__ x, double *__restrict__ p,
-                                                     const double *__restrict__ z) {
-  int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
-  const int64_t stride = (int64_t)gridDim.x * TB;
-  for (; i < n; i += stride) {
-    if (FIRST) p[i] = z[i];
-    else { const double pi = p[i]; x[i] = x[i] + a * pi; p[i] = z[i] + beta * pi; }
-  }
-}
-// 16-byte form (same per-element expressions: same bits)
-template <bool FIRST>
-__global__ __launch_bounds__(TB) void pcg_dir_vec_kernel(int64_t n, double a, double beta, double *__restrict__ x, double *__restrict__ p,
-                                                         const double *__restrict__ z, int nts) {
-  const int64_t n2 = n >> 1;
-  vd2 *__restrict__ xv = reinterpret_cast<vd2 *>(x);
-  vd2 *__restrict__ pv = reinterpret_cast<vd2 *>(p);
-  const vd2 *__restrict__ zv = reinterpret_cast<const vd2 *>(z);
-  const int64_t stride = (int64_t)gridDim.x * TB;
-  for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < n2; i += stride) {
-    const vd2 zi = zv[i];
-    if (FIRST) st2(pv + i, zi, nts != 0);
-    else {
-      const vd2 pi = pv[i], xi = xv[i]; vd2 xo, po;
-      xo.x = xi.x + a * pi.x; xo.y = xi.y + a * pi.y;
-      po.x = zi.x + beta * pi.x; po.y = zi.y + beta * pi.y;
-      st2(xv + i, xo, nts != 0);
-      st2(pv + i, po, nts != 0);
-    }
-  }
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-    if (FIRST) p[n - 1] = z[n - 1];
-    else { const double pi = p[n - 1]; x[n - 1] = x[n - 1] + a * pi; p[n - 1] = z[n - 1] + beta * pi; }
-  }
-}
-// Residual pass IN PLACE: r ← r − a·q with ‖r‖² (24 B per row: read r, q; write r).  update_dot2_partial*_kernel is out of place
-// (`__restrict__` on source and destination) and must not be aliased.  Partial pair per workgroup, the second sum stays zero so
-// that the staged fold of the pairs (k_dot2_finish) serves.
-__global__ __launch_bounds__(TB) void pcg_resid_kernel(int64_t n, double a, double *__restrict__ r, const double *__restrict__ q, double *__restrict__ part) {
-  __shared__ double sh[TB / 64];
-  double s0 = 0.0;
-  int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
-  const int64_t stride = (int64_t)gridDim.x * TB;
-  for (; i < n; i += stride) { const double ri = r[i] - a * q[i]; r[i] = ri; s0 += ri * ri; }
-  for (int off = 32; off > 0; off >>= 1) s0 += __shfl_down(s0, off);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s0;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t0 = 0.0;
-    for (int w = 0; w < TB / 64; ++w) t0 += sh[w];
-    part[blockIdx.x] = t0; part[gridDim.x + blockIdx.x] = 0.0;
-  }
-}
-// 16-byte form (same per-element expression; lane t adds its pair x then y, a fixed order that does not depend on scheduling)
-__global__ __launch_bounds__(TB) void pcg_resid_vec_kernel(int64_t n, double a, double *__restrict__ r, const double *__restrict__ q, double *__restrict__ part, int nts) {
-  __shared__ double sh[TB / 64];
-  const int64_t n2 = n >> 1;
-  vd2 *__restrict__ rv = reinterpret_cast<vd2 *>(r);
-  const vd2 *__restrict__ qv = reinterpret_cast<const vd2 *>(q);
-  double s0 = 0.0;
-  const int64_t stride = (int64_t)gridDim.x * TB;
-  for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < n2; i += stride) {
-    const vd2 ri = rv[i], qi = qv[i]; vd2 o;
-    o.x = ri.x - a * qi.x; o.y = ri.y - a * qi.y;
-    st2(rv + i, o, nts != 0);
-    s0 += o.x * o.x; s0 += o.y * o.y;
-  }
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) { const double ri = r[n - 1] - a * q[n - 1]; r[n - 1] = ri; s0 += ri * ri; }
-  for (int off = 32; off > 0; off >>= 1) s0 += __shfl_down(s0, off);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s0;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t0 = 0.0;
-    for (int w = 0; w < TB / 64; ++w) t0 += sh[w];
-    part[blockIdx.x] = t0; part[gridDim.x + blockIdx.x] = 0.0;
-  }
-}
-
-// one or two inner products, one pair of elements per lane, one-shot workgroups (see grid_vec): partial pair per workgroup ([2][gridDim.x];
-// NP = 1 leaves the second sum at zero so that the staged fold of the pairs serves both)
-template <int NP>
-__global__ __launch_bounds__(TB) void dot_block_vec_kernel(int64_t n, const double *__restrict__ x, const double *__restrict__ y,
-                                                           const double *__restrict__ z, const double *__restrict__ w, double *__restrict__ part) {
-  __shared__ double sh[2][TB / 64];
-  const int64_t n2 = n >> 1;
-  const vd2 *__restrict__ xv = reinterpret_cast<const vd2 *>(x);
-  const vd2 *__restrict__ yv = reinterpret_cast<const vd2 *>(y);
-  const vd2 *__restrict__ zv = reinterpret_cast<const vd2 *>(z);
-  const vd2 *__restrict__ wv = reinterpret_cast<const vd2 *>(w);
-  double s0 = 0.0, s1 = 0.0;
-  const int64_t stride = (int64_t)gridDim.x * TB;
-  for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < n2; i += stride) {
-    const vd2 p = xv[i], q = yv[i];
-    s0 += p.x * q.x; s0 += p.y * q.y;
-    if (NP == 2) { const vd2 a = zv[i], b = wv[i]; s1 += a.x * b.x; s1 += a.y * b.y; }
-  }
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) { s0 += x[n - 1] * y[n - 1]; if (NP == 2) s1 += z[n - 1] * w[n - 1]; }
-  for (int off = 32; off > 0; off >>= 1) { s0 += __shfl_down(s0, off); s1 += __shfl_down(s1, off); }
-  if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = s0; sh[1][threadIdx.x >> 6] = s1; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t0 = 0.0, t1 = 0.0;
-    for (int q = 0; q < TB / 64; ++q) { t0 += sh[0][q]; t1 += sh[1][q]; }
-    part[blockIdx.x] = t0; part[gridDim.x + blockIdx.x] = t1;
-  }
-}
-
-// ------------------------------------------------------------------ constant null space: v ← v − mean(v) (k_project_const)
-// Two launches beside the fold, the scalar stays on the device.  Sum pass: one partial per workgroup in a fixed layout ([2][gridDim.x], the
-// second sum zero so that dot2_mid_kernel / k_dot2_finish serve), folded in index order by one workgroup whose last step stores m = sum/n —
-// the order does not depend on scheduling, so m and with it every shifted entry is bit-reproducible from run to run.  Shift pass:
-// v_i ← v_i − m with m loaded once per lane; NRM adds ‖v − m‖² (partial pair per workgroup); STORE = false leaves v as it is (‖Πb‖ of the
-// caller's const right-hand side).  24 B per row for the pair (read, read, write).
-__global__ __launch_bounds__(TB) void sum_partial_kernel(int64_t n, const double *__restrict__ v, double *__restrict__ part) {
-  __shared__ double sh[TB / 64];
-  double s = 0.0;
-  int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
-  const int64_t stride = (int64_t)gridDim.x * TB;
-  for (; i < n; i += stride) s += v[i];
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) { double t = 0.0; for (int w = 0; w < TB / 64; ++w) t += sh[w]; part[blockIdx.x] = t; part[gridDim.x + blockIdx.x] = 0.0; }
-}
-// 16-byte form (lane t adds its pair x then y, a fixed order)
-__global__ __launch_bounds__(TB) void sum_partial_vec_kernel(int64_t n, const double *__restrict__ v, double *__restrict__ part) {
-  __shared__ double sh[TB / 64];
-  const int64_t n2 = n >> 1;
-  const vd2 *__restrict__ vv = reinterpret_cast<const vd2 *>(v);
-  double s = 0.0;
-  const int64_t stride = (int64_t)gridDim.x * TB;
-  for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < n2; i += stride) { const vd2 p = vv[i]; s += p.x; s += p.y; }
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) s += v[n - 1];
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) { double t = 0.0; for (int w = 0; w < TB / 64; ++w) t += sh[w]; part[blockIdx.x] = t; part[gridDim.x + blockIdx.x] = 0.0; }
-}
-__global__ __launch_bounds__(TB) void mean_final_kernel(int nb, const double *__restrict__ part, double n, double *__restrict__ mean) {
-  __shared__ double sh[TB];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < nb; i += TB) s += part[i];
-  sh[threadIdx.x] = s;
-  __syncthreads();
-  for (int w = TB / 2; w > 0; w >>= 1) { if (threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w]; __syncthreads(); }
-  if (threadIdx.x == 0) mean[0] = sh[0] / n;
-}
-template <bool STORE, bool NRM>
-__global__ __launch_bounds__(TB) void shift_const_kernel(int64_t n, double *__restrict__ v, const double *__restrict__ mean, double *__restrict__ part) {
-  __shared__ double sh[TB / 64];
-  const double m = mean[0];
-  double s0 = 0.0;
-  int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
-  const int64_t stride = (int64_t)gridDim.x * TB;
-  for (; i < n; i += stride) { const double o = v[i] - m; if (STORE) v[i] = o; if (NRM) s0 += o * o; }
-  if (!NRM) return;
-  for (int off = 32; off > 0; off >>= 1) s0 += __shfl_down(s0, off);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s0;
-  __syncthreads();
-  if (threadIdx.x == 0) { double t0 = 0.0; for (int w = 0; w < TB / 64; ++w) t0 += sh[w]; part[blockIdx.x] = t0; part[gridDim.x + blockIdx.x] = 0.0; }
-}
-// 16-byte form (same per-element expression: same bits)
-template <bool STORE, bool NRM>
-__global__ __launch_bounds__(TB) void shift_const_vec_kernel(int64_t n, double *__restrict__ v, const double *__restrict__ mean, double *__restrict__ part, int nts) {
-  __shared__ double sh[TB / 64];
-  const double m = mean[0];
-  const int64_t n2 = n >> 1;
-  vd2 *__restrict__ vv = reinterpret_cast<vd2 *>(v);
-  double s0 = 0.0;
-  const int64_t stride = (int64_t)gridDim.x * TB;
-  for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < n2; i += stride) {
-    const vd2 p = vv[i]; vd2 o;
-    o.x = p.x - m; o.y = p.y - m;
-    if (STORE) st2(vv + i, o, nts != 0);
-    if (NRM) { s0 += o.x * o.x; s0 += o.y * o.y; }
-  }
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) { const double o = v[n - 1] - m; if (STORE) v[n - 1] = o; if (NRM) s0 += o * o; }
-  if (!NRM) return;
-  for (int off = 32; off > 0; off >>= 1) s0 += __shfl_down(s0, off);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s0;
-  __syncthreads();
-  if (threadIdx.x == 0) { double t0 = 0.0; for (int w = 0; w < TB / 64; ++w) t0 += sh[w]; part[blockIdx.x] = t0; part[gridDim.x + blockIdx.x] = 0.0; }
-}
 // |v_i| in place (mgs_csr_nullspace_defect: |A| of a private copy)
 __global__ void abs_vals_kernel(int64_t n, double *__restrict__ v) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -618,147 +248,17 @@ __global__ void abs_vals_kernel(int64_t n, double *__restrict__ v) {
   for (; i < n; i += stride) v[i] = fabs(v[i]);
 }
 
-// ------------------------------------------------------------------ several inner products against one vector, one pass
-// s_k = Σ a_i·b_k[i], k < K ≤ MDOT_MAX: `a` is read once.  Partials [K][gridDim.x] in a fixed order (no atomics), folded by
-// mdot_final_kernel — the K-cycle's (ρ1, α1) and the flexible Krylov methods' orthogonalisation coefficients.
-constexpr int MDOT_MAX = 16;
-struct MDotVecs { const double *b[MDOT_MAX]; };
-__global__ __launch_bounds__(TB) void mdot_partial_kernel(int64_t n, int K, const double *__restrict__ a, const MDotVecs B, double *__restrict__ part) {
-  __shared__ double sh[MDOT_MAX][TB / 64];
-  double s[MDOT_MAX];
-#pragma unroll
-  for (int k = 0; k < MDOT_MAX; ++k) s[k] = 0.0;
-  const int64_t n2 = n >> 1, stride = (int64_t)gridDim.x * TB;
-  const vd2 *__restrict__ av = reinterpret_cast<const vd2 *>(a);
-  for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < n2; i += stride) {
-    const vd2 ai = av[i];
-#pragma unroll
-    for (int k = 0; k < MDOT_MAX; ++k)
-      if (k < K) { const vd2 bi = reinterpret_cast<const vd2 *>(B.b[k])[i]; s[k] += ai.x * bi.x; s[k] += ai.y * bi.y; }
-  }
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-#pragma unroll
-    for (int k = 0; k < MDOT_MAX; ++k) if (k < K) s[k] += a[n - 1] * B.b[k][n - 1];
-  }
-#pragma unroll
-  for (int k = 0; k < MDOT_MAX; ++k) {
-    if (k < K) {
-      double t = s[k];
-      for (int off = 32; off > 0; off >>= 1) t += __shfl_down(t, off);
-      if ((threadIdx.x & 63) == 0) sh[k][threadIdx.x >> 6] = t;
-    }
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < K) {
-    double t = 0.0;
-    for (int q = 0; q < TB / 64; ++q) t += sh[threadIdx.x][q];
-    part[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = t;
-  }
-}
-// fold of K partial arrays of nb entries each (one workgroup, fixed order); out (device) and, with pa.hv, the host's mapped buffer
-__global__ __launch_bounds__(TB) void mdot_final_kernel(int nb, int K, const double *__restrict__ part, double *__restrict__ out, Post pa) {
-  __shared__ double sh[TB];
-  __shared__ double res[MDOT_MAX + 4];
-  for (int k = 0; k < K; ++k) {
-    double s = 0.0;
-    for (int i = threadIdx.x; i < nb; i += TB) s += part[(size_t)k * nb + i];
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = TB / 2; w > 0; w >>= 1) { if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w]; __syncthreads(); }
-    if (threadIdx.x == 0) { res[k] = sh[0]; if (out) out[k] = sh[0]; }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0 && pa.hv) post_to_host(pa, res, K);
-}
-
-// z = x − Σ_{j<K} coef_j·w_j (coefficients by value: they come from the host, which needed them for its own bookkeeping), with
-// (z·z, z·u) accumulated in the same pass (u = NULL: second sum stays 0) — the orthogonalisation update of the flexible Krylov
-// methods: the new direction against the window, its norm and its product with the residual, one read of every vector.
-struct MAxpyArgs { const double *w[MDOT_MAX]; double coef[MDOT_MAX]; };
-template <bool VEC>
-__global__ __launch_bounds__(TB) void maxpy_dot2_kernel(int64_t n, int K, const double *__restrict__ x, const MAxpyArgs W, double *__restrict__ z,
-                                                        const double *__restrict__ u, const double *__restrict__ u2, double *__restrict__ part) {
-  __shared__ double sh[2][TB / 64];
-  double s0 = 0.0, s1 = 0.0;
-  const int64_t stride = (int64_t)gridDim.x * TB;
-  if (VEC) {              // 16 bytes per lane and stream (every operand 16-byte aligned; an odd last element goes to one lane below)
-    const int64_t n2 = n >> 1;
-    const vd2 *__restrict__ xv = reinterpret_cast<const vd2 *>(x);
-    vd2 *__restrict__ zv = reinterpret_cast<vd2 *>(z);
-    for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < n2; i += stride) {
-      vd2 zi = xv[i];
-#pragma unroll
-      for (int k = 0; k < MDOT_MAX; ++k)
-        if (k < K) { const vd2 wi = reinterpret_cast<const vd2 *>(W.w[k])[i]; zi.x -= W.coef[k] * wi.x; zi.y -= W.coef[k] * wi.y; }
-      zv[i] = zi;
-      if (part) {
-        if (u2) { const vd2 q = reinterpret_cast<const vd2 *>(u2)[i]; s0 += zi.x * q.x; s0 += zi.y * q.y; } else { s0 += zi.x * zi.x; s0 += zi.y * zi.y; }
-        if (u) { const vd2 q = reinterpret_cast<const vd2 *>(u)[i]; s1 += zi.x * q.x; s1 += zi.y * q.y; }
-      }
-    }
-    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-      double zi = x[n - 1];
-      for (int k = 0; k < K; ++k) zi -= W.coef[k] * W.w[k][n - 1];
-      z[n - 1] = zi;
-      s0 += zi * (u2 ? u2[n - 1] : zi);
-      if (u) s1 += zi * u[n - 1];
-    }
-  } else {
-    for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < n; i += stride) {
-      double zi = x[i];
-#pragma unroll
-      for (int k = 0; k < MDOT_MAX; ++k) if (k < K) zi -= W.coef[k] * W.w[k][i];
-      z[i] = zi;
-      s0 += zi * (u2 ? u2[i] : zi);
-      if (u) s1 += zi * u[i];
-    }
-  }
-  if (!part) return;                               // plain multi-axpy
-  for (int off = 32; off > 0; off >>= 1) { s0 += __shfl_down(s0, off); s1 += __shfl_down(s1, off); }
-  if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = s0; sh[1][threadIdx.x >> 6] = s1; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t0 = 0.0, t1 = 0.0;
-    for (int q = 0; q < TB / 64; ++q) { t0 += sh[0][q]; t1 += sh[1][q]; }
-    part[blockIdx.x] = t0; part[gridDim.x + blockIdx.x] = t1;
-  }
-}
-
 // ------------------------------------------------------------------ K-cycle helpers (device-resident scalars)
 // Two Krylov steps on the coarse problem (Notay, SISC 34 (2012), K-cycle; docs/AGMG_For_Convection_Diffusion.pdf §3.1) with the second
 // direction orthogonalised EXPLICITLY: scal = {ρ1 = d1·v1, α1 = d1·r, γ = d2·v1, ρ2 = d2'·v2', α2 = d2'·r'} with g = γ/ρ1,
 // c2' = c2 − g·c1, v2' = v2 − g·v1 and d = v (GCR form) or d = c (energy form).  ρ2 is a sum of products of the orthogonalised vectors,
 // not the difference β − γ²/ρ1 of two nearly equal numbers (round 3: lost up to five digits where c2 is almost parallel to c1).
-// No host round trip, graph-capturable.
+// No host round trip, graph-capturable.  The two elementwise kernels are here; the pair (ρ2, α2) is a reduction: kc_orth_dots_kernel, blas1.hip.
 __global__ void kc_update_r_kernel(int n, const double *__restrict__ scal, const double *__restrict__ r, const double *__restrict__ v1, double *__restrict__ rp) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const double rho1 = scal[0], a = rho1 != 0.0 ? scal[1] / rho1 : 0.0;
   rp[i] = r[i] - a * v1[i];
-}
-// (ρ2, α2) of the orthogonalised second direction: partial pair per workgroup
-template <bool ENERGY>
-__global__ __launch_bounds__(TB) void kc_orth_dots_kernel(int n, const double *__restrict__ scal, const double *__restrict__ c1, const double *__restrict__ c2,
-                                                          const double *__restrict__ v1, const double *__restrict__ v2, const double *__restrict__ rp,
-                                                          double *__restrict__ part) {
-  __shared__ double sh[2][TB / 64];
-  const double rho1 = scal[0], g = rho1 != 0.0 ? scal[2] / rho1 : 0.0;
-  double s0 = 0.0, s1 = 0.0;
-  const int stride = gridDim.x * TB;
-  for (int i = blockIdx.x * TB + threadIdx.x; i < n; i += stride) {
-    const double v2o = v2[i] - g * v1[i];
-    const double d2o = ENERGY ? c2[i] - g * c1[i] : v2o;
-    s0 += d2o * v2o;
-    s1 += d2o * rp[i];
-  }
-  for (int off = 32; off > 0; off >>= 1) { s0 += __shfl_down(s0, off); s1 += __shfl_down(s1, off); }
-  if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = s0; sh[1][threadIdx.x >> 6] = s1; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t0 = 0.0, t1 = 0.0;
-    for (int q = 0; q < TB / 64; ++q) { t0 += sh[0][q]; t1 += sh[1][q]; }
-    part[blockIdx.x] = t0; part[gridDim.x + blockIdx.x] = t1;
-  }
 }
 // x = (α1/ρ1)·c1 + (α2/ρ2)·(c2 − g·c1)
 __global__ void kc_combine_kernel(int n, const double *__restrict__ scal, const double *__restrict__ c1, const double *__restrict__ c2, double *__restrict__ x) {
@@ -952,32 +452,6 @@ __global__ void poisson2d_kernel(int n, int *__restrict__ rowptr, int *__restric
 }  // namespace
 
 // ============================================================ host launchers
-// Grid of the 16-byte update kernels: ONE pair per lane, one-shot workgroups (the loop in the kernels then runs once).  Measured at
-// 512³ (tools/studies_r1_r3/blas1_grid.py): axpby 0.695 ms with the capped persistent grid (n_cu × 8 workgroups, grid-stride, unroll 4), 0.541 ms
-// one-shot (5.96 TB/s); 2 / 4 / 8 pairs per lane: 0.568 / 0.623 / 0.671 ms — on this part a stream wants many short-lived
-// workgroups, not a few resident ones (the row-block kernels are one-shot already; tools/microbench/rw_mix.hip shows the same).
-// Option blas1_pairs = k: k pairs per lane (0: the capped grid), for that A/B.
-static inline int grid_vec(int64_t n2, const mgs_ctx *ctx) {
-  const int iters = ctx->opt_blas1_pairs;
-  int64_t g = (n2 + TB - 1) / TB;
-  if (iters > 0) { g = (g + iters - 1) / iters; return (int)(g < 1 ? 1 : g); }
-  const int64_t cap = (int64_t)ctx->n_cu * 8;
-  return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-}
-// per-workgroup partial pairs of a one-shot reduction launch ([2][nb] doubles; grown outside any capture)
-int mgs_ensure_dot_part(mgs_ctx *ctx, int64_t doubles) {
-  if (ctx->dot_part_cap >= doubles) return MGS_OK;
-  if (ctx->dot_part) { MGS_HIP(ctx, hipStreamSynchronize(ctx->stream)); mgs_hip_free(ctx->dot_part); ctx->dot_part = nullptr; ctx->dot_part_cap = 0; }
-  MGS_TRY(mgs_dev_alloc(ctx, &ctx->dot_part, (size_t)doubles));
-  ctx->dot_part_cap = doubles;
-  return MGS_OK;
-}
-static inline int grid_cap(int64_t n, int ncu) {
-  int64_t g = (n + TB - 1) / TB;
-  int64_t cap = (int64_t)ncu * 8;
-  return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-}
-
 int k_diag_inv(const mgs_csr *A, double *dinv, int *bad_count_host) {
   mgs_ctx *ctx = A->ctx;
   int *bad = nullptr;
@@ -1039,34 +513,12 @@ int k_jacobi_zero(mgs_ctx *ctx, int n, double omega, const double *dinv, const d
   return MGS_OK;
 }
 int k_fill(mgs_ctx *ctx, double *d, int64_t n, double v) {
-  if (n) hipLaunchKernelGGL(fill_kernel, dim3(grid_cap(n, ctx->n_cu)), dim3(TB), 0, ctx->stream, d, n, v);
+  if (n) hipLaunchKernelGGL(fill_kernel, dim3(mgs_blas1_grid_capped(ctx, n)), dim3(TB), 0, ctx->stream, d, n, v);
   MGS_HIP(ctx, hipGetLastError());
   return MGS_OK;
 }
 int k_rand(mgs_ctx *ctx, double *d, int64_t n, uint64_t seed, int64_t off) {
-  if (n) hipLaunchKernelGGL(rand_kernel, dim3(grid_cap(n, ctx->n_cu)), dim3(TB), 0, ctx->stream, d, n, seed, off);
-  MGS_HIP(ctx, hipGetLastError());
-  return MGS_OK;
-}
-int k_axpby(mgs_ctx *ctx, int64_t n, double a, const double *x, double b, double *y) {
-  if (n && ctx->opt_blas1_vec && al16(x) && al16(y)) {
-    const dim3 g(grid_vec((n + 1) / 2, ctx));
-    const int nts = ctx->opt_nt_store > 0 && n >= ctx->opt_nt_store;
-    if (b == 0.0) hipLaunchKernelGGL(axpby_vec_kernel<false>, g, dim3(TB), 0, ctx->stream, n, a, x, b, y, nts);
-    else hipLaunchKernelGGL(axpby_vec_kernel<true>, g, dim3(TB), 0, ctx->stream, n, a, x, b, y, nts);
-  } else
-  if (n) hipLaunchKernelGGL(axpby_kernel, dim3(grid_cap(n, ctx->n_cu)), dim3(TB), 0, ctx->stream, n, a, x, b, y);
-  MGS_HIP(ctx, hipGetLastError());
-  return MGS_OK;
-}
-int k_axpbypcz(mgs_ctx *ctx, int64_t n, double a, const double *x, double b, const double *y, double c, double *z) {
-  if (n && ctx->opt_blas1_vec && al16(x) && al16(y) && al16(z)) {
-    const dim3 g(grid_vec((n + 1) / 2, ctx));
-    const int nts = ctx->opt_nt_store > 0 && n >= ctx->opt_nt_store;
-    if (c == 0.0) hipLaunchKernelGGL(axpbypcz_vec_kernel<false>, g, dim3(TB), 0, ctx->stream, n, a, x, b, y, c, z, nts);
-    else hipLaunchKernelGGL(axpbypcz_vec_kernel<true>, g, dim3(TB), 0, ctx->stream, n, a, x, b, y, c, z, nts);
-  } else
-  if (n) hipLaunchKernelGGL(axpbypcz_kernel, dim3(grid_cap(n, ctx->n_cu)), dim3(TB), 0, ctx->stream, n, a, x, b, y, c, z);
+  if (n) hipLaunchKernelGGL(rand_kernel, dim3(mgs_blas1_grid_capped(ctx, n)), dim3(TB), 0, ctx->stream, d, n, seed, off);
   MGS_HIP(ctx, hipGetLastError());
   return MGS_OK;
 }
@@ -1137,319 +589,19 @@ int k_concat_i32(mgs_ctx *ctx, const int *a, int na, const int *b, int nb, int *
   MGS_HIP(ctx, hipGetLastError());
   return MGS_OK;
 }
-// ---- results of a reduction to the host without a copy engine and without an interrupt
-// The last stage of a reduction (one workgroup) stores the folded values into red_dev[DOT_BLOCKS ..] and, for the host, into the
-// context's mapped, coherent host buffer, then a ticket (system-scope release); the host polls the ticket.  Against hipMemcpyAsync + hipStreamSynchronize this removes
-// the blit/SDMA hop and the interrupt wake-up from every inner product of a Krylov loop: four per BiCGSTAB iteration — ≈ 60 of the
-// 135 µs of an iteration on the bundled operators, and on a freshly started box, where the first process' wake-ups take milliseconds,
-// 13 of 33 ms per iteration at 512³ (tools/studies_r1_r3/solve_repeat.py).  Option post_results = 0 restores copy + synchronize; so does any
-// transport that sums over ranks in between (ncomm / all-reduce callback), and a wait that sees no ticket for 2 s.
-static Post begin_post(mgs_ctx *ctx) {
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  const bool posted = ctx->opt_post_results && ctx->red_host_dev && !ctx->ncomm && hipStreamIsCapturing(ctx->stream, &cs) == hipSuccess &&
-                      cs == hipStreamCaptureStatusNone;
-  if (!posted) return Post{nullptr, nullptr, 0ull};
-  return Post{ctx->red_host_dev, reinterpret_cast<unsigned long long *>(ctx->red_host_dev + MGS_RED_VALS), ++ctx->red_ticket};
-}
-// the reduction's last kernel (launched with `pa`) has been enqueued: wait for its results
-static int fetch_results(mgs_ctx *ctx, int cnt, double *out_host, const Post &pa) {
-  if (pa.hv) {
-    volatile unsigned long long *tk = reinterpret_cast<volatile unsigned long long *>(ctx->red_host + MGS_RED_VALS);
-    const unsigned long long want = pa.ticket;
-    MGS_HIP(ctx, hipGetLastError());
-    const auto t0 = std::chrono::steady_clock::now();
-    bool seen = false;
-    for (;;) {
-      if (__atomic_load_n(const_cast<unsigned long long *>(tk), __ATOMIC_ACQUIRE) == want) { seen = true; break; }
-      const double waited = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-      if (waited > 2.0) break;                                   // never seen: fall back to the stream's own completion below
-      if (waited < 300e-6) { for (int q = 0; q < 8; ++q) __builtin_ia32_pause(); }
-      else { struct timespec ts = {0, 25000}; nanosleep(&ts, nullptr); }     // long kernels ahead of the ticket: stop burning the core
-    }
-    if (!seen) {
-      MGS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      if (__atomic_load_n(const_cast<unsigned long long *>(tk), __ATOMIC_ACQUIRE) != want)
-        return mgs_fail(ctx, MGS_ERR_HIP, "reduction results never reached the host buffer");
-    }
-    for (int q = 0; q < cnt; ++q) out_host[q] = ctx->red_host[q];
-  } else {
-    MGS_HIP(ctx, hipMemcpyAsync(ctx->red_host, ctx->red_dev + DOT_BLOCKS, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, ctx->stream));
-    MGS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int q = 0; q < cnt; ++q) out_host[q] = ctx->red_host[q];
-  }
-  if (ctx->allreduce && !ctx->ncomm) {
-    int rc = ctx->allreduce(ctx->allreduce_user, out_host, cnt);
-    if (rc) return mgs_fail(ctx, MGS_ERR_STATE, "allreduce callback failed (%d)", rc);
-  }
-  return MGS_OK;
-}
-
-// "Enqueue and fold" without "fetch" (mgs_pcg_plan, pcg_plan.hip): a reduction called with a NULL host pointer launches exactly what it
-// launches otherwise, posts nothing and returns as soon as the fold is enqueued; the folded values stay in red_dev[DOT_BLOCKS ..], where the
-// next kernel on the stream finds them.  With a host pointer nothing changes.
-static const Post NO_POST = {nullptr, nullptr, 0ull};
-static int fetch_or_leave(mgs_ctx *ctx, int cnt, double *out_host, const Post &pa) {
-  if (out_host) return fetch_results(ctx, cnt, out_host, pa);
-  MGS_HIP(ctx, hipGetLastError());
-  return MGS_OK;
-}
-int mgs_blas1_grid(const mgs_ctx *ctx, int64_t n2) { return grid_vec(n2, ctx); }
-int mgs_blas1_grid_capped(const mgs_ctx *ctx, int64_t n) { return grid_cap(n, ctx->n_cu); }
-
-int k_dot(mgs_ctx *ctx, int64_t n, const double *x, const double *y, double *out_host) {
-  if (ctx->opt_blas1_vec && n >= 2 && al16(x) && al16(y)) {       // one-shot workgroups, staged fold (as the fused update kernels)
-    const int nbv = grid_vec(n / 2, ctx);
-    double *part = ctx->red_dev;
-    if (nbv > DOT_BLOCKS / 2) { MGS_TRY(mgs_ensure_dot_part(ctx, 2 * (int64_t)nbv)); part = ctx->dot_part; }
-    hipLaunchKernelGGL(dot_block_vec_kernel<1>, dim3(nbv), dim3(TB), 0, ctx->stream, n, x, y, x, y, part);
-    MGS_HIP(ctx, hipGetLastError());
-    if (!out_host) return k_dot2_finish(ctx, nbv, part, nullptr);
-    double two[2] = {0.0, 0.0};
-    MGS_TRY(k_dot2_finish(ctx, nbv, part, two));
-    *out_host = two[0];
-    return MGS_OK;
-  }
-  int nb = (int)((n + TB - 1) / TB);
-  if (nb > DOT_BLOCKS) nb = DOT_BLOCKS;
-  if (nb < 1) nb = 1;
-  hipLaunchKernelGGL(dot_partial_kernel, dim3(nb), dim3(TB), 0, ctx->stream, n, x, y, ctx->red_dev);
-  const Post pa = out_host ? begin_post(ctx) : NO_POST;
-  hipLaunchKernelGGL(dot_final_kernel, dim3(1), dim3(TB), 0, ctx->stream, nb, ctx->red_dev, ctx->red_dev + DOT_BLOCKS, pa);
-  if (ctx->ncomm) MGS_TRY(mgs_comm_allreduce_sum(ctx->ncomm, ctx->red_dev + DOT_BLOCKS, 1));   // sum over the row shards, on this stream
-  return fetch_or_leave(ctx, 1, out_host, pa);
-}
-
-// middle stage for long partial arrays (one pair per row block of a 512³ operator = 2 × 524 288): workgroup g sums the g-th
-// contiguous chunk of each array in a fixed order
-__global__ __launch_bounds__(TB) void dot2_mid_kernel(int nb, int chunk, const double *__restrict__ part, double *__restrict__ out /*[2][gridDim.x]*/) {
-  __shared__ double sh[2][TB / 64];
-  const int lo = blockIdx.x * chunk, hi = min(lo + chunk, nb);
-  double s0 = 0.0, s1 = 0.0;
-  for (int i = lo + threadIdx.x; i < hi; i += TB) { s0 += part[i]; s1 += part[nb + i]; }
-  for (int off = 32; off > 0; off >>= 1) { s0 += __shfl_down(s0, off); s1 += __shfl_down(s1, off); }
-  if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = s0; sh[1][threadIdx.x >> 6] = s1; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t0 = 0.0, t1 = 0.0;
-    for (int q = 0; q < TB / 64; ++q) { t0 += sh[0][q]; t1 += sh[1][q]; }
-    out[blockIdx.x] = t0; out[gridDim.x + blockIdx.x] = t1;
-  }
-}
-int k_dot2_finish(mgs_ctx *ctx, int nb, const double *part, double *out_host2) {
-  if (nb > 4096) {          // three stages: row-block partials → 256 chunk sums (in red_dev) → the pair
-    const int groups = 256, chunk = (nb + groups - 1) / groups;
-    hipLaunchKernelGGL(dot2_mid_kernel, dim3(groups), dim3(TB), 0, ctx->stream, nb, chunk, part, ctx->red_dev);
-    part = ctx->red_dev; nb = groups;
-  }
-  const Post pa = out_host2 ? begin_post(ctx) : NO_POST;
-  hipLaunchKernelGGL(dot2_final_kernel, dim3(1), dim3(TB), 0, ctx->stream, nb, part, ctx->red_dev + DOT_BLOCKS, pa);
-  MGS_HIP(ctx, hipGetLastError());
-  if (ctx->ncomm) MGS_TRY(mgs_comm_allreduce_sum(ctx->ncomm, ctx->red_dev + DOT_BLOCKS, 2));
-  return fetch_or_leave(ctx, 2, out_host2, pa);
-}
-int k_dot2(mgs_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w, double *out_host2) {
-  if (ctx->opt_blas1_vec && n >= 2 && al16(x) && al16(y) && al16(z) && al16(w)) {
-    const int nbv = grid_vec(n / 2, ctx);
-    double *part = ctx->red_dev;
-    if (nbv > DOT_BLOCKS / 2) { MGS_TRY(mgs_ensure_dot_part(ctx, 2 * (int64_t)nbv)); part = ctx->dot_part; }
-    hipLaunchKernelGGL(dot_block_vec_kernel<2>, dim3(nbv), dim3(TB), 0, ctx->stream, n, x, y, z, w, part);
-    MGS_HIP(ctx, hipGetLastError());
-    return k_dot2_finish(ctx, nbv, part, out_host2);
-  }
-  int nb = (int)((n + TB - 1) / TB);
-  if (nb > DOT_BLOCKS / 2) nb = DOT_BLOCKS / 2;
-  if (nb < 1) nb = 1;
-  hipLaunchKernelGGL(dot2_partial_kernel, dim3(nb), dim3(TB), 0, ctx->stream, n, x, y, z, w, ctx->red_dev);
-  const Post pa = out_host2 ? begin_post(ctx) : NO_POST;
-  hipLaunchKernelGGL(dot2_final_kernel, dim3(1), dim3(TB), 0, ctx->stream, nb, ctx->red_dev, ctx->red_dev + DOT_BLOCKS, pa);
-  if (ctx->ncomm) MGS_TRY(mgs_comm_allreduce_sum(ctx->ncomm, ctx->red_dev + DOT_BLOCKS, 2));
-  return fetch_or_leave(ctx, 2, out_host2, pa);
-}
-int k_update_dot2(mgs_ctx *ctx, int64_t n, double a, const double *x, double b, const double *y, double *z, const double *w, double *out_host2) {
-  int nb = (int)((n + TB - 1) / TB);
-  if (nb > DOT_BLOCKS / 2) nb = DOT_BLOCKS / 2;
-  if (nb < 1) nb = 1;
-  if (ctx->opt_blas1_vec && al16(x) && al16(y) && al16(z) && al16(w)) {
-    // one-shot workgroups (see grid_vec): one partial pair per workgroup, folded in fixed order by k_dot2_finish
-    nb = grid_vec((n + 1) / 2, ctx);
-    const int nts = ctx->opt_nt_store > 0 && n >= ctx->opt_nt_store;
-    double *part = ctx->red_dev;
-    if (nb > DOT_BLOCKS / 2) { MGS_TRY(mgs_ensure_dot_part(ctx, 2 * (int64_t)nb)); part = ctx->dot_part; }
-    if (w) hipLaunchKernelGGL(update_dot2_partial_vec_kernel<true>, dim3(nb), dim3(TB), 0, ctx->stream, n, a, x, b, y, z, w, part, nts);
-    else hipLaunchKernelGGL(update_dot2_partial_vec_kernel<false>, dim3(nb), dim3(TB), 0, ctx->stream, n, a, x, b, y, z, w, part, nts);
-    MGS_HIP(ctx, hipGetLastError());
-    return k_dot2_finish(ctx, nb, part, out_host2);
-  }
-  hipLaunchKernelGGL(update_dot2_partial_kernel, dim3(nb), dim3(TB), 0, ctx->stream, n, a, x, b, y, z, w, ctx->red_dev);
-  const Post pa = begin_post(ctx);
-  hipLaunchKernelGGL(dot2_final_kernel, dim3(1), dim3(TB), 0, ctx->stream, nb, ctx->red_dev, ctx->red_dev + DOT_BLOCKS, pa);
-  if (ctx->ncomm) MGS_TRY(mgs_comm_allreduce_sum(ctx->ncomm, ctx->red_dev + DOT_BLOCKS, 2));
-  return fetch_results(ctx, 2, out_host2, pa);
-}
-// mgs_pcg, direction pass: first != 0: p ← z (p not read, x not touched); else x ← x + a·p, p ← z + beta·p
-int k_pcg_direction(mgs_ctx *ctx, int64_t n, int first, double a, double beta, double *x, double *p, const double *z) {
-  if (!n) return MGS_OK;
-  if (ctx->opt_blas1_vec && al16(p) && al16(z) && (first || al16(x))) {
-    const dim3 g(grid_vec((n + 1) / 2, ctx));
-    const int nts = ctx->opt_nt_store > 0 && n >= ctx->opt_nt_store;
-    if (first) hipLaunchKernelGGL(pcg_dir_vec_kernel<true>, g, dim3(TB), 0, ctx->stream, n, a, beta, x, p, z, nts);
-    else hipLaunchKernelGGL(pcg_dir_vec_kernel<false>, g, dim3(TB), 0, ctx->stream, n, a, beta, x, p, z, nts);
-  } else {
-    const dim3 g(grid_cap(n, ctx->n_cu));
-    if (first) hipLaunchKernelGGL(pcg_dir_kernel<true>, g, dim3(TB), 0, ctx->stream, n, a, beta, x, p, z);
-    else hipLaunchKernelGGL(pcg_dir_kernel<false>, g, dim3(TB), 0, ctx->stream, n, a, beta, x, p, z);
-  }
-  MGS_HIP(ctx, hipGetLastError());
-  return MGS_OK;
-}
-// mgs_pcg, residual pass in place: r ← r − a·q, out_host2[0] = ‖r‖² (summed over the row shards), out_host2[1] = 0
-int k_pcg_residual(mgs_ctx *ctx, int64_t n, double a, double *r, const double *q, double *out_host2) {
-  if (ctx->opt_blas1_vec && al16(r) && al16(q)) {
-    const int nb = grid_vec((n + 1) / 2, ctx);
-    const int nts = ctx->opt_nt_store > 0 && n >= ctx->opt_nt_store;
-    double *part = ctx->red_dev;
-    if (nb > DOT_BLOCKS / 2) { MGS_TRY(mgs_ensure_dot_part(ctx, 2 * (int64_t)nb)); part = ctx->dot_part; }
-    hipLaunchKernelGGL(pcg_resid_vec_kernel, dim3(nb), dim3(TB), 0, ctx->stream, n, a, r, q, part, nts);
-    MGS_HIP(ctx, hipGetLastError());
-    return k_dot2_finish(ctx, nb, part, out_host2);
-  }
-  int nb = (int)((n + TB - 1) / TB);
-  if (nb > DOT_BLOCKS / 2) nb = DOT_BLOCKS / 2;
-  if (nb < 1) nb = 1;
-  hipLaunchKernelGGL(pcg_resid_kernel, dim3(nb), dim3(TB), 0, ctx->stream, n, a, r, q, ctx->red_dev);
-  MGS_HIP(ctx, hipGetLastError());
-  return k_dot2_finish(ctx, nb, ctx->red_dev, out_host2);
-}
-// ---- constant null space: v ← v − mean(v)
-// The mean stays on the device, behind the folded results of the reductions (red_dev[DOT_BLOCKS + MGS_RED_VALS]).
-constexpr int MEAN_SLOT = DOT_BLOCKS + MGS_RED_VALS;
-static_assert(DOT_BLOCKS == MGS_DOT_BLOCKS && MEAN_SLOT < MGS_RED_CAP, "the mean slot lies behind the folded results, inside mgs_ctx::red_dev");
-// store: v is shifted in place (else only read); nrm2_host != NULL: nrm2_host[0] = ‖v − m‖² reaches the host (k_dot2_finish), nrm2_host[1] = 0
-static int project_const_impl(mgs_ctx *ctx, int64_t n, double *v, bool store, double *nrm2_host, bool nrm2_fold = false) {
-  if (n <= 0) { if (nrm2_host) nrm2_host[0] = nrm2_host[1] = 0.0; return MGS_OK; }
-  const bool vec = ctx->opt_blas1_vec && al16(v);
-  int nb = vec ? grid_vec((n + 1) / 2, ctx) : std::max(1, std::min(mgs_grid(n, TB), DOT_BLOCKS / 2));
-  double *part = ctx->red_dev, *mean = ctx->red_dev + MEAN_SLOT;
-  if (nb > DOT_BLOCKS / 2) { MGS_TRY(mgs_ensure_dot_part(ctx, 2 * (int64_t)nb)); part = ctx->dot_part; }
-  hipStream_t s = ctx->stream;
-  if (vec) hipLaunchKernelGGL(sum_partial_vec_kernel, dim3(nb), dim3(TB), 0, s, n, v, part);
-  else hipLaunchKernelGGL(sum_partial_kernel, dim3(nb), dim3(TB), 0, s, n, v, part);
-  const double *fold = part; int nf = nb;
-  if (nf > 4096) {          // long partial arrays: 256 chunk sums first (in red_dev), as k_dot2_finish does
-    const int groups = 256, chunk = (nf + groups - 1) / groups;
-    hipLaunchKernelGGL(dot2_mid_kernel, dim3(groups), dim3(TB), 0, s, nf, chunk, part, ctx->red_dev);
-    fold = ctx->red_dev; nf = groups;
-  }
-  hipLaunchKernelGGL(mean_final_kernel, dim3(1), dim3(TB), 0, s, nf, fold, (double)n, mean);
-  const int nts = ctx->opt_nt_store > 0 && n >= ctx->opt_nt_store;
-  const bool nrm = nrm2_host != nullptr || nrm2_fold;
-#define SHIFT_(ST, NR)                                                                                                              \
-  do {                                                                                                                              \
-    if (vec) hipLaunchKernelGGL((shift_const_vec_kernel<ST, NR>), dim3(nb), dim3(TB), 0, s, n, v, mean, part, nts);                  \
-    else hipLaunchKernelGGL((shift_const_kernel<ST, NR>), dim3(nb), dim3(TB), 0, s, n, v, mean, part);                               \
-  } while (0)
-  if (store && nrm) SHIFT_(true, true); else if (store) SHIFT_(true, false); else if (nrm) SHIFT_(false, true);
-#undef SHIFT_
-  MGS_HIP(ctx, hipGetLastError());
-  return nrm ? k_dot2_finish(ctx, nb, part, nrm2_host) : MGS_OK;
-}
-int k_project_const(mgs_ctx *ctx, int64_t n, double *v) { return project_const_impl(ctx, n, v, true, nullptr); }
-int k_project_const_nrm2(mgs_ctx *ctx, int64_t n, double *v, double *out_host2) { return project_const_impl(ctx, n, v, true, out_host2); }
-int k_const_dev_nrm2(mgs_ctx *ctx, int64_t n, const double *v, double *out_host2) { return project_const_impl(ctx, n, const_cast<double *>(v), false, out_host2); }
-// the mean the last projection on this context subtracted (diagnostics; synchronises)
-// the same two with the norm left on the device (red_dev[DOT_BLOCKS], see fetch_or_leave): no host round trip
-int k_project_const_nrm2_fold(mgs_ctx *ctx, int64_t n, double *v) { return project_const_impl(ctx, n, v, true, nullptr, true); }
-int k_const_dev_nrm2_fold(mgs_ctx *ctx, int64_t n, const double *v) { return project_const_impl(ctx, n, const_cast<double *>(v), false, nullptr, true); }
-int k_project_const_mean(mgs_ctx *ctx, double *mean_host) {
-  MGS_HIP(ctx, hipMemcpyAsync(mean_host, ctx->red_dev + MEAN_SLOT, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  MGS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return MGS_OK;
-}
 int k_abs_inplace(mgs_ctx *ctx, int64_t n, double *v) {
-  if (n) hipLaunchKernelGGL(abs_vals_kernel, dim3(grid_cap(n, ctx->n_cu)), dim3(TB), 0, ctx->stream, n, v);
+  if (n) hipLaunchKernelGGL(abs_vals_kernel, dim3(mgs_blas1_grid_capped(ctx, n)), dim3(TB), 0, ctx->stream, n, v);
   MGS_HIP(ctx, hipGetLastError());
   return MGS_OK;
 }
 // max_i |v_i| as the bits of a non-negative double, folded into *amax_bits_dev (the caller zeroes it; a NaN wins): dense_absmax_kernel
 int k_absmax_dev(mgs_ctx *ctx, int64_t n, const double *v, unsigned long long *amax_bits_dev) {
-  if (n) hipLaunchKernelGGL(dense_absmax_kernel, dim3(grid_cap(n, ctx->n_cu)), dim3(TB), 0, ctx->stream, n, v, amax_bits_dev);
+  if (n) hipLaunchKernelGGL(dense_absmax_kernel, dim3(mgs_blas1_grid_capped(ctx, n)), dim3(TB), 0, ctx->stream, n, v, amax_bits_dev);
   MGS_HIP(ctx, hipGetLastError());
   return MGS_OK;
-}
-int k_dot_dev(mgs_ctx *ctx, int64_t n, const double *x, const double *y, double *out_dev) {
-  int nb = (int)((n + TB - 1) / TB);
-  if (nb > DOT_BLOCKS) nb = DOT_BLOCKS;
-  if (nb < 1) nb = 1;
-  hipLaunchKernelGGL(dot_partial_kernel, dim3(nb), dim3(TB), 0, ctx->stream, n, x, y, ctx->red_dev);
-  hipLaunchKernelGGL(dot_final_kernel, dim3(1), dim3(TB), 0, ctx->stream, nb, ctx->red_dev, out_dev, Post{nullptr, nullptr, 0ull});
-  MGS_HIP(ctx, hipGetLastError());
-  return MGS_OK;
-}
-// workgroups of a multi-vector reduction pass: one-shot at small sizes, a few elements per lane at large ones (partials stay short)
-static int mdot_grid(int64_t n) {
-  int64_t nb = (n / 2 + (int64_t)TB * 4 - 1) / ((int64_t)TB * 4);
-  return (int)std::min<int64_t>(std::max<int64_t>(nb, 1), 2048);
-}
-// s_k = a·b_k, k < K ≤ MDOT_MAX: to device scalars (out_dev) and/or, summed over the ranks, to the host (out_host)
-int k_mdot(mgs_ctx *ctx, int64_t n, int K, const double *a, const double *const *b, double *out_dev, double *out_host) {
-  MGS_CHECK(ctx, K >= 1 && K <= MDOT_MAX && K <= MGS_RED_VALS, MGS_ERR_INVALID, "k_mdot: %d inner products (at most %d)", K, MDOT_MAX);
-  MDotVecs B;
-  bool aligned = al16(a);
-  for (int k = 0; k < MDOT_MAX; ++k) { B.b[k] = k < K ? b[k] : a; if (k < K && !al16(b[k])) aligned = false; }
-  const int nb = mdot_grid(n);
-  double *part = ctx->red_dev;        // (the K-cycle's pairs always fit the context's own scratch: nothing is allocated inside a captured cycle)
-  if ((int64_t)K * nb > DOT_BLOCKS) { MGS_TRY(mgs_ensure_dot_part(ctx, (int64_t)K * nb)); part = ctx->dot_part; }
-  double *res = out_dev ? out_dev : ctx->red_dev + DOT_BLOCKS;
-  if (!aligned) {      // operands that do not start on 16 bytes (views into the middle of a vector): K two-vector reductions
-    for (int k = 0; k < K; ++k) MGS_TRY(k_dot_dev(ctx, n, a, b[k], res + k));
-    if (!out_host) return MGS_OK;
-    if (ctx->ncomm) {
-      if (res != ctx->red_dev + DOT_BLOCKS) MGS_HIP(ctx, hipMemcpyAsync(ctx->red_dev + DOT_BLOCKS, res, sizeof(double) * (size_t)K, hipMemcpyDeviceToDevice, ctx->stream));
-      MGS_TRY(mgs_comm_allreduce_sum(ctx->ncomm, ctx->red_dev + DOT_BLOCKS, (size_t)K));
-      res = ctx->red_dev + DOT_BLOCKS;
-    }
-    MGS_HIP(ctx, hipMemcpyAsync(ctx->red_host, res, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost, ctx->stream));
-    MGS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int k = 0; k < K; ++k) out_host[k] = ctx->red_host[k];
-    if (ctx->allreduce && !ctx->ncomm && ctx->allreduce(ctx->allreduce_user, out_host, K)) return mgs_fail(ctx, MGS_ERR_STATE, "allreduce callback failed");
-    return MGS_OK;
-  }
-  hipLaunchKernelGGL(mdot_partial_kernel, dim3(nb), dim3(TB), 0, ctx->stream, n, K, a, B, part);
-  const Post pa = out_host ? begin_post(ctx) : Post{nullptr, nullptr, 0ull};
-  hipLaunchKernelGGL(mdot_final_kernel, dim3(1), dim3(TB), 0, ctx->stream, nb, K, part, res, pa);
-  MGS_HIP(ctx, hipGetLastError());
-  if (!out_host) return MGS_OK;
-  if (res != ctx->red_dev + DOT_BLOCKS) MGS_HIP(ctx, hipMemcpyAsync(ctx->red_dev + DOT_BLOCKS, res, sizeof(double) * (size_t)K, hipMemcpyDeviceToDevice, ctx->stream));   // where fetch_results looks
-  if (ctx->ncomm) MGS_TRY(mgs_comm_allreduce_sum(ctx->ncomm, ctx->red_dev + DOT_BLOCKS, (size_t)K));
-  return fetch_results(ctx, K, out_host, pa);
-}
-// z = x − Σ_{j<K} coef_j·w_j with (z·u2 — or z·z when u2 is NULL —, z·u) to the host in the same pass (out_host2 = NULL: no sums, no round trip)
-int k_maxpy_dot2(mgs_ctx *ctx, int64_t n, int K, const double *x, const double *const *w, const double *coef, double *z, const double *u, const double *u2, double *out_host2) {
-  MGS_CHECK(ctx, K >= 0 && K <= MDOT_MAX, MGS_ERR_INVALID, "k_maxpy_dot2: %d terms (at most %d)", K, MDOT_MAX);
-  MAxpyArgs W;
-  for (int k = 0; k < MDOT_MAX; ++k) { W.w[k] = k < K ? w[k] : x; W.coef[k] = k < K ? coef[k] : 0.0; }
-  bool vec = n >= 2 && al16(x) && al16(z) && (!u || al16(u)) && (!u2 || al16(u2));
-  for (int k = 0; k < K; ++k) vec = vec && al16(w[k]);
-  int64_t nbl = (n + (int64_t)TB * 4 - 1) / ((int64_t)TB * 4);       // two 16-byte (or four 8-byte) elements per lane
-  const int nb = (int)std::min<int64_t>(std::max<int64_t>(nbl, 1), 1 << 20);
-  double *part = nullptr;
-  if (out_host2) { part = ctx->red_dev; if (nb > DOT_BLOCKS / 2) { MGS_TRY(mgs_ensure_dot_part(ctx, 2 * (int64_t)nb)); part = ctx->dot_part; } }
-  if (vec) hipLaunchKernelGGL(maxpy_dot2_kernel<true>, dim3(nb), dim3(TB), 0, ctx->stream, n, K, x, W, z, u, u2, part);
-  else hipLaunchKernelGGL(maxpy_dot2_kernel<false>, dim3(nb), dim3(TB), 0, ctx->stream, n, K, x, W, z, u, u2, part);
-  MGS_HIP(ctx, hipGetLastError());
-  return out_host2 ? k_dot2_finish(ctx, nb, part, out_host2) : MGS_OK;
 }
 int k_kc_update_r(mgs_ctx *ctx, int n, const double *scal, const double *r, const double *v1, double *rp) {
   if (n) hipLaunchKernelGGL(kc_update_r_kernel, dim3(mgs_grid(n, TB)), dim3(TB), 0, ctx->stream, n, scal, r, v1, rp);
-  MGS_HIP(ctx, hipGetLastError());
-  return MGS_OK;
-}
-// scal[3] = ρ2, scal[4] = α2 of the explicitly orthogonalised second direction (see kc_orth_dots_kernel)
-int k_kc_orth_dots(mgs_ctx *ctx, int n, bool energy, double *scal, const double *c1, const double *c2, const double *v1, const double *v2, const double *rp) {
-  const int nb = std::max(1, std::min(mgs_grid(n, TB * 4), DOT_BLOCKS / 2));
-  if (energy) hipLaunchKernelGGL(kc_orth_dots_kernel<true>, dim3(nb), dim3(TB), 0, ctx->stream, n, scal, c1, c2, v1, v2, rp, ctx->red_dev);
-  else hipLaunchKernelGGL(kc_orth_dots_kernel<false>, dim3(nb), dim3(TB), 0, ctx->stream, n, scal, c1, c2, v1, v2, rp, ctx->red_dev);
-  hipLaunchKernelGGL(dot2_final_kernel, dim3(1), dim3(TB), 0, ctx->stream, nb, ctx->red_dev, scal + 3, Post{nullptr, nullptr, 0ull});
   MGS_HIP(ctx, hipGetLastError());
   return MGS_OK;
 }
@@ -1486,7 +638,7 @@ int k_dense_inverse(mgs_ctx *ctx, const mgs_csr *A, double **inv_out, int reg_co
     MGS_HIP(ctx, hipMemsetAsync(W, 0, sizeof(double) * (size_t)n * 2 * n, s));
     MGS_HIP(ctx, hipMemsetAsync(piv, 0, 2 * sizeof(int), s));
     MGS_HIP(ctx, hipMemsetAsync(amax, 0, sizeof(unsigned long long), s));
-    if (A->nnz) hipLaunchKernelGGL(dense_absmax_kernel, dim3(grid_cap(A->nnz, ctx->n_cu)), dim3(TB), 0, s, (int64_t)A->nnz, A->val, amax);
+    if (A->nnz) hipLaunchKernelGGL(dense_absmax_kernel, dim3(mgs_blas1_grid_capped(ctx, A->nnz)), dim3(TB), 0, s, (int64_t)A->nnz, A->val, amax);
     if (n) hipLaunchKernelGGL(dense_scatter_kernel, dim3(mgs_grid(n, TB)), dim3(TB), 0, s, n, A->rowptr, A->col, A->val, W);
     if (n && reg_const) hipLaunchKernelGGL(dense_reg_const_kernel, dim3(mgs_grid(n, TB), n), dim3(TB), 0, s, n, W, amax);
     for (int k = 0; k < n; ++k) {

@@ -235,7 +235,7 @@ int mgs_fgcr(const mgs_csr *A, mgs_vec *x, const mgs_vec *b, mgs_hier *h, int re
   MGS_TRY(mgs_krylov_nullspace(A, h, "mgs_fgcr", &ns));
   MGS_TRY(mgs_csr_optimize(const_cast<mgs_csr *>(A)));
   const int n = A->rows;
-  constexpr int CH = 16;                             // vectors per multi-vector pass (kernels_aux.hip: MDOT_MAX)
+  constexpr int CH = 16;                             // vectors per multi-vector pass (blas1.hip: MDOT_MAX)
   krylov_frame f{ctx, h, n, ns, false, {}};
   mgs_vec *r = nullptr; MGS_TRY(f.take(&r, n));
   std::vector<mgs_vec *> C((size_t)restart, nullptr), V((size_t)restart, nullptr);

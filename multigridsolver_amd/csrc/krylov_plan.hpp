@@ -5,36 +5,13 @@
 #include <chrono>
 #include <time.h>
 
+#include "blas1.hpp"
 #include "krylov_lookahead.hpp"
-#include "mgs_internal.hpp"
 
 namespace krylov {
-constexpr int PTB = 256;                 // lanes per workgroup of the vector passes (the BLAS-1 kernels' TB)
+using blas1::vd2; using blas1::st2; using blas1::al16; using blas1::nts_of;      // the vector passes end in BLAS1_FOLD1 / BLAS1_FOLD2
+constexpr int PTB = blas1::TB;           // lanes per workgroup of the vector passes
 constexpr int RED = MGS_DOT_BLOCKS;      // red_dev[RED], red_dev[RED + 1]: what the last fold left
-typedef double kd2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void kst2(kd2 *p, kd2 v, bool nt) {      // streaming store, as st2 in kernels_aux.hip
-  if (nt) asm volatile("global_store_dwordx4 %0, %1, off nt" : : "v"(p), "v"(v) : "memory");
-  else *p = v;
-}
-inline bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-inline int nts_of(const mgs_ctx *ctx, int64_t n) { return ctx->opt_nt_store > 0 && n >= ctx->opt_nt_store; }
-
-// The end of every pass with two sums: the lanes' pair (s0, s1) folded over the wave, then over the workgroup's PTB/64 waves, into the partials
-// [2][gridDim.x] that k_dot2_finish folds.  Every lane of the workgroup comes here; sh: the kernel's __shared__ double [2][PTB / 64].
-// A macro, not a function: as an inlined function the same statements were scheduled differently in five of the nine passes
-// (profiles/r17_krylov_plan_base.md), and the passes are held to the instructions they had.
-#define KRYLOV_FOLD2(s0, s1, sh, part)                                                                                    \
-  do {                                                                                                                    \
-    for (int off = 32; off > 0; off >>= 1) { s0 += __shfl_down(s0, off); s1 += __shfl_down(s1, off); }                    \
-    if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = s0; sh[1][threadIdx.x >> 6] = s1; }                          \
-    __syncthreads();                                                                                                      \
-    if (threadIdx.x == 0) {                                                                                               \
-      double t0 = 0.0, t1 = 0.0;                                                                                          \
-      for (int q = 0; q < PTB / 64; ++q) { t0 += sh[0][q]; t1 += sh[1][q]; }                                              \
-      part[blockIdx.x] = t0; part[gridDim.x + blockIdx.x] = t1;                                                           \
-    }                                                                                                                     \
-  } while (0)
 
 // What a posting step leaves for the host.  aux0, aux1: fields of the state that only its own plan reads (mgs_fgcr_plan: why, m_open), or 0
 struct Slot {      // 64 bytes of mapped host memory

@@ -24,7 +24,7 @@ struct mgs_launch_report {
   const int *tptr = nullptr;   // device: table bounds of the pattern code the launch handed to its kernel (NULL: none, no block is coded)
 };
 constexpr int MGS_RED_VALS = 32;   // results one reduction can hand to the host (mgs_ctx::red_host)
-// mgs_ctx::red_dev (kernels_aux.hip): MGS_DOT_BLOCKS partial slots, then MGS_RED_VALS folded results, then MGS_RED_VALS device-only scalars
+// mgs_ctx::red_dev (blas1.hip): MGS_DOT_BLOCKS partial slots, then MGS_RED_VALS folded results, then MGS_RED_VALS device-only scalars
 // (the first one: the mean of the last k_project_const)
 constexpr int MGS_DOT_BLOCKS = 4096;
 constexpr int MGS_RED_CAP = MGS_DOT_BLOCKS + 2 * MGS_RED_VALS;
@@ -422,7 +422,7 @@ int mgs_launch_group_pre(const mgs_csr *Ahat, const mgs_groups *G, const mgs_xfe
                          double *t_out, double *r_out, double *rc_out, const double *hv, int split,
                          const double *val_nd = nullptr, const signed char *nd_code = nullptr, double omega = 0.0, mgs_pack7 *pk = nullptr);
                          // pk: packed copy of the operand the coded + staged blocks stream (val_nd if given, Ahat->val otherwise), or NULL
-// (kernels_aux.hip)
+// (kernels_aux.hip; the BLAS-1 updates and reductions among these: blas1.hip)
 int k_diag_inv(const mgs_csr *A, double *dinv, int *bad_count_host);
 int k_diag_inv_async(const mgs_csr *A, double *dinv, int *bad_dev);   // no host round trip: bad rows are added to *bad_dev
 int k_diag_pos(const mgs_csr *A, unsigned char *dpos);

@@ -7,7 +7,7 @@
 // −α·(z·q)/ρ_prev, resid = √(r·r)/‖b‖ — no fast-math in this build, FP64 division and sqrt are correctly rounded), and the vector passes
 // take α and β from the state block instead of from kernel arguments.  Everything else is the launches mgs_pcg makes: the cycle, the
 // projection, the partial reductions and their folds, the SpMV with its dot epilogue — called with a NULL host pointer, which enqueues and
-// folds without fetching (kernels_aux.hip: fetch_or_leave).  So the bits of every vector agree with mgs_pcg's.
+// folds without fetching (blas1.hip: fetch_or_leave).  So the bits of every vector agree with mgs_pcg's.
 //
 // One iteration is a fixed launch sequence: cycle (or copy) · projection (declared null space) · dots and fold · RHO · direction ·
 // SpMV with p·q and fold · PQ · residual and fold · RES.  A solve that converges or breaks down sets `frozen`; from then on every scalar
@@ -108,19 +108,19 @@ __global__ __launch_bounds__(PTB) void pcgp_dir_vec_kernel(int64_t n, const PcgS
   const bool first = st->first != 0;
   const double a = st->alpha, beta = st->beta;
   const int64_t n2 = n >> 1;
-  kd2 *__restrict__ xv = reinterpret_cast<kd2 *>(x);
-  kd2 *__restrict__ pv = reinterpret_cast<kd2 *>(p);
-  const kd2 *__restrict__ zv = reinterpret_cast<const kd2 *>(z);
+  vd2 *__restrict__ xv = reinterpret_cast<vd2 *>(x);
+  vd2 *__restrict__ pv = reinterpret_cast<vd2 *>(p);
+  const vd2 *__restrict__ zv = reinterpret_cast<const vd2 *>(z);
   const int64_t stride = (int64_t)gridDim.x * PTB;
   for (int64_t i = (int64_t)blockIdx.x * PTB + threadIdx.x; i < n2; i += stride) {
-    const kd2 zi = zv[i];
-    if (first) kst2(pv + i, zi, nts != 0);
+    const vd2 zi = zv[i];
+    if (first) st2(pv + i, zi, nts != 0);
     else {
-      const kd2 pi = pv[i], xi = xv[i]; kd2 xo, po;
+      const vd2 pi = pv[i], xi = xv[i]; vd2 xo, po;
       xo.x = xi.x + a * pi.x; xo.y = xi.y + a * pi.y;
       po.x = zi.x + beta * pi.x; po.y = zi.y + beta * pi.y;
-      kst2(xv + i, xo, nts != 0);
-      kst2(pv + i, po, nts != 0);
+      st2(xv + i, xo, nts != 0);
+      st2(pv + i, po, nts != 0);
     }
   }
   if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
@@ -148,25 +148,18 @@ __global__ __launch_bounds__(PTB) void pcgp_resid_vec_kernel(int64_t n, const Pc
   const double a = st->alpha;
   __shared__ double sh[PTB / 64];
   const int64_t n2 = n >> 1;
-  kd2 *__restrict__ rv = reinterpret_cast<kd2 *>(r);
-  const kd2 *__restrict__ qv = reinterpret_cast<const kd2 *>(q);
+  vd2 *__restrict__ rv = reinterpret_cast<vd2 *>(r);
+  const vd2 *__restrict__ qv = reinterpret_cast<const vd2 *>(q);
   double s0 = 0.0;
   const int64_t stride = (int64_t)gridDim.x * PTB;
   for (int64_t i = (int64_t)blockIdx.x * PTB + threadIdx.x; i < n2; i += stride) {
-    const kd2 ri = rv[i], qi = qv[i]; kd2 o;
+    const vd2 ri = rv[i], qi = qv[i]; vd2 o;
     o.x = ri.x - a * qi.x; o.y = ri.y - a * qi.y;
-    kst2(rv + i, o, nts != 0);
+    st2(rv + i, o, nts != 0);
     s0 += o.x * o.x; s0 += o.y * o.y;
   }
   if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) { const double ri = r[n - 1] - a * q[n - 1]; r[n - 1] = ri; s0 += ri * ri; }
-  for (int off = 32; off > 0; off >>= 1) s0 += __shfl_down(s0, off);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s0;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t0 = 0.0;
-    for (int w = 0; w < PTB / 64; ++w) t0 += sh[w];
-    part[blockIdx.x] = t0; part[gridDim.x + blockIdx.x] = 0.0;
-  }
+  BLAS1_FOLD1(s0, sh, part, true);
 }
 __global__ __launch_bounds__(PTB) void pcgp_resid_kernel(int64_t n, const PcgState *__restrict__ st, double *__restrict__ r, const double *__restrict__ q,
                                                          double *__restrict__ part) {
@@ -177,14 +170,7 @@ __global__ __launch_bounds__(PTB) void pcgp_resid_kernel(int64_t n, const PcgSta
   int64_t i = (int64_t)blockIdx.x * PTB + threadIdx.x;
   const int64_t stride = (int64_t)gridDim.x * PTB;
   for (; i < n; i += stride) { const double ri = r[i] - a * q[i]; r[i] = ri; s0 += ri * ri; }
-  for (int off = 32; off > 0; off >>= 1) s0 += __shfl_down(s0, off);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s0;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t0 = 0.0;
-    for (int w = 0; w < PTB / 64; ++w) t0 += sh[w];
-    part[blockIdx.x] = t0; part[gridDim.x + blockIdx.x] = 0.0;
-  }
+  BLAS1_FOLD1(s0, sh, part, true);
 }
 // Flush: x ← x + a·p when `pending` (mgs_pcg: mgs_axpby(alpha, p, 1, x) = a·p + 1·x, the same bits: 1·x is exact and the sum commutes).
 // Not predicated on `frozen`: it is the frozen solve whose x lags.
@@ -192,13 +178,13 @@ __global__ __launch_bounds__(PTB) void pcgp_flush_vec_kernel(int64_t n, const Pc
   if (!st->pending) return;
   const double a = st->alpha;
   const int64_t n2 = n >> 1;
-  kd2 *__restrict__ xv = reinterpret_cast<kd2 *>(x);
-  const kd2 *__restrict__ pv = reinterpret_cast<const kd2 *>(p);
+  vd2 *__restrict__ xv = reinterpret_cast<vd2 *>(x);
+  const vd2 *__restrict__ pv = reinterpret_cast<const vd2 *>(p);
   const int64_t stride = (int64_t)gridDim.x * PTB;
   for (int64_t i = (int64_t)blockIdx.x * PTB + threadIdx.x; i < n2; i += stride) {
-    const kd2 pi = pv[i], xi = xv[i]; kd2 xo;
+    const vd2 pi = pv[i], xi = xv[i]; vd2 xo;
     xo.x = a * pi.x + xi.x; xo.y = a * pi.y + xi.y;
-    kst2(xv + i, xo, nts != 0);
+    st2(xv + i, xo, nts != 0);
   }
   if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) x[n - 1] = a * p[n - 1] + x[n - 1];
 }

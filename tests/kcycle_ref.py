@@ -1,5 +1,5 @@
 """Host restatement of the K-cycle's two Krylov steps (coarse_solve_inner, multigridsolver_amd/csrc/cycle.hip) and of the reductions and
-element-wise kernels they launch (multigridsolver_amd/csrc/kernels_aux.hip), numpy only.
+element-wise kernels they launch (multigridsolver_amd/csrc/blas1.hip, kernels_aux.hip), numpy only.
 
 Every function takes a `dtype`.  In float64 the sums are formed in the kernels' own association — which lane adds which product in which
 order, the wave tree, the four wave sums, the layout of the partials, the one-workgroup fold — and products and sums round separately, as
