@@ -12,7 +12,7 @@ namespace blas1 {
 constexpr int TB = 256;                  // lanes per workgroup of every pass
 typedef double vd2 __attribute__((ext_vector_type(2)));
 
-// streaming store (the instruction spelled out: see st_stream in kernels_spmv.hip); nothing reads back what it stored
+// streaming store (the instruction spelled out: see st_stream in rowblock.hpp); nothing reads back what it stored
 __device__ __forceinline__ void st2(vd2 *p, vd2 v, bool nt) {
   if (nt) asm volatile("global_store_dwordx4 %0, %1, off nt" : : "v"(p), "v"(v) : "memory");
   else *p = v;

@@ -77,7 +77,7 @@ struct mgs_ctx {
   int opt_group_stray_pct = 6; // ... unless more than this share of a level's aggregates leaves its row-block group
   int opt_post_results = 1;   // inner products reach the host through a mapped buffer + ticket the host polls (no copy engine, no interrupt)
   int opt_rowptr_scan = 1;    // coded row blocks take a row's entry range from its pattern's length (wave prefix sum, one rowptr load per wave) instead of
-                              // two rowptr loads per row: 4 B per row less to stream (kernels_spmv.hip: coded_row_range)
+                              // two rowptr loads per row: 4 B per row less to stream (rowblock.hpp: coded_row_range)
   int opt_pre_nodiag = 1;     // grouped pre pass of an unsharded FP64 level: Â's diagonal entries (ω up to three roundings) are streamed as one byte per row,
                               // their distance from ω, instead of a double (7 B per row less, the same bits; 0: the kernels read val_wd as it is)
   int opt_pack7 = 1;          // fused passes of an unsharded FP64 level: coded + staged row blocks whose values span fewer than 8 binades stream a packed
@@ -104,7 +104,7 @@ static inline void report_launch(const mgs_ctx *ctx, int kernel, int u, int flag
   if (ctx->report) *ctx->report = {kernel, u, flags, capv, capi, bits, tptr};
 }
 
-// pattern code of a CSR-shaped index array (kernels_spmv.hip): one byte per row + a small table per row block
+// pattern code of a CSR-shaped index array (format: rowblock.hpp; built by rowblock_setup.hip): one byte per row + a small table per row block
 struct mgs_rowcode {
   unsigned char *pid = nullptr;  // n: the row's tuple within its row block's table
   int *tptr = nullptr;           // nblocks+1: table slice of each row block in tab (empty: block keeps its index array)
@@ -171,7 +171,7 @@ struct mgs_csr {
 // a row shard as far as the library can tell: more columns than rows AND generated as a shard or living in a context that sums over ranks
 // (a rectangular matrix of a single-process context is just a rectangular matrix)
 static inline bool mgs_csr_is_shard(const mgs_csr *A) { return A->cols > A->rows && (A->halo_cols || A->ctx->allreduce || A->ctx->ncomm); }
-constexpr int MGS_RB = 256;   // rows per row block of the row-block kernels (kernels_spmv.hip) == their threads per workgroup
+constexpr int MGS_RB = 256;   // rows per row block of the row-block kernels (rowblock.hpp and its four units) == their threads per workgroup
 static inline int mgs_row_blocks(const mgs_csr *A) { return (A->rows + MGS_RB - 1) / MGS_RB; }
 
 struct mgs_vec {
@@ -245,7 +245,7 @@ struct mgs_native_tail {
   int n_halo_global = 0;
 };
 
-// Aggregate-complete row-block groups of a level (kernels_spmv.hip, "grouped pre pass"): one workgroup sweeps the 1–2 row
+// Aggregate-complete row-block groups of a level (kernels_fused.hip, "grouped pre pass"): one workgroup sweeps the 1–2 row
 // blocks of a group, keeps their residuals in LDS and restricts every aggregate that lies inside the group — the
 // restriction kernel and the residual vector's trip through HBM disappear.  Aggregates that leave their group
 // ("strays": odd shapes at domain boundaries) are restricted afterwards from the residuals their member rows also store.
@@ -380,7 +380,7 @@ int mgs_fail(mgs_ctx *ctx, int code, const char *fmt, ...);
   } while (0)
 
 // ------------------------------------------------------------------ kernel launchers
-// (kernels_spmv.hip)
+// (kernels_spmv.hip; the fused passes and the grouped pre pass: kernels_fused.hip; plan and pattern code: rowblock_setup.hip)
 enum { MGS_OP_SPMV = 0, MGS_OP_RESIDUAL = 1, MGS_OP_JACOBI = 2, FUSE_PRE = 3, FUSE_POST = 4,
        FUSE_POST_MAPPED = 5 /* FUSE_POST whose column array already holds agg[col] */ };
 int mgs_launch_fused(const mgs_csr *A, int which, const double *wd, const double *bvec, const double *xin, const int *agg,

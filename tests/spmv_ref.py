@@ -1,5 +1,6 @@
 """Host restatement of the standalone operator kernels (mgs_spmv, mgs_residual, mgs_jacobi: mgs_launch_csr_op_range and the kernels of
-multigridsolver_amd/csrc/kernels_spmv.hip), of the plan that picks their arm (mgs_plan_csr), their derived per-row error bar, and the
+multigridsolver_amd/csrc/kernels_spmv.hip and, for the variants 2–4, 6 and 7, kernels_variants.hip), of the plan that picks their arm (mgs_plan_csr,
+rowblock_setup.hip), their derived per-row error bar, and the
 fixtures the CPU and GPU tests of these kernels share.  NumPy, FP64; no device, no oracle.
 
 The operation.  For a CSR matrix A (stored order = ascending columns) and vectors x, b, dinv with  s_i = Σ_k v_ik·x[c_ik]:

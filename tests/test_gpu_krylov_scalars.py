@@ -1,6 +1,6 @@
 """The scalars of the Krylov solvers (mgs_dot / mgs_nrm2, the pair reductions, the update-with-dots passes, the PCG passes, the
 multi-dot and multi-update passes, the SpMV epilogue's inner products) against extended-precision references, at the lengths where
-their launchers change path (multigridsolver_amd/csrc/blas1.hip, kernels_spmv.hip):
+their launchers change path (multigridsolver_amd/csrc/blas1.hip, kernels_spmv.hip: mgs_spmv_dots and the coded kernel's epilogue):
 
     n                 why
     1, 2, 3           below one pair, one pair, pair + tail

@@ -65,7 +65,7 @@ def on_off(ctx, fn):
 
 
 def pre_width(rowptr):
-    """the gather width of the pre pass's walk (kernels_spmv.hip: gather_width)"""
+    """the gather width of the pre pass's walk (rowblock.hpp: gather_width)"""
     ln = np.diff(rowptr); mean = ln.mean()
     return 4 if mean <= 4.5 else (7 if mean <= 7.5 and ln.max() <= 14 else 8)
 

@@ -59,7 +59,7 @@ def build(ctx, mg, c):
 
 
 def expected_u(op):
-    """the gather width the launchers document for an operand (mgs.h / launch_coded)"""
+    """the gather width the launchers document for an operand (mgs.h / launch_coded in kernels_spmv.hip, post_gather_width in rowblock.hpp)"""
     mean, mx = op.mean_len, op.max_len
     if 4.5 < mean <= 5.5 and mx <= 10:
         return 5

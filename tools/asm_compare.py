@@ -1,20 +1,23 @@
 #!/usr/bin/env python3
-"""Device assembly of two builds of one source file, function by function: which functions of the first build have a function with the same
-instructions in the second (whatever its name: a new template parameter changes the mangled name), which do not, and which functions of the
-second are new.  Make the inputs with
-  hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off --cuda-device-only -save-temps=obj -c kernels_spmv.hip -o DIR/x.o
-in each tree and pass the two DIR/*-gfx950.s files.  Compared: everything between a function's label and its end label, comments and blank
+"""Device assembly of two builds, function by function: which functions of the first build have a function with the same instructions in the
+second (whatever its name or its file: a new template parameter or a moved type changes the mangled name, a split moves the function to
+another unit), which do not, and which functions of the second are new.  Either side may be several files — one source file against the
+units it was split into.  Make the inputs with
+  hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off --cuda-device-only -save-temps=obj -c UNIT.hip -o DIR/UNIT.o
+for every unit concerned in each tree (the row-block kernels: kernels_spmv.hip, kernels_variants.hip, kernels_fused.hip, rowblock_setup.hip)
+and pass the DIR/*-gfx950.s files.  Compared: everything between a function's label and its end label, comments and blank
 lines dropped, the function's own name and the numbers of its local labels normalised, the `.amdhsa_kernarg_size` line left out (a trailing
-parameter a form does not read changes nothing else).  usage: asm_compare.py PARENT.s NEW.s"""
+parameter a form does not read changes nothing else).
+usage: asm_compare.py PARENT.s NEW.s   or   asm_compare.py PARENT.s [PARENT.s ...] -- NEW.s [NEW.s ...]"""
 import hashlib
 import re
 import subprocess
 import sys
 
 
-def funcs(path):
+def funcs(paths):
     out, name, body = {}, None, []
-    for line in open(path):
+    for line in (line for path in paths for line in open(path)):
         m = re.match(r'^(_Z\w+):\s*(;.*)?$', line)
         if m and name is None:
             name, body = m.group(1), []
@@ -40,7 +43,9 @@ def demangled(names):
 
 
 def main():
-    a, b = funcs(sys.argv[1]), funcs(sys.argv[2])
+    args = sys.argv[1:]
+    cut = args.index('--') if '--' in args else 1
+    a, b = funcs(args[:cut]), funcs([p for p in args[cut:] if p != '--'])
     twins = {}
     for n, body in b.items():
         twins.setdefault(digest(n, body), []).append(n)
