@@ -262,7 +262,7 @@ int mgs_csr_from_diag(mgs_ctx *ctx, const mgs_vec *d, mgs_csr **out);
  * both, as in mgs_csr_from_device.  rows_dev == NULL: every row in order, nr is ignored and S has A's rows.  A given row list may be
  * in any order and may repeat rows.  cols_dev == NULL: every column, nc is ignored and S has A's columns.  A given column list must be
  * strictly ascending: that keeps every row of S ascending without a sort and makes the list free of duplicates; a general column
- * permutation is out of scope.  No kernel uses a list entry as an address before it has compared it with its bounds; 64-bit entries
+ * permutation is mgs_csr_permute.  No kernel uses a list entry as an address before it has compared it with its bounds; 64-bit entries
  * are compared as 64-bit values before they are narrowed.  Value bits are copied unchanged: -0.0 stays -0.0 and a NaN keeps its payload.
  * The pattern is structural: stored zeros stay entries (the pattern is what mgs_hier_refresh keys on).  S is an ordinary matrix,
  * indistinguishable from an uploaded one (launch plan, mgs_csr_optimize, hierarchies, the Krylov solvers, a factor of mgs_csr_spgemm or
@@ -300,6 +300,77 @@ int mgs_csr_extract_numeric(const mgs_csr *A, mgs_csr *S);
 int mgs_csr_extract_info(const mgs_csr *S, int64_t out[4]);
 int mgs_vec_gather(const mgs_vec *x, const void *idx_dev, int64_t n, int index_bits, mgs_vec *y, int64_t *bad);
 int mgs_vec_scatter(const mgs_vec *y, const void *idx_dev, int64_t n, int index_bits, mgs_vec *x, int64_t *bad);
+/* ---- reordering a device matrix, assembling one from a grid of blocks ----
+ * Nearest reference line: none — the reference reads whole operators from files (MatrixIO.cpp:12-37); a renumbering of the unknowns
+ * (interleaved fields to field-major and back, a bandwidth-reducing or plane-major order) and the assembly of a coupled operator
+ * [[A, Bᵀ], [B, -C]] from its fields are done by its callers before that.
+ * mgs_csr_permute — C[i, j] = A[rperm[i], cperm[j]]: C has A's shape, row k of C is row rperm[k] of A, column cperm[q] of A is renumbered
+ * to q (scipy's A[rperm][:, cperm], the convention of mgs_csr_extract).  rperm_dev holds A->rows entries and cperm_dev A->cols entries,
+ * arrays in device memory (make them visible first) of index_bits = 32 or 64 bits per entry, one width for both.  rperm_dev == NULL or
+ * cperm_dev == NULL: the identity on that side; both NULL give a copy.  A symmetric reordering P·A·Pᵀ passes the same list twice;
+ * rectangular matrices are allowed.  With the vectors moved by mgs_vec_gather: C·gather(x, cperm) = gather(A·x, rperm).
+ * Each list must be a bijection, and that is checked on the device before any entry is used as an address: 64-bit entries are compared
+ * as 64-bit values before they are narrowed, a value outside [0, n) is refused and so is a value that repeats an earlier entry.  The
+ * message names the list, the lowest offending position and its value (a range violation and a repeat are both positions: the lowest
+ * one is named, whichever kind it is; a violation of the row list before any of the column list), so it is deterministic.
+ * Row i of C holds the entries of A's row rperm[i] in ascending order of their new column.  The new columns of one row are distinct,
+ * so an entry's place is its rank, the number of entries of its row with a smaller new column: every place is computed from the row
+ * alone, without a sort network, without staging that would limit the length of a row and without atomics on places or values — two
+ * identical calls give identical arrays.  Without a column list the rows are copied as they are, entry-parallel (an output entry finds
+ * its row by bisection); with one, a source row of at most 64 entries is ranked by one lane and a longer one by one wave that holds 64
+ * entries at a time and counts ranks against the row chunk by chunk.  Value bits are copied unchanged: -0.0 stays -0.0 and a NaN keeps
+ * its payload.  The pattern is structural: stored zeros stay entries.  C is an ordinary matrix, indistinguishable from an uploaded one
+ * (launch plan, mgs_csr_optimize, hierarchies, the Krylov solvers, mgs_csr_update_values*, a factor of mgs_csr_spgemm, mgs_csr_add or
+ * mgs_csr_bmat); it carries no null-space declaration and no origin.  The work is enqueued on the context's stream and the call
+ * synchronises before it returns, as mgs_csr_extract does.
+ * MGS_ERR_INVALID, with a message: a NULL A or C; index_bits neither 32 nor 64; a list that is no bijection (above); a row shard as A
+ * (see mgs_csr_spgemm).  On failure nothing is written to *C and everything the call allocated is released.
+ * keep_map != 0: C keeps the position in A's arrays of every entry (4 B per entry of C, freed by mgs_csr_destroy) and records A's rows,
+ * columns and number of entries.
+ * mgs_csr_permute_numeric — C.val[k] = A.val[src[k]] through the kept map, for an A whose values changed and whose pattern did not
+ * (mgs_csr_update_values*, *_numeric): one entry-parallel launch on the context's stream, no host wait, no allocation, no scan; the bits
+ * are those of a fresh mgs_csr_permute.  C's arrays do not move, so hierarchies built on C and their cached graphs stay valid (follow
+ * with mgs_hier_refresh).  MGS_ERR_STATE: C keeps no map.  MGS_ERR_INVALID: a NULL handle; different contexts; an A whose rows, columns
+ * or number of entries differ from those recorded; a value-carrying pattern code on C (option "valcode").
+ * mgs_csr_permute_info — diagnostics: out[0] rows ranked by one lane, out[1] rows ranked by one wave, out[2] longest row of C, out[3]
+ * bytes of the kept map.  All four are 0 for a matrix that mgs_csr_permute did not build; out[0] and out[1] are 0 for cperm_dev == NULL
+ * (nothing is ranked).  MGS_ERR_INVALID: NULL argument.
+ * mgs_csr_bmat — C assembled from a grid of br × bc blocks (scipy.sparse.bmat): blocks is a host array of br·bc handles, row-major; NULL
+ * stands for a zero block and the same handle may appear in several places.  br == 1 is an hstack, bc == 1 a vstack, NULL off the
+ * diagonal a block-diagonal matrix.  All blocks of block row I share their row count and all blocks of block column J their column
+ * count.  row_sizes (br ints) and col_sizes (bc ints) are host arrays, either may be NULL; a given size must agree with the blocks, and
+ * a block row or column made only of NULLs needs its size from the array.  Row roff_I + i of C is the concatenation over J of row i of
+ * block (I, J) with coff_J added to the columns, so rows come out ascending without a sort; an all-NULL block row gives empty rows.
+ * The block descriptors (rowptr, col, val, column offset) live in a table in device memory that C keeps.  One lane per output row sums
+ * at most bc row lengths, a 64-bit total beside them; the library's scan; then an entry-parallel fill with coalesced stores in which
+ * an output entry finds its row by bisection in C's rowptr, its block from the row's per-block lengths and its source position from
+ * the block's rowptr.  No limit on the length of a row, no atomics on places or values: two identical calls give identical arrays.
+ * Value bits are copied unchanged (-0.0, NaN payloads); stored zeros stay entries.  C is an ordinary matrix without null-space
+ * declaration or origin; the call synchronises before it returns.
+ * MGS_ERR_INVALID, with a message that names the block position (I, J) where there is one: a NULL ctx, blocks or C; br or bc below 1
+ * or br·bc above MGS_BMAT_MAX_BLOCKS; a block of another context; sizes that disagree; a block row or column without any size; a row
+ * shard as a block; a total of 2^31 - 1 rows, columns or entries or more.  On failure nothing is written to *C and everything the call
+ * allocated is released.
+ * mgs_csr_bmat_numeric — the values of C again, in place, from the current values of the blocks: the fill pass's own place computation
+ * writing values only (no map is kept), so the bits are those of a fresh mgs_csr_bmat; no allocation; C's arrays do not move: follow
+ * with mgs_hier_refresh.  blocks holds as many handles as C's grid (out[1]·out[2] of mgs_csr_bmat_info): the call takes no dimensions.
+ * ONE LAUNCH WITH NO HOST WAIT ONLY FOR THE RECORDED HANDLES: when blocks are the handles C was assembled from (their arrays do not
+ * move under mgs_csr_update_values*), the table in device memory is left alone and the call is enqueued.  Other handles of the same
+ * shapes and entry counts are accepted, but the call then waits for the stream, rewrites the table with a blocking copy and
+ * records the new handles — it is not enqueue-only in that case.  Precondition: the blocks have the patterns they had.  C records per block position whether it was NULL, its shape
+ * and its number of entries; MGS_ERR_INVALID, naming the position: blocks that differ in any of these; also a NULL argument, a C that
+ * mgs_csr_bmat did not build, a block of another context, a value-carrying pattern code on C (option "valcode").
+ * mgs_csr_bmat_info — diagnostics: out[0] blocks that are not NULL, out[1] br, out[2] bc, out[3] longest row of C.  All four are 0 for
+ * a matrix that mgs_csr_bmat did not build.  MGS_ERR_INVALID: NULL argument. */
+#define MGS_BMAT_MAX_BLOCKS 256   /* most block positions (br·bc) one mgs_csr_bmat call takes */
+int mgs_csr_permute(const mgs_csr *A, const void *rperm_dev, const void *cperm_dev,
+                    int index_bits, int keep_map, mgs_csr **C);
+int mgs_csr_permute_numeric(const mgs_csr *A, mgs_csr *C);
+int mgs_csr_permute_info(const mgs_csr *C, int64_t out[4]);
+int mgs_csr_bmat(mgs_ctx *ctx, int br, int bc, const mgs_csr *const *blocks,
+                 const int *row_sizes, const int *col_sizes, mgs_csr **C);
+int mgs_csr_bmat_numeric(mgs_csr *C, const mgs_csr *const *blocks);
+int mgs_csr_bmat_info(const mgs_csr *C, int64_t out[4]);
 
 /* -------------------------------------------------------------------- device vectors */
 /* Eigen::VectorXd on the device (bicg.cpp:153-162).                                    */

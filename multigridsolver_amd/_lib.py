@@ -102,6 +102,12 @@ PROTOTYPES = {
     "mgs_csr_extract": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "mgs_csr_extract_numeric": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mgs_csr_extract_info": (C.c_int, [C.c_void_p, c_i64_p]),
+    "mgs_csr_permute": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "mgs_csr_permute_numeric": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mgs_csr_permute_info": (C.c_int, [C.c_void_p, c_i64_p]),
+    "mgs_csr_bmat": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_void_p)]),
+    "mgs_csr_bmat_numeric": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "mgs_csr_bmat_info": (C.c_int, [C.c_void_p, c_i64_p]),
     "mgs_vec_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, c_i64_p]),
     "mgs_vec_scatter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, c_i64_p]),
     "mgs_vec_create": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]),

@@ -409,6 +409,95 @@ class Csr:
         out = (C.c_int64 * 4)(); check(lib().mgs_csr_extract_info(self.h, out), self.ctx.h)
         return dict(zip(["lane_rows", "wave_rows", "max_row_len", "map_bytes"], [int(v) for v in out]))
 
+    def permute(self, rows=None, cols=None, keep_map=False):
+        """C = self[rows][:, cols] for two permutations on the device (mgs_csr_permute): C[i, j] = self[rows[i], cols[j]].  Index lists
+        as in extract (torch tensors or objects with __cuda_array_interface__, int32 or int64, one width for both; make them visible
+        first), of exactly shape[0] and shape[1] entries; None: the identity on that side.  Each list must be a bijection (checked on
+        the device).  A symmetric reordering passes the same list twice.  Value bits are copied unchanged.  keep_map=True keeps what
+        permute_update needs."""
+        ptr, bits = [None, None], [0, 0]
+        for k, (name, a) in enumerate((("rows", rows), ("cols", cols))):
+            if a is not None:
+                p, n, bits[k] = _dev_array(self.ctx, a, name, True)
+                if n != self.shape[k]:
+                    raise ValueError(f"permute: {name} holds {n} entries, the matrix has {self.shape[k]} {name}")
+                ptr[k] = C.c_void_p(p or self.device_ptrs()[0])      # an empty list has no address of its own: any device address, never read
+        if bits[0] and bits[1] and bits[0] != bits[1]:
+            raise TypeError(f"rows holds {bits[0]}-bit indices, cols {bits[1]}-bit ones")
+        h = C.c_void_p()
+        check(lib().mgs_csr_permute(self.h, ptr[0], ptr[1], bits[0] or bits[1] or 32, int(bool(keep_map)), C.byref(h)), self.ctx.h)
+        return Csr(self.ctx, h)
+
+    def permute_update(self, A):
+        """this matrix = A.permute(..., keep_map=True) built earlier: its values again, in place, from the current values of A with its
+        pattern unchanged (mgs_csr_permute_numeric; enqueued, no host wait); returns self.  Follow with Hierarchy.refresh()."""
+        check(lib().mgs_csr_permute_numeric(A.h, self.h), A.ctx.h); return self      # the call reports on A's context
+
+    def permute_info(self):
+        out = (C.c_int64 * 4)(); check(lib().mgs_csr_permute_info(self.h, out), self.ctx.h)
+        return dict(zip(["lane_rows", "wave_rows", "max_row_len", "map_bytes"], [int(v) for v in out]))
+
+    @staticmethod
+    def _block_grid(blocks):
+        grid = [list(row) for row in blocks]
+        if not grid or not grid[0] or any(len(row) != len(grid[0]) for row in grid):
+            raise ValueError("bmat: a non-empty rectangular list of lists of blocks expected")
+        for row in grid:
+            for b in row:
+                if b is not None and not isinstance(b, Csr):
+                    raise TypeError(f"bmat: a Csr or None expected, got {type(b).__name__}")
+        flat = [b for row in grid for b in row]
+        return len(grid), len(grid[0]), flat, (C.c_void_p * len(flat))(*[b.h if b is not None else None for b in flat])
+
+    @staticmethod
+    def bmat(ctx, blocks, row_sizes=None, col_sizes=None):
+        """the matrix assembled from a grid of blocks on the device (mgs_csr_bmat; scipy.sparse.bmat): blocks is a list of lists of Csr
+        or None (a zero block); the same Csr may appear in several places.  row_sizes / col_sizes: the sizes of the block rows /
+        columns, needed only where a whole block row or column is None."""
+        br, bc, _, arr = Csr._block_grid(blocks)
+        sizes = []
+        for name, given, count in (("row_sizes", row_sizes, br), ("col_sizes", col_sizes, bc)):
+            if given is None:
+                sizes.append(None)
+            else:
+                if len(given) != count:
+                    raise ValueError(f"bmat: {name} holds {len(given)} sizes, the grid has {count}")
+                sizes.append((C.c_int * count)(*[int(v) for v in given]))
+        h = C.c_void_p()
+        check(lib().mgs_csr_bmat(ctx.h, br, bc, arr, sizes[0], sizes[1], C.byref(h)), ctx.h)
+        return Csr(ctx, h)
+
+    @staticmethod
+    def hstack(ctx, blocks):
+        """[B0 B1 …] (mgs_csr_bmat with one block row)"""
+        return Csr.bmat(ctx, [list(blocks)])
+
+    @staticmethod
+    def vstack(ctx, blocks):
+        """[B0; B1; …] (mgs_csr_bmat with one block column)"""
+        return Csr.bmat(ctx, [[b] for b in blocks])
+
+    @staticmethod
+    def block_diag(ctx, blocks):
+        """diag(B0, B1, …) (mgs_csr_bmat with None off the diagonal; at most 16 blocks: the grid holds 256 positions)"""
+        blocks = list(blocks)
+        return Csr.bmat(ctx, [[b if i == j else None for j in range(len(blocks))] for i, b in enumerate(blocks)])
+
+    def bmat_update(self, blocks):
+        """this matrix = Csr.bmat(ctx, blocks) built earlier: its values again, in place, from the current values of the blocks with
+        their patterns unchanged (mgs_csr_bmat_numeric; one launch); returns self.  Follow with Hierarchy.refresh()."""
+        br, bc, _, arr = Csr._block_grid(blocks)
+        info = self.bmat_info()      # the C call takes no grid dimensions: it reads as many handles as this matrix recorded
+        if info["blocks"] == 0 and info["block_rows"] == 0:
+            check(lib().mgs_csr_bmat_numeric(self.h, arr), self.ctx.h)      # not built by bmat: the library's own refusal, which reads no handle
+        if (br, bc) != (info["block_rows"], info["block_cols"]):
+            raise ValueError(f"bmat_update: a grid of {br} x {bc} blocks given, this matrix was assembled from {info['block_rows']} x {info['block_cols']}")
+        check(lib().mgs_csr_bmat_numeric(self.h, arr), self.ctx.h); return self
+
+    def bmat_info(self):
+        out = (C.c_int64 * 4)(); check(lib().mgs_csr_bmat_info(self.h, out), self.ctx.h)
+        return dict(zip(["blocks", "block_rows", "block_cols", "max_row_len"], [int(v) for v in out]))
+
     def spmv(self, x, y=None):
         y = y or Vec(self.ctx, self.shape[0])
         check(lib().mgs_spmv(self.h, x.h, y.h), self.ctx.h); return y

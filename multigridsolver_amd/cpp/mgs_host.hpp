@@ -136,6 +136,11 @@ class DeviceMatrix {
     M.a_ = std::shared_ptr<mgs_csr>(p, [](mgs_csr *q) { mgs_csr_destroy(q); });
     return M;
   }
+  static std::vector<const mgs_csr *> handles(int br, int bc, const DeviceMatrix *const *blocks) {   // a grid of blocks as the C-ABI takes it
+    std::vector<const mgs_csr *> h((size_t)(br > 0 ? br : 0) * (size_t)(bc > 0 ? bc : 0), nullptr);
+    for (size_t q = 0; q < h.size(); ++q) h[q] = blocks && blocks[q] ? blocks[q]->a_.get() : nullptr;
+    return h;
+  }
  public:
   DeviceMatrix() {}
   DeviceMatrix(const SMatrix &A) : rows_(A.rows()), cols_(A.cols()) {
@@ -229,6 +234,38 @@ class DeviceMatrix {
     return adopt(p, rows_dev ? (int)nr : rows_, cols_dev ? (int)nc : cols_);
   }
   void extractUpdate(const DeviceMatrix &A) { check(mgs_csr_extract_numeric(A.a_.get(), a_.get()), context()); }
+  // C = (*this)(rperm, cperm) for two permutations in device memory (mgs.h: mgs_csr_permute; no reference counterpart): C(i, j) =
+  // (*this)(rperm[i], cperm[j]); rows() and cols() entries of index_bits 32 or 64 for both; a NULL list is the identity.  Each list must
+  // be a bijection (checked on the device); a symmetric reordering passes the same list twice.  keepMap keeps what permuteUpdate needs.
+  // permuteUpdate: this matrix is A.permute(..., keepMap = true) built earlier — its values again, in place, from the current values of
+  // A with its pattern unchanged (mgs_csr_permute_numeric; enqueued, no host wait).
+  DeviceMatrix permute(const void *rperm_dev, const void *cperm_dev, int index_bits = 32, bool keepMap = false) const {
+    mgs_csr *p = nullptr;
+    check(mgs_csr_permute(a_.get(), rperm_dev, cperm_dev, index_bits, keepMap ? 1 : 0, &p), context());
+    return adopt(p, rows_, cols_);
+  }
+  void permuteUpdate(const DeviceMatrix &A) { check(mgs_csr_permute_numeric(A.a_.get(), a_.get()), context()); }
+  // The matrix assembled from a br × bc grid of blocks, row-major (mgs.h: mgs_csr_bmat; scipy.sparse.bmat): a NULL pointer is a zero
+  // block, the same matrix may appear in several places; row_sizes / col_sizes (br / bc ints, or NULL) are needed only where a whole
+  // block row or column is NULL.  bmatUpdate: this matrix is bmat(...) built earlier — its values again, in place, from the current
+  // values of the blocks with their patterns unchanged (mgs_csr_bmat_numeric; one launch).
+  static DeviceMatrix bmat(int br, int bc, const DeviceMatrix *const *blocks, const int *row_sizes = nullptr, const int *col_sizes = nullptr) {
+    std::vector<const mgs_csr *> h = handles(br, bc, blocks);
+    mgs_csr *p = nullptr;
+    check(mgs_csr_bmat(context(), br, bc, h.data(), row_sizes, col_sizes, &p), context());
+    int r = 0, c = 0;
+    check(mgs_csr_shape(p, &r, &c, nullptr), context());
+    return adopt(p, r, c);
+  }
+  void bmatUpdate(int br, int bc, const DeviceMatrix *const *blocks) {
+    int64_t info[4] = {0, 0, 0, 0};      // the C call takes no grid dimensions: it reads as many handles as this matrix recorded
+    check(mgs_csr_bmat_info(a_.get(), info), context());
+    if (info[1] != br || info[2] != bc)
+      throw Error(MGS_ERR_INVALID, "DeviceMatrix::bmatUpdate: a grid of " + std::to_string(br) + " x " + std::to_string(bc) + " blocks given, this matrix was assembled from " +
+                                       std::to_string((long long)info[1]) + " x " + std::to_string((long long)info[2]));
+    std::vector<const mgs_csr *> h = handles(br, bc, blocks);
+    check(mgs_csr_bmat_numeric(a_.get(), h.data()), context());
+  }
   Vector operator*(const Vector &x) const {            // bicg.cpp:57,82,107,117
     Vector y(rows_); check(mgs_spmv(a_.get(), x.handle(), y.out()), context()); return y;
   }

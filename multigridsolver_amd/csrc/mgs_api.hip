@@ -367,6 +367,7 @@ int mgs_csr_destroy(mgs_csr *A) {
   mgs_free_spgemm(A->spg);
   mgs_free_add(A->addp);
   mgs_free_extract(A->extp);
+  mgs_free_reorder(A->reop);
   delete A;
   return MGS_OK;
 }
@@ -461,6 +462,17 @@ int mgs_csr_extract(const mgs_csr *A, const void *rows_dev, int64_t nr, const vo
 }
 int mgs_csr_extract_numeric(const mgs_csr *A, mgs_csr *S) { return k_csr_extract_numeric(A, S); }
 int mgs_csr_extract_info(const mgs_csr *S, int64_t out[4]) { return k_csr_extract_info(S, out); }
+// permutations of a device matrix and assembly from a grid of blocks (reorder.hip)
+int mgs_csr_permute(const mgs_csr *A, const void *rperm_dev, const void *cperm_dev, int index_bits, int keep_map, mgs_csr **C) {
+  return k_csr_permute(A, rperm_dev, cperm_dev, index_bits, keep_map, C);
+}
+int mgs_csr_permute_numeric(const mgs_csr *A, mgs_csr *C) { return k_csr_permute_numeric(A, C); }
+int mgs_csr_permute_info(const mgs_csr *C, int64_t out[4]) { return k_csr_permute_info(C, out); }
+int mgs_csr_bmat(mgs_ctx *ctx, int br, int bc, const mgs_csr *const *blocks, const int *row_sizes, const int *col_sizes, mgs_csr **C) {
+  return k_csr_bmat(ctx, br, bc, blocks, row_sizes, col_sizes, C);
+}
+int mgs_csr_bmat_numeric(mgs_csr *C, const mgs_csr *const *blocks) { return k_csr_bmat_numeric(C, blocks); }
+int mgs_csr_bmat_info(const mgs_csr *C, int64_t out[4]) { return k_csr_bmat_info(C, out); }
 int mgs_vec_gather(const mgs_vec *x, const void *idx_dev, int64_t n, int index_bits, mgs_vec *y, int64_t *bad) { return k_vec_gather(x, idx_dev, n, index_bits, y, bad); }
 int mgs_vec_scatter(const mgs_vec *y, const void *idx_dev, int64_t n, int index_bits, mgs_vec *x, int64_t *bad) { return k_vec_scatter(y, idx_dev, n, index_bits, x, bad); }
 

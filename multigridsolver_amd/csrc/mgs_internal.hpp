@@ -166,6 +166,7 @@ struct mgs_csr {
   struct mgs_spgemm_plan *spg = nullptr;   // matrices built by mgs_csr_spgemm (spgemm.hip; owned): the row bins its numeric pass launches over
   struct mgs_add_plan *addp = nullptr;     // matrices built by mgs_csr_add (csr_algebra.hip; owned): the row bins mgs_csr_add_numeric launches over
   struct mgs_extract_plan *extp = nullptr; // matrices built by mgs_csr_extract (extract.hip; owned): the bins it counted and, with keep_map, the source position of every entry
+  struct mgs_reorder_plan *reop = nullptr; // matrices built by mgs_csr_permute or mgs_csr_bmat (reorder.hip; owned): the kept source map, or the block table and what it recorded of the blocks
   bool halo_cols = false;   // generated as a row shard (mgs_csr_poisson3d on a plane range): the columns beyond the rows are halo columns
 };
 // a row shard as far as the library can tell: more columns than rows AND generated as a shard or living in a context that sums over ranks
@@ -510,6 +511,14 @@ int k_csr_extract_info(const mgs_csr *S, int64_t out[4]);
 int k_vec_gather(const mgs_vec *x, const void *idx_dev, int64_t n, int index_bits, mgs_vec *y, int64_t *bad);
 int k_vec_scatter(const mgs_vec *y, const void *idx_dev, int64_t n, int index_bits, mgs_vec *x, int64_t *bad);
 void mgs_free_extract(struct mgs_extract_plan *p);
+// (reorder.hip) C[i, j] = A[rperm[i], cperm[j]] from permutations in device memory, its values again through the kept map; C assembled from a grid of blocks, its values again
+int k_csr_permute(const mgs_csr *A, const void *rperm_dev, const void *cperm_dev, int index_bits, int keep_map, mgs_csr **out);
+int k_csr_permute_numeric(const mgs_csr *A, mgs_csr *C);
+int k_csr_permute_info(const mgs_csr *C, int64_t out[4]);
+int k_csr_bmat(mgs_ctx *ctx, int br, int bc, const mgs_csr *const *blocks, const int *row_sizes, const int *col_sizes, mgs_csr **out);
+int k_csr_bmat_numeric(mgs_csr *C, const mgs_csr *const *blocks);
+int k_csr_bmat_info(const mgs_csr *C, int64_t out[4]);
+void mgs_free_reorder(struct mgs_reorder_plan *p);
 
 // helpers (mgs_api.hip)
 int mgs_csr_alloc(mgs_ctx *ctx, int rows, int cols, int64_t nnz, mgs_csr **out);
