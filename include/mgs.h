@@ -613,6 +613,33 @@ int mgs_fgcr(const mgs_csr *A, mgs_vec *x, const mgs_vec *b, mgs_hier *h, int re
 int mgs_pcg(const mgs_csr *A, mgs_vec *x, const mgs_vec *b, mgs_hier *h, int flexible,
             int *max_iter, double *tol, int *status);
 
+/* Preconditioned MINRES for symmetric A that may be indefinite (saddle-point systems [[A, Bᵀ], [B, −C]]: Stokes, mixed Darcy, KKT) with a
+ * symmetric positive definite preconditioner.  Nearest reference line: src/CPU_Matlab/solve.m:28-33, whose driver chooses between pcg and
+ * bicgstab; the reference has no MINRES.  Same in/out convention as mgs_pcg: x is the initial guess, *max_iter returns the iterations done
+ * (for status 2 and 3 the iteration that stopped, 0 at the start), *tol the TRUE relative residual ‖b − A·x‖/‖b‖ whatever the status (one
+ * more SpMV where none was just made).  h may be NULL (identity preconditioner).
+ * The method is the form of Elman, Silvester and Wathen, Alg. 4.1 (Paige-Saunders); v and z̃ = M·v are stored unnormalised:
+ *   start:  normb = ‖b‖ (1 if 0); v = b − A·x; resid = ‖v‖/normb, status 0 with 0 iterations if resid <= tol; z̃ = M·v; g2 = z̃·v, status 2
+ *           unless g2 > 0; γ = √g2, γ_prev = 1, η = γ, κ = resid·normb/γ, s0 = s1 = 0, c0 = c1 = 1, w_prev = w = v_prev = 0.
+ *   step j: q = A·z̃; δ = (q·z̃)/γ²; v_new = (1/γ)·q − (δ/γ)·v − (γ/γ_prev)·v_prev; z̃_new = M·v_new; gn2 = z̃_new·v_new, status 2 unless
+ *           gn2 >= 0; γn = √gn2; a0 = c1·δ − c0·s1·γ, a1 = √(a0² + gn2), a2 = s1·δ + c0·c1·γ, a3 = s0·γ; status 3 if a1 == 0 (x not
+ *           updated); cn = a0/a1, sn = γn/a1; w_new = ((1/γ)·z̃ − a3·w_prev − a2·w)/a1; x ← x + (cn·η)·w_new; η ← −sn·η; rotate.
+ *   stop:   |η| is ‖r‖ in the M⁻¹ norm, not the 2-norm.  est = κ·|η|/normb after every step; when est < tol or γn == 0 the true residual is
+ *           formed: below tol → status 0; else γn == 0 → status 3; else κ ← (true·normb)/|η| and the recurrence goes on undisturbed (no
+ *           restart, no tuned constant).
+ * *status: 0 converged (decided on the true residual only) / 1 max_iter / 2 z̃·v negative or not a number (the preconditioner is not
+ * positive definite) / 3 the Krylov space is exhausted above the tolerance (a singular, inconsistent system).
+ * Seven work vectors from the context's pool (mgs_bicgstab: eight, mgs_fgcr(10): 21), one cycle and one SpMV per iteration (mgs_bicgstab: two
+ * of each), two host looks, 96 B per row of vector passes beside them (mgs_pcg: 80).  The cycle alternates between two (v, z̃) pairs and
+ * replays from two cached graphs.  A's symmetry is the caller's responsibility, as in mgs_pcg.
+ * MGS_ERR_INVALID, with a message: a NULL out parameter; vectors shorter than A's rows; x aliasing b; a hierarchy that is not a fixed
+ * symmetric operator (nu1 != nu2, or a K-cycle set through mgs_hier_set_kcycle / mgs_hier_set_kcycle_entry; the additive form, a correction
+ * scale and FP32 operands are allowed, as for mgs_pcg with flexible = 0); a row shard (the criteria of mgs_pcg_plan_create); an A or a
+ * hierarchy with a declared null space (the constant vector is not the null space of a saddle system).
+ * Option "minres_nt" (default 0): the update pass stores its direction vector with the `nt` hint on operators nt_store covers (A/B knob). */
+int mgs_minres(const mgs_csr *A, mgs_vec *x, const mgs_vec *b, mgs_hier *h,
+               int *max_iter, double *tol, int *status);
+
 /* ------------------------------------- PCG with device-resident scalars: enqueue-only solves, one host look per iteration */
 /* Nearest reference line: src/CPU_Matlab/solve.m:28-31 (pcg); the reference has no counterpart for the asynchronous form.  mgs_pcg computes ρ, α, β
  * and the stopping test on the host: three host looks per iteration, each one draining the queue behind it, and the call cannot return before
@@ -886,7 +913,9 @@ int mgs_ctx_set_allreduce(mgs_ctx *ctx, mgs_allreduce_fn fn, void *user);
 /* ------------------------------------------------------------------ instrumentation  */
 /* Time `reps` back-to-back launches of one hot-path kernel with hipEvents on the
  * context's stream (what bench.py's roofline.achieved uses).  op: 0 spmv, 1 residual,
- * 2 jacobi.  Returns mean milliseconds per launch in *ms.                              */
+ * 2 jacobi, 3 the update pass of mgs_minres over A's rows (x = z̃, b = w, dinv = w_prev,
+ * out = the solution; fixed coefficients; the matrix itself is not read).  Returns mean
+ * milliseconds per launch in *ms.                                                      */
 int mgs_time_kernel(const mgs_csr *A, int op, const mgs_vec *x, const mgs_vec *b,
                     const mgs_vec *dinv, mgs_vec *out, int reps, double *ms);
 /* Time `reps` V-cycles with hipEvents on the context's stream.                        */
@@ -1056,7 +1085,7 @@ int mgs_hier_graph_info(const mgs_hier *h, int64_t out[4]);
  * hold exactly one diagonal entry streams Â's diagonal entry — ω up to three roundings for every row — as one byte, its distance from ω in units of the last place: 7 B per row less, +8 B of HBM per
  * off-diagonal entry and 1 B per row; default 1, the same bits as with 0), "pack7" (the fused passes of an unsharded FP64 level stream a packed copy of their operands' values, 7 bytes per
  * entry — sign, three exponent bits against a base exponent per row block, 52 mantissa bits — in the coded row blocks whose values span fewer than 8 binades; +7 B of HBM per entry; the same
- * bits as with 0; see mgs_hier_pack_info), "diag_from_values", "fuse_dots", "lds_pad", "blkptr".
+ * bits as with 0; see mgs_hier_pack_info), "minres_nt" (see mgs_minres; default 0), "diag_from_values", "fuse_dots", "lds_pad", "blkptr".
  * Unknown key: MGS_ERR_INVALID. */
 int mgs_ctx_set_option(mgs_ctx *ctx, const char *key, int value);
 

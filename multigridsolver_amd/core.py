@@ -8,6 +8,7 @@ import numpy as np
 from ._lib import ALLREDUCE_FN, HALO_FN, HALO_FUSED_FN, MgsError, check, lib
 
 OP_SPMV, OP_RESIDUAL, OP_JACOBI = 0, 1, 2
+OP_MINRES_UPDATE = 3      # Csr.time_kernel only: the update pass of mgs_minres (x = z̃, b = w, dinv = w_prev, out = the solution)
 _check = check      # for methods whose own argument is called `check`
 
 
@@ -1055,4 +1056,14 @@ def pcg(A, x, b, hier=None, max_iter=10000, tol=1e-6, flexible=False):
     preconditioner that is not a fixed symmetric operator (V(ν1 ≠ ν2), K-cycle)"""
     mi, t, st = C.c_int(max_iter), C.c_double(tol), C.c_int(-1)
     check(lib().mgs_pcg(A.h, x.h, b.h, hier.h if hier else None, int(bool(flexible)), C.byref(mi), C.byref(t), C.byref(st)), A.ctx.h)
+    return st.value, mi.value, t.value
+
+
+def minres(A, x, b, hier=None, max_iter=10000, tol=1e-6):
+    """preconditioned MINRES for symmetric A that may be indefinite (saddle-point systems), hier a symmetric positive definite preconditioner:
+    V(ν, ν), no K-cycle (reference src/CPU_Matlab/solve.m:28-33 chooses between pcg and bicgstab; it has no MINRES) → (status, iterations, resid);
+    resid is the true relative residual whatever the status; status 0 converged on the true residual / 1 max_iter / 2 z̃·v negative or not a
+    number (preconditioner not positive definite) / 3 Krylov space exhausted above the tolerance (singular, inconsistent system)"""
+    mi, t, st = C.c_int(max_iter), C.c_double(tol), C.c_int(-1)
+    check(lib().mgs_minres(A.h, x.h, b.h, hier.h if hier else None, C.byref(mi), C.byref(t), C.byref(st)), A.ctx.h)
     return st.value, mi.value, t.value

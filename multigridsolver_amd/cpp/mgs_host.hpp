@@ -429,6 +429,64 @@ inline int CGiml(const SMatrix &, Vector &x, const Vector &b, const MultiGridPre
   return CGiml(M.matrix(), x, b, M, max_iter, tol);
 }
 
+// Preconditioned MINRES for symmetric A that may be indefinite (saddle-point systems), in the calling shape of BiCGSTABiml.  The reference
+// has no MINRES: its Matlab driver, src/CPU_Matlab/solve.m:28-33, chooses between pcg and bicgstab.  Status: 0 ok (confirmed on the true
+// residual b − A·x) / 1 max_iter / 2 z̃·v negative or not a number (M is not positive definite) / 3 Krylov space exhausted above the
+// tolerance; max_iter is written back, and tol with the TRUE relative residual whatever the status.  Generic form (mgs.h: mgs_minres states
+// the recurrence): any Matrix with operator*(Vec), any Preconditioner with solve(Vec) that is a fixed symmetric positive definite operator.
+template <class Matrix, class Vec, class Preconditioner, class Real>
+int MINRESiml(const Matrix &A, Vec &x, const Vec &b, const Preconditioner &M, int &max_iter, Real &tol) {
+  Real normb = norm(b);
+  if (normb == 0.0) normb = 1;
+  Vec v = b - A * x, v_prev = 0.0 * v, w = v_prev, w_prev = v_prev, q;
+  Real resid = norm(v) / normb;
+  if (resid <= tol) { tol = resid; max_iter = 0; return 0; }
+  Vec z = M.solve(v);
+  Real g2 = dot(z, v);
+  if (!(g2 > 0)) { tol = resid; max_iter = 0; return 2; }
+  Real gam = std::sqrt(g2), gam_prev = 1, eta = gam, kappa = resid * normb / gam, s0 = 0, s1 = 0, c0 = 1, c1 = 1;
+  auto true_resid = [&]() { q = b - A * x; return Real(norm(q) / normb); };
+  const int maxit = max_iter;
+  for (int j = 1; j <= maxit; j++) {
+    q = A * z;
+    const Real delta = dot(q, z) / (gam * gam);
+    Vec v_new = (1.0 / gam) * q - (delta / gam) * v - (gam / gam_prev) * v_prev;
+    Vec z_new = M.solve(v_new);
+    const Real gn2 = dot(z_new, v_new);
+    if (!(gn2 >= 0)) { tol = true_resid(); max_iter = j; return 2; }
+    const Real gamn = std::sqrt(gn2);
+    const Real a0 = c1 * delta - c0 * s1 * gam, a1 = std::sqrt(a0 * a0 + gn2), a2 = s1 * delta + c0 * c1 * gam, a3 = s0 * gam;
+    if (a1 == 0) { tol = true_resid(); max_iter = j; return 3; }
+    const Real cn = a0 / a1, sn = gamn / a1;
+    Vec w_new = (1.0 / a1) * ((1.0 / gam) * z - a3 * w_prev - a2 * w);      // (Vec need not offer a quotient; the device path divides)
+    x += (cn * eta) * w_new;
+    eta = -sn * eta;
+    v_prev = v; v = v_new; z = z_new; w_prev = w; w = w_new;
+    s0 = s1; s1 = sn; c0 = c1; c1 = cn; gam_prev = gam; gam = gamn;
+    bool fresh = false;
+    if (kappa * std::fabs(eta) / normb < tol || gamn == 0) {
+      resid = true_resid(); fresh = true;
+      if (resid < tol) { tol = resid; max_iter = j; return 0; }
+      if (gamn == 0) { tol = resid; max_iter = j; return 3; }
+      kappa = resid * normb / std::fabs(eta);
+    }
+    if (j == maxit && !fresh) resid = true_resid();
+  }
+  tol = resid;
+  return 1;
+}
+// Device-resident fast path (mgs_minres: seven work vectors, one cycle and one SpMV per iteration).  The hierarchy must be a fixed symmetric
+// operator (nu1 == nu2, no K-cycle): mgs_minres refuses any other, and there is no flexible form to fall back to.
+inline int MINRESiml(const DeviceMatrix &A, Vector &x, const Vector &b, const MultiGridPrecond &M, int &max_iter, double &tol) {
+  int status = -1;
+  check(mgs_minres(A.handle(), x.out(), b.handle(), M.use_preconditioner() ? M.handle() : nullptr, &max_iter, &tol, &status), context());
+  return status;
+}
+// with the host SMatrix the preconditioner was built from, as the reference's main() calls its solver (bicg.cpp:168)
+inline int MINRESiml(const SMatrix &, Vector &x, const Vector &b, const MultiGridPrecond &M, int &max_iter, double &tol) {
+  return MINRESiml(M.matrix(), x, b, M, max_iter, tol);
+}
+
 // ---------------------------------------------------------------- projected initial guesses (mgs.h: mgs_guess)
 // No reference counterpart: the reference solves one right-hand side (bicg.cpp:159-166).  For a caller who solves with the same operator
 // again and again:   SolutionGuess guess(A, MGS_GUESS_ENERGY);   per step:  guess.apply(b, x);  CGiml(A, x, b, M, it, tol);  guess.update(x);

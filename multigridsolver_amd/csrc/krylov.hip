@@ -37,30 +37,6 @@ int mgs_krylov_nullspace(const mgs_csr *A, const mgs_hier *h, const char *who, b
   return MGS_OK;
 }
 
-// What the three solvers share.  Work vectors are taken from the pool in the order the solver asks and go back when the solve ends, first-taken-first
-// or (reverse) last-taken-first: the next solve must find the same vectors in the same roles (graph slots are keyed by their addresses).
-struct krylov_frame {
-  mgs_ctx *ctx; mgs_hier *h; int n; bool ns, reverse;      // n: owned rows; ns: constant null space declared
-  std::vector<mgs_vec *> taken;
-  ~krylov_frame() {
-    hipStreamSynchronize(ctx->stream);
-    if (reverse) std::reverse(taken.begin(), taken.end());
-    for (mgs_vec *v : taken) mgs_ws_put(ctx, v);
-  }
-  int take(mgs_vec **q, int64_t len) { MGS_TRY(mgs_ws_get(ctx, len, n, q)); taken.push_back(*q); return MGS_OK; }
-  mgs_vec view(const mgs_vec *full) const { mgs_vec v; v.ctx = ctx; v.n = n; v.d = full->d; v.owns = false; return v; }      // the owned part, so BLAS-1 sizes agree
-  // halo of the level-0 vector w through the hierarchy's transport (no hierarchy: nothing to refresh); a failed exchange has always been MGS_ERR_STATE here
-  int halo(mgs_vec *w) const { return !h || mgs_halo_exchange(h, 0, w->d, w->d + n) == MGS_OK ? MGS_OK : MGS_ERR_STATE; }
-  // ‖b‖ (bicg.cpp:80), of a zero vector 1 (:85-86); constant null space: ‖Πb‖, b only read
-  int norm_b(const mgs_vec &bv, double *normb) const {
-    double d2[2];
-    if (ns) { MGS_TRY(k_const_dev_nrm2(ctx, n, bv.d, d2)); *normb = std::sqrt(d2[0]); }
-    else MGS_TRY(mgs_nrm2(&bv, normb));
-    if (*normb == 0.0) *normb = 1;
-    return MGS_OK;
-  }
-};
-
 extern "C" {
 
 // BiCGSTABiml, reference src/common/bicg.cpp:74-136, statement by statement on device vectors.

@@ -211,7 +211,8 @@ int mgs_ctx_set_option(mgs_ctx *ctx, const char *key, int value) {
   else if (k == "blas1_vec") ctx->opt_blas1_vec = value;
   else if (k == "post_results") ctx->opt_post_results = value;
   else if (k == "blas1_pairs") ctx->opt_blas1_pairs = value;
-  else if (k == "stage_unroll") ctx->opt_stage_unroll = value;
+  else if (k == "minres_nt") ctx->opt_minres_nt = value;
+  else if (k == "stage_unroll")ctx->opt_stage_unroll = value;
   else if (k == "rowptr_scan") ctx->opt_rowptr_scan = value;
   else if (k == "pre_nodiag") ctx->opt_pre_nodiag = value;
   else if (k == "pack7") ctx->opt_pack7 = value;
@@ -1362,11 +1363,15 @@ int mgs_time_kernel(const mgs_csr *A, int op, const mgs_vec *x, const mgs_vec *b
   mgs_ctx *ctx = A->ctx;
   MGS_CHECK(ctx, reps > 0 && ms && x && out, MGS_ERR_INVALID, "mgs_time_kernel: bad arguments");
   MGS_CHECK(ctx, op == MGS_OP_SPMV || (b && (op == MGS_OP_RESIDUAL || dinv)), MGS_ERR_INVALID, "mgs_time_kernel: missing operand");
+  const bool upd = op == 3;      // mgs_minres's update pass: x = z̃, b = w, dinv = w_prev, out = the solution; coefficients that keep every entry bounded
+  MGS_CHECK(ctx, !upd || (x->n >= A->rows && b->n >= A->rows && dinv->n >= A->rows && out->n >= A->rows), MGS_ERR_INVALID, "mgs_time_kernel: vectors shorter than %d", A->rows);
   hipEvent_t e0, e1;
   MGS_HIP(ctx, hipEventCreate(&e0)); MGS_HIP(ctx, hipEventCreate(&e1));
   MGS_HIP(ctx, hipEventRecord(e0, ctx->stream));
-  for (int i = 0; i < reps; ++i)
-    MGS_TRY(mgs_launch_csr_op(A, op, x->d, b ? b->d : nullptr, dinv ? dinv->d : nullptr, 0.6, out->d));
+  for (int i = 0; i < reps; ++i) {
+    if (upd) MGS_TRY(k_minres_update(ctx, A->rows, 0.7, -0.3, 1.9, 2.3, 1.1e-3, x->d, dinv->d, b->d, out->d));
+    else MGS_TRY(mgs_launch_csr_op(A, op, x->d, b ? b->d : nullptr, dinv ? dinv->d : nullptr, 0.6, out->d));
+  }
   MGS_HIP(ctx, hipEventRecord(e1, ctx->stream));
   MGS_HIP(ctx, hipEventSynchronize(e1));
   float t = 0; MGS_HIP(ctx, hipEventElapsedTime(&t, e0, e1));

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -86,7 +88,9 @@ struct mgs_ctx {
   int opt_stage_unroll = 1;   // row-block kernels stage their value slice without a loop in front of the barrier (predicated 16-byte loads / LDS-DMA): −4 … −7 % per cycle
   int opt_blas1_pairs = 1;    // ... pairs per lane of those kernels: 1 = one-shot workgroups (0: capped persistent grid, k: k pairs per lane)
   int opt_blas1_vec = 1;      // axpby / axpbypcz / update+dots move 16 B per lane with four loads per stream in flight (same per-element bits)
-  int opt_aggpre_max_rows = 300000;   // levels with at most this many rows run pre pass + restriction as ONE aggregate-parallel kernel (launch-bound sizes; same bits)
+  int opt_minres_nt = 0;      // k_minres_update stores w_prev (read again two passes later) with the `nt` hint where nt_store applies; x keeps plain stores.  Off: the gain
+                              // is unmeasured (tools/ab_minres.py, profiles/r21_minres.md)
+  int opt_aggpre_max_rows = 300000;  // levels with at most this many rows run pre pass + restriction as ONE aggregate-parallel kernel (launch-bound sizes; same bits)
   int opt_emu_split_self = 0;   // tools/emulate_rank.py only: a packed exchange with the rank itself goes out as two messages (a middle rank has two neighbours)
   int opt_kcycle_energy = 0;  // K-cycle coefficients from energy inner products (flexible-CG form; SPD operators) instead of the GCR form of the paper
   int opt_native_graph = 1;   // row shards on the native RCCL transport: capture the whole cycle (exchanges included) in a hipGraph
@@ -446,6 +450,11 @@ int k_dot2(mgs_ctx *ctx, int64_t n, const double *x, const double *y, const doub
 // and the residual in place (r ← r − a·q, out_host2[0] = ‖r‖²)
 int k_pcg_direction(mgs_ctx *ctx, int64_t n, int first, double a, double beta, double *x, double *p, const double *z);
 int k_pcg_residual(mgs_ctx *ctx, int64_t n, double a, double *r, const double *q, double *out_host2);
+// (minres.hip) mgs_minres's one pass of its own: the new search direction over the one before last, and the x update with it.  Per entry
+// t = inv_g·z − a3·w_prev; t = t − a2·w; wn = t/a1; w_prev = wn; x = x + step·wn — every product, sum and quotient rounded on its own
+// (tests/minres_ref.py: update_ref restates the bits).  48 B per row: read z, w_prev, w, x; write w_prev, x.
+int k_minres_update(mgs_ctx *ctx, int64_t n, double inv_g, double a3, double a2, double a1, double step,
+                    const double *z, double *w_prev /* in: w_{j−1}, out: w_{j+1} */, const double *w, double *x);
 // Reductions that end in a host look (k_dot, k_dot2, k_dot2_finish, mgs_spmv_dots) take out_host = NULL as "enqueue and fold, do not fetch": the
 // same launches, nothing posted, the folded values left in red_dev[MGS_DOT_BLOCKS ..] for the next kernel on the stream (mgs_pcg_plan).
 int mgs_blas1_grid(const mgs_ctx *ctx, int64_t n2);          // workgroups of a 16-byte BLAS-1 launch over n2 pairs (grid_vec)
@@ -532,6 +541,29 @@ int mgs_halo_exchange(mgs_hier *h, int l, const double *src, double *dst, bool f
 int mgs_krylov_nullspace(const mgs_csr *A, const mgs_hier *h, const char *who, bool *ns_out);
 int mgs_ws_get(mgs_ctx *ctx, int64_t n, int64_t owned, mgs_vec **out);
 void mgs_ws_put(mgs_ctx *ctx, mgs_vec *v);
+// What the host-driven solvers share (krylov.hip, minres.hip).  Work vectors are taken from the pool in the order the solver asks and go back when the solve ends, first-taken-first
+// or (reverse) last-taken-first: the next solve must find the same vectors in the same roles (graph slots are keyed by their addresses).
+struct krylov_frame {
+  mgs_ctx *ctx; mgs_hier *h; int n; bool ns, reverse;      // n: owned rows; ns: constant null space declared
+  std::vector<mgs_vec *> taken;
+  ~krylov_frame() {
+    hipStreamSynchronize(ctx->stream);
+    if (reverse) std::reverse(taken.begin(), taken.end());
+    for (mgs_vec *v : taken) mgs_ws_put(ctx, v);
+  }
+  int take(mgs_vec **q, int64_t len) { MGS_TRY(mgs_ws_get(ctx, len, n, q)); taken.push_back(*q); return MGS_OK; }
+  mgs_vec view(const mgs_vec *full) const { mgs_vec v; v.ctx = ctx; v.n = n; v.d = full->d; v.owns = false; return v; }      // the owned part, so BLAS-1 sizes agree
+  // halo of the level-0 vector w through the hierarchy's transport (no hierarchy: nothing to refresh); a failed exchange has always been MGS_ERR_STATE here
+  int halo(mgs_vec *w) const { return !h || mgs_halo_exchange(h, 0, w->d, w->d + n) == MGS_OK ? MGS_OK : MGS_ERR_STATE; }
+  // ‖b‖ (bicg.cpp:80), of a zero vector 1 (:85-86); constant null space: ‖Πb‖, b only read
+  int norm_b(const mgs_vec &bv, double *normb) const {
+    double d2[2];
+    if (ns) { MGS_TRY(k_const_dev_nrm2(ctx, n, bv.d, d2)); *normb = std::sqrt(d2[0]); }
+    else MGS_TRY(mgs_nrm2(&bv, normb));
+    if (*normb == 0.0) *normb = 1;
+    return MGS_OK;
+  }
+};
 template <class T>
 static inline int mgs_dev_alloc(mgs_ctx *ctx, T **p, size_t count) {
   *p = nullptr;

@@ -24,7 +24,8 @@ def main(argv=None):
     ap.add_argument("--P", default=None, help="prolongation .mtx from the AGMG setup (single GPU only); default: aggregate on device")
     ap.add_argument("--tol", type=float, default=1e-6)           # bicg.cpp:148
     ap.add_argument("--max-iter", type=int, default=10000)       # bicg.cpp:164
-    ap.add_argument("--solver", choices=["bicgstab", "fgcr", "pcg"], default=None, help="default: bicgstab")
+    ap.add_argument("--solver", choices=["bicgstab", "fgcr", "pcg", "minres"], default=None,
+                    help="default: bicgstab; minres: symmetric indefinite systems with a V(nu, nu) preconditioner, single GPU only")
     ap.add_argument("--pcg-flexible", action="store_true", help="--solver pcg: flexible β, for a preconditioner that is not a fixed symmetric operator (--nu1 != --nu2, --kcycle)")
     ap.add_argument("--ahead", type=int, default=None, metavar="N",
                     help="--solver pcg or --solver bicgstab, named on the command line: solve through a PcgPlan resp. BicgstabPlan (scalars stay on the "
@@ -55,6 +56,8 @@ def main(argv=None):
         raise SystemExit("multi-GPU: --nullspace is a single-GPU option (row shards carry no null-space declaration)")
     if args.ahead is not None and (args.solver not in ("pcg", "bicgstab") or world > 1 or args.ahead < 0):
         raise SystemExit("--ahead N (N >= 0) goes with --solver pcg or --solver bicgstab, named explicitly, on a single GPU")
+    if args.solver == "minres" and (args.ahead is not None or world > 1):
+        raise SystemExit("--solver minres runs on a single GPU and has no plan (--ahead goes with --solver pcg or --solver bicgstab)")
     if args.fgcr_ahead is not None and (args.solver != "fgcr" or world > 1 or args.fgcr_ahead < 0):
         raise SystemExit("--fgcr-ahead N (N >= 0) goes with --solver fgcr on a single GPU")
     if args.solver is None:
@@ -92,6 +95,8 @@ def main(argv=None):
             st, it, tol = plan.solve(x, b, args.max_iter, args.tol, args.ahead if args.fgcr_ahead is None else args.fgcr_ahead)
         elif args.solver == "pcg":
             st, it, tol = mg.pcg(A, x, b, h, args.max_iter, args.tol, args.pcg_flexible)
+        elif args.solver == "minres":
+            st, it, tol = mg.minres(A, x, b, h, args.max_iter, args.tol)
         else:
             st, it, tol = (mg.bicgstab if args.solver == "bicgstab" else lambda *a: mg.fgcr(a[0], a[1], a[2], a[3], 10, a[4], a[5]))(A, x, b, h, args.max_iter, args.tol)
         ctx.sync(); dt = time.perf_counter() - t0
@@ -121,13 +126,13 @@ def main(argv=None):
         parts = comm.all_gather_object(x.numpy(plan.n_loc))
         xs = np.concatenate(parts)
     if rank == 0:
-        pcg = args.solver == "pcg"
-        sys.stderr.write("    \033[1;34m[time] \033[0m%-42s : %f.\n" % ("PCG_SolveTimer" if pcg else "BiCGStab_SolveTimer", dt))
+        name = {"pcg": "PCG", "minres": "MINRES"}.get(args.solver)
+        sys.stderr.write("    \033[1;34m[time] \033[0m%-42s : %f.\n" % (name + "_SolveTimer" if name else "BiCGStab_SolveTimer", dt))
         if st == 0:
             print("    \033[32m\033[1m[info] \033[00m%-42s : %g." % ("Tolerance ", tol))
-            print("    \033[32m\033[1m[info] \033[00m%-42s : %d." % ("Number of iterations PCG" if pcg else "Number of iterations BICG", it))
+            print("    \033[32m\033[1m[info] \033[00m%-42s : %d." % ("Number of iterations " + name if name else "Number of iterations BICG", it))
         else:
-            print(("PCG encountered a problem with status code: %d" if pcg else "BiCGSTABiml encountered a problem with status code: %d") % st)
+            print((name + " encountered a problem with status code: %d" if name else "BiCGSTABiml encountered a problem with status code: %d") % st)
         if args.dump_x:
             xs.astype("<f8").tofile(args.dump_x)
     if world > 1:
