@@ -167,12 +167,12 @@ static bool level_fuses(const mgs_hier *h, int l) {
   bool transport_ok = true;
   if (L.A->cols > L.A->rows) transport_ok = L.hbuf && L.halo_dinv && L.cmap_ext && (L.nx || h->halo_fused);
   if (C.A->cols > C.A->rows) transport_ok = transport_ok && (C.nx || h->halo_fused);
-  return h->ctx->opt_fuse && !h->additive && h->nu1 == 1 && h->nu2 == 1 && L.wd && L.wd_omega == h->omega && L.T->aggregation && L.A->lds_cap > 0 && transport_ok;
+  return h->ctx->opt_fuse && !h->additive && h->nu1 == 1 && h->nu2 == 1 && L.wd && mgs_operand_in_step(L, OPD_WD) && L.T->aggregation && L.A->lds_cap > 0 && transport_ok;
 }
 
 // option pre_nodiag: the grouped pre pass of this level runs on val_nd (an eligible unsharded FP64 level whose compact operand is in step with val_wd)
 static bool level_pre_nodiag(const mgs_hier *h, const mgs_level &L, bool halo, bool f32) {
-  return h->ctx->opt_pre_nodiag && L.val_nd && L.nd_code && L.nd_ok && !L.nd_stale && !halo && !f32 && !h->ctx->opt_valcode;
+  return h->ctx->opt_pre_nodiag && mgs_level_nd_ready(L) && !halo && !f32 && !h->ctx->opt_valcode;
 }
 // The arm of level l's fused pre pass under the options as they stand — the ONE place that chooses it (cycle_fused and
 // mgs_hier_pre_pass_info both ask here).  shard_split: a row shard that launches its interior row blocks beside the halo exchange, uncaptured and

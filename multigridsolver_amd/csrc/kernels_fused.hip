@@ -714,7 +714,7 @@ int mgs_launch_group_pre(const mgs_csr *A, const mgs_groups *G, const mgs_xfer *
   const bool ordered = !pairs && G->gorder && ctx->opt_group_order > 0 && ctx->opt_xcd_remap;
   if (ordered) grid = dim3(8 * G->gorder_per_xcd);
   // option pack7: a packed copy of the operand the coded blocks stream (val_nd or Â's values), in step with it
-  const bool packed = pk && ctx->opt_pack7 && !pk->stale && pk->nd == (val_nd != nullptr) && c && !f32 && !hv && !pairs;
+  const bool packed = mgs_pack7_serves(pk, val_nd != nullptr) && ctx->opt_pack7 && c && !f32 && !hv && !pairs;
   if (pk) pk->ran = packed ? 1 : 0;
   // the pair kernel's parameters are the leading ones of the one-block kernel's; `more`: what the latter takes behind them
   auto launch = [&](auto kernel, auto vals, int threads, size_t lds, auto... more) {

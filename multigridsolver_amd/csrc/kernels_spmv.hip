@@ -427,7 +427,7 @@ int launch_coded(const mgs_csr *A, const mgs_rowcode *c, int op, const int *idx,
   const bool sweep = A->sweep && !f32 && !hv && !vtab && op == FUSE_POST_MAPPED;
   // option pack7: the view carries a packed copy of its FP64 values that is in step with them (pre pass on Â, post pass on A·P; unsharded, no value tuples)
   mgs_pack7 *pk = A->pk7;
-  const bool packed = pk && ctx->opt_pack7 && !pk->stale && !pk->nd && c && !f32 && !hv && !vtab && !sweep && (op == MGS_OP_RESIDUAL || op == FUSE_POST_MAPPED);
+  const bool packed = mgs_pack7_serves(pk, false) && ctx->opt_pack7 && c && !f32 && !hv && !vtab && !sweep && (op == MGS_OP_RESIDUAL || op == FUSE_POST_MAPPED);
   if (pk) pk->ran = packed ? 1 : 0;
   BlockMap gbm; dim3 ggrid(1);
   if (sweep) ggrid = plan_group_map(A, A->sweep, gbm);

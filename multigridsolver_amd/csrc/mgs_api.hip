@@ -1,5 +1,6 @@
 // mgs_api.hip — C-ABI implementation (include/mgs.h): the arena, context, device containers, primitives and the
-// multilevel hierarchy (construction, options, refresh, operands of the fused passes); the cycle is cycle.hip, the Krylov solvers krylov.hip.
+// multilevel hierarchy (construction, options, refresh); the operands of the fused passes are hier_operands.hip, the cycle is cycle.hip, the Krylov
+// solvers krylov.hip.
 // The host logic is C++; every numeric step is a HIP kernel on the context's stream.  No CPU fallback.
 #include "mgs_internal.hpp"
 
@@ -635,23 +636,8 @@ static int diag0_needed(mgs_hier *h, const char *who) {
 static void level_free(mgs_level &L) {
   if (L.own_A && L.A) mgs_csr_destroy(const_cast<mgs_csr *>(L.A));
   if (L.T) mgs_xfer_destroy(L.T);
-  mgs_vec_destroy(L.dinv); mgs_vec_destroy(L.r); mgs_vec_destroy(L.tmp); mgs_vec_destroy(L.b); mgs_vec_destroy(L.x); mgs_vec_destroy(L.wd);
-  mgs_vec_destroy(L.hbuf);
-  if (L.val_wd) mgs_hip_free(L.val_wd);
-  if (L.val_nd) mgs_hip_free(L.val_nd);
-  if (L.nd_code) mgs_hip_free(L.nd_code);
-  for (mgs_pack7 *p : {L.pk_hat, L.pk_ap}) if (p) { if (p->data) mgs_hip_free(p->data); if (p->e0) mgs_hip_free(p->e0); delete p; }
-  if (L.val_wd32) mgs_hip_free(L.val_wd32);
-  if (L.ap_val32) mgs_hip_free(L.ap_val32);
-  if (L.col_agg) mgs_hip_free(L.col_agg);
-  if (L.cmap_ext) mgs_hip_free(L.cmap_ext);
-  mgs_free_rowcode(L.code_agg);
-  if (L.AP) mgs_csr_destroy(L.AP);
-  mgs_free_rowcode(L.code_ap);
-  mgs_free_rowcode(L.code_pre);
-  mgs_free_rowcode(L.code_hat);
-  mgs_free_groups(L.grp);
-  if (L.dpos) mgs_hip_free(L.dpos);
+  mgs_vec_destroy(L.dinv); mgs_vec_destroy(L.r); mgs_vec_destroy(L.tmp); mgs_vec_destroy(L.b); mgs_vec_destroy(L.x);
+  mgs_operands_free(L);
   if (L.nx) { if (L.nx->send_idx) mgs_hip_free(L.nx->send_idx); if (L.nx->sendbuf) mgs_hip_free(L.nx->sendbuf); delete L.nx; L.nx = nullptr; }
   mgs_vec_destroy(L.kc1); mgs_vec_destroy(L.kv1); mgs_vec_destroy(L.kc2); mgs_vec_destroy(L.kv2); mgs_vec_destroy(L.kr);
   if (L.kscal) mgs_hip_free(L.kscal);
@@ -661,61 +647,14 @@ void mgs_drop_graph(mgs_hier *h) {
   for (auto &g : h->graphs) { if (g.exec) hipGraphExecDestroy(g.exec); g = mgs_hier::GraphSlot(); }
   if (h->coarse_exec) { hipGraphExecDestroy(h->coarse_exec); h->coarse_exec = nullptr; }
 }
-// ---- operand precision (mgs_hier_set_operand_precision) ----
-// A level can run its two fused passes on FP32 copies of Â's and A·P's values when both operands exist, the level is square (no halo
-// columns) and both have short rows — then the float forms of the coded / grouped / aggregate-parallel kernels serve every row block.
-static bool level_f32_eligible(const mgs_hier *h, int l) {
-  if (l < 0 || l + 1 >= (int)h->lev.size()) return false;
-  const mgs_level &L = h->lev[l];
-  const mgs_ctx *ctx = h->ctx;
-  return ctx->opt_fuse && ctx->opt_fuse_operands && ctx->opt_merge_ap && !ctx->opt_valcode && L.T && L.T->aggregation && L.A->rows == L.A->cols &&
-         L.val_wd && L.AP && L.A->blkptr && L.AP->blkptr && L.A->lds_cap > 0 && L.AP->lds_cap > 0 && L.A->max_row_len <= 64 && L.AP->max_row_len <= 64;
+bool mgs_hier_sharded(const mgs_hier *h) {      // row-sharded in any form: such hierarchies are rebuilt, not refreshed, and keep FP64 operands
+  bool shard = h->halo || h->halo_begin || h->halo_fused || h->native || h->ntail || h->coarse;
+  for (auto &L : h->lev) shard = shard || L.A->cols > L.A->rows || L.nx;
+  return shard;
 }
-// ... and does so in the cycle the hierarchy would run NOW: only the fused zero-guess V(1,1) branch reads the operands at all
-bool mgs_level_runs_f32(const mgs_hier *h, int l) {
-  if (l < 0 || l >= (int)h->lev.size()) return false;
-  const mgs_level &L = h->lev[l];
-  return L.op_bits == 32 && L.val_wd32 && L.ap_val32 && h->nu1 == 1 && h->nu2 == 1 && !h->additive && level_f32_eligible(h, l);
+int mgs_level_in_range(const mgs_hier *h, int level, const char *who) {
+  MGS_CHECK(h->ctx, level >= 0 && level < (int)h->lev.size(), MGS_ERR_INVALID, "%s: level %d out of range", who, level); return MGS_OK;
 }
-// (re)builds the FP32 copies of a level switched to 32 bits from the FP64 operands; vals_changed: Â was rescaled (new ω)
-static int level_refresh_f32(mgs_hier *h, mgs_level &L, bool vals_changed) {
-  mgs_ctx *ctx = h->ctx;
-  if (L.op_bits != 32 || !L.val_wd || !L.AP) return MGS_OK;
-  if (!L.val_wd32) { MGS_TRY(mgs_dev_alloc(ctx, &L.val_wd32, (size_t)L.A->nnz + 8)); vals_changed = true; mgs_drop_graph(h); }
-  if (vals_changed) MGS_TRY(k_round_vals(ctx, L.val_wd, L.val_wd32, L.A->nnz));
-  if (!L.ap_val32) {
-    MGS_TRY(mgs_dev_alloc(ctx, &L.ap_val32, (size_t)L.AP->nnz + 8));
-    MGS_TRY(k_round_vals(ctx, L.AP->val, L.ap_val32, L.AP->nnz));
-    mgs_drop_graph(h);
-  }
-  return MGS_OK;
-}
-
-// option pack7: (re)builds the packed copies of a level's two operands where they are missing, stale or of the wrong source; all: whatever their
-// state (mgs_hier_refresh, whose new values sit in the buffers the cached graphs know).  Allocation drops the graphs; repacking in place does not.
-static int pack7_build(mgs_hier *h, mgs_pack7 *&p, const int *blkptr, int nblocks, int64_t nent, bool nd, int nd_rows, const double *src, bool all) {
-  mgs_ctx *ctx = h->ctx;
-  if (p && (p->nd != nd || p->nent != nent || p->nblocks != nblocks)) { mgs_hip_free(p->data); mgs_hip_free(p->e0); delete p; p = nullptr; mgs_drop_graph(h); }
-  if (!p) {
-    p = new mgs_pack7();
-    p->nd = nd; p->nent = nent; p->nblocks = nblocks;
-    const size_t bytes = (size_t)112 * (size_t)((nent + 15) / 16) + 16;      // padded to a whole record
-    MGS_TRY(mgs_dev_alloc(ctx, &p->data, bytes));
-    MGS_HIP(ctx, hipMemsetAsync(p->data, 0, bytes, ctx->stream));
-    MGS_TRY(mgs_dev_alloc(ctx, &p->e0, (size_t)nblocks));
-    mgs_drop_graph(h);
-  }
-  if (p->stale || all) { MGS_TRY(k_pack7(ctx, blkptr, nblocks, nd ? nd_rows : -1, src, p->e0, p->data)); p->stale = false; }
-  return MGS_OK;
-}
-static bool level_pack7_nd(const mgs_level &L) { return L.val_nd && L.nd_code && L.nd_ok && !L.nd_stale; }      // the pre pass's copy is of val_nd
-static int level_pack7(mgs_hier *h, mgs_level &L, bool all) {
-  const bool nd = level_pack7_nd(L);
-  MGS_TRY(pack7_build(h, L.pk_hat, L.A->blkptr, mgs_row_blocks(L.A), nd ? L.A->nnz - L.A->rows : L.A->nnz, nd, L.A->rows, nd ? L.val_nd : L.val_wd, all));
-  if (L.AP && L.AP->blkptr) MGS_TRY(pack7_build(h, L.pk_ap, L.AP->blkptr, mgs_row_blocks(L.AP), L.AP->nnz, false, 0, L.AP->val, all));
-  return MGS_OK;
-}
-
 extern "C" {
 
 int mgs_hier_create(mgs_ctx *ctx, const mgs_csr *A, double omega, int nu1, int nu2, mgs_hier **out) {
@@ -752,47 +691,14 @@ int mgs_hier_destroy(mgs_hier *h) {
 }
 int mgs_hier_set_smoother(mgs_hier *h, double omega, int nu1, int nu2) {
   MGS_CHECK(h->ctx, nu1 >= 0 && nu2 >= 0, MGS_ERR_INVALID, "negative sweep count");
+  if (omega != h->omega) for (auto &L : h->lev) mgs_operands_mark(L, OPD_WD);      // a new ω: the Â branch of every level
   h->omega = omega; h->nu1 = nu1; h->nu2 = nu2; mgs_drop_graph(h);
-  return MGS_OK;
-}
-int mgs_hier_set_operand_precision(mgs_hier *h, int bits, int levels) {
-  MGS_CHECK(nullptr, h, MGS_ERR_INVALID, "mgs_hier_set_operand_precision: NULL hierarchy");
-  mgs_ctx *ctx = h->ctx;
-  MGS_CHECK(ctx, bits == 64 || bits == 32, MGS_ERR_INVALID, "mgs_hier_set_operand_precision: bits must be 64 or 32 (got %d)", bits);
-  MGS_CHECK(ctx, h->finalized, MGS_ERR_INVALID, "mgs_hier_set_operand_precision: call mgs_hier_finalize first");
-  if (bits == 32) {
-    MGS_CHECK(ctx, !ctx->opt_valcode, MGS_ERR_INVALID, "mgs_hier_set_operand_precision: option valcode is on (coded blocks stream no values: nothing to shrink)");
-    bool shard = h->halo || h->halo_begin || h->halo_fused || h->native || h->ntail || h->coarse;
-    for (auto &L : h->lev) shard = shard || L.A->cols > L.A->rows || L.nx;
-    MGS_CHECK(ctx, !shard, MGS_ERR_INVALID, "mgs_hier_set_operand_precision: row-sharded hierarchies (halo columns, native tail) keep FP64 operands");
-    // the operands are prepared lazily, before a hierarchy's first cycle: do it now, so that the query answers right after this call
-    MGS_TRY(mgs_prepare_fused(h));
-  }
-  const int nl = (int)h->lev.size();
-  int k = 0;      // the longest eligible prefix, at most `levels` long
-  if (bits == 32) while (k < nl - 1 && (levels < 0 || k < levels) && level_f32_eligible(h, k)) ++k;
-  for (int l = 0; l < nl; ++l) {
-    mgs_level &L = h->lev[l];
-    L.op_bits = l < k ? 32 : 64;
-    if (L.op_bits == 32) MGS_TRY(level_refresh_f32(h, L, false));
-    else {      // the FP64 operands were kept: nothing to rebuild on the way back
-      if (L.val_wd32) { hipStreamSynchronize(ctx->stream); mgs_hip_free(L.val_wd32); L.val_wd32 = nullptr; }
-      if (L.ap_val32) { hipStreamSynchronize(ctx->stream); mgs_hip_free(L.ap_val32); L.ap_val32 = nullptr; }
-    }
-  }
-  mgs_drop_graph(h);
-  return MGS_OK;
-}
-int mgs_hier_operand_precision(const mgs_hier *h, int level, int *bits) {
-  MGS_CHECK(nullptr, h && bits, MGS_ERR_INVALID, "mgs_hier_operand_precision: NULL argument");
-  MGS_CHECK(h->ctx, level >= 0 && level < (int)h->lev.size(), MGS_ERR_INVALID, "mgs_hier_operand_precision: level %d out of range", level);
-  *bits = mgs_level_runs_f32(h, level) ? 32 : 64;
   return MGS_OK;
 }
 // ---- native RCCL transport of a sharded hierarchy (comm_rccl.hip) ----
 int mgs_hier_set_native_exchange(mgs_hier *h, int level, mgs_comm *c, const int *send_idx, const int *send_counts, const int *recv_counts) {
   mgs_ctx *ctx = h->ctx;
-  MGS_CHECK(ctx, level >= 0 && level < (int)h->lev.size(), MGS_ERR_INVALID, "mgs_hier_set_native_exchange: level %d out of range", level);
+  MGS_TRY(mgs_level_in_range(h, level, "mgs_hier_set_native_exchange"));
   mgs_level &L = h->lev[level];
   auto free_plan = [](mgs_native_plan *P) { if (!P) return; if (P->send_idx) mgs_hip_free(P->send_idx); if (P->sendbuf) mgs_hip_free(P->sendbuf); delete P; };
   free_plan(L.nx); L.nx = nullptr;
@@ -932,7 +838,7 @@ int mgs_hier_set_kcycle_entry(mgs_hier *h, int on) { h->kcycle_entry = on != 0; 
 int mgs_hier_kcycle_scalars(mgs_hier *h, int level, double out[5]) {
   MGS_CHECK(nullptr, h && out, MGS_ERR_INVALID, "mgs_hier_kcycle_scalars: NULL argument");
   mgs_ctx *ctx = h->ctx;
-  MGS_CHECK(ctx, level >= 0 && level < (int)h->lev.size(), MGS_ERR_INVALID, "mgs_hier_kcycle_scalars: level %d out of range", level);
+  MGS_TRY(mgs_level_in_range(h, level, "mgs_hier_kcycle_scalars"));
   const mgs_level &L = h->lev[level];
   MGS_CHECK(ctx, L.kscal, MGS_ERR_STATE, "mgs_hier_kcycle_scalars: level %d has run no K step", level);
   MGS_HIP(ctx, hipMemcpyAsync(out, L.kscal, sizeof(double) * 5, hipMemcpyDeviceToHost, ctx->stream));
@@ -1098,7 +1004,7 @@ int mgs_hier_finalize(mgs_hier *h) {
 
 // Values changed, pattern did not: everything in h that depends on matrix VALUES is recomputed from the fine operator's current
 // values, level by level from the top — D⁻¹, the next level's operator (numeric Galerkin product into the existing val array), and
-// whichever operands of the fused passes mgs_prepare_fused has already built (wd, Â, A·P, their FP32 copies), each in its existing
+// whichever operands of the fused passes mgs_prepare_fused has already built (mgs_operands_fill), each in its existing
 // buffer.  Aggregates, patterns, pattern codes, row-block groups, buffers and — because no device buffer moves — the cached cycle
 // graphs are kept.  Everything is enqueued on the context's stream; the host reads two counters once, before the dense inverse.
 int mgs_hier_refresh(mgs_hier *h) {
@@ -1106,9 +1012,7 @@ int mgs_hier_refresh(mgs_hier *h) {
   mgs_ctx *ctx = h->ctx;
   MGS_CHECK(ctx, h->finalized || h->refresh_failed, MGS_ERR_STATE, "mgs_hier_refresh: call mgs_hier_finalize first");
   MGS_CHECK(ctx, !ctx->opt_valcode, MGS_ERR_INVALID, "mgs_hier_refresh: option valcode is on (pattern codes carry the values): rebuild the hierarchy instead");
-  bool shard = h->halo || h->halo_begin || h->halo_fused || h->native || h->ntail || h->coarse;
-  for (auto &L : h->lev) shard = shard || L.A->cols > L.A->rows || L.nx;
-  MGS_CHECK(ctx, !shard, MGS_ERR_INVALID, "mgs_hier_refresh: row-sharded hierarchies (halo columns, halo callbacks, native plans or tail) are not refreshed: rebuild them");
+  MGS_CHECK(ctx, !mgs_hier_sharded(h), MGS_ERR_INVALID, "mgs_hier_refresh: row-sharded hierarchies (halo columns, halo callbacks, native plans or tail) are not refreshed: rebuild them");
   const int nl = (int)h->lev.size();
   for (int l = 0; l < nl; ++l) {
     const mgs_level &L = h->lev[l];
@@ -1118,7 +1022,7 @@ int mgs_hier_refresh(mgs_hier *h) {
   }
   const bool ns = hier_nullspace_const(h);
   if (ns) MGS_TRY(nullspace_check(h, "mgs_hier_refresh"));
-  bool kept = true, nd_built = false;
+  bool kept = true;
   if (!h->refresh_flags) MGS_TRY(mgs_dev_alloc(ctx, &h->refresh_flags, 2));
   MGS_HIP(ctx, hipMemsetAsync(h->refresh_flags, 0, 2 * sizeof(int), ctx->stream));
   if (h->nd_flag) MGS_HIP(ctx, hipMemsetAsync(h->nd_flag, 0, sizeof(int), ctx->stream));
@@ -1128,20 +1032,10 @@ int mgs_hier_refresh(mgs_hier *h) {
     rc = k_diag_inv_async(L.A, L.dinv->d, h->refresh_flags);
     if (l + 1 >= nl) break;
     if (rc == MGS_OK) rc = k_galerkin_numeric(L.A, L.T->n_coarse, L.T->cptr, L.T->members, L.T->agg, const_cast<mgs_csr *>(h->lev[l + 1].A), h->refresh_flags + 1);
-    if (!L.wd) continue;      // operands not built yet: the next cycle's mgs_prepare_fused sees the new values anyway
-    if (rc == MGS_OK) rc = k_axpby(ctx, L.n_ext, h->omega, L.dinv->d, 0.0, L.wd->d);
-    L.wd_omega = h->omega;    // (a new ω set since the last cycle: mgs_hier_set_smoother has dropped the graphs already)
-    if (rc == MGS_OK && L.val_wd) rc = k_scale_vals(ctx, L.A, L.wd->d, L.val_wd);
-    if (rc == MGS_OK && L.val_wd && L.val_nd && L.nd_ok) { rc = k_drop_diag_vals(ctx, L.A, L.val_wd, h->omega, L.val_nd, L.nd_code, h->nd_flag); L.nd_omega = h->omega; nd_built = true; }
-    if (rc == MGS_OK && L.AP) rc = k_galerkin_numeric(L.A, L.A->rows, nullptr, nullptr, L.T->agg, L.AP, h->refresh_flags + 1);
-    if (rc == MGS_OK && L.val_wd && L.val_wd32) rc = k_round_vals(ctx, L.val_wd, L.val_wd32, L.A->nnz);
-    if (rc == MGS_OK && L.AP && L.ap_val32) rc = k_round_vals(ctx, L.AP->val, L.ap_val32, L.AP->nnz);
-    // packed copies follow their sources, in place (a level whose nd_ok ends below streams val_wd unpacked until the next cycle's setup repacks it)
-    if (rc == MGS_OK && L.pk_hat && L.pk_hat->nd == level_pack7_nd(L)) rc = level_pack7(h, L, true);
-    else if (L.pk_hat) L.pk_hat->stale = true;
+    mgs_operands_mark(L, OPD_WD | OPD_AP); if (rc == MGS_OK) rc = mgs_operands_fill(h, l, ~0u);      // the whole chain of derived operands: refilled where built, each in its existing buffer
   }
   int flags[2] = {0, 0}, nd_bad = 0;
-  if (rc == MGS_OK && nd_built && hipMemcpyAsync(&nd_bad, h->nd_flag, sizeof nd_bad, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = mgs_fail(ctx, MGS_ERR_HIP, "mgs_hier_refresh: flag copy failed");
+  if (rc == MGS_OK && h->nd_flag && hipMemcpyAsync(&nd_bad, h->nd_flag, sizeof nd_bad, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = mgs_fail(ctx, MGS_ERR_HIP, "mgs_hier_refresh: flag copy failed");
   if (rc == MGS_OK && hipMemcpyAsync(flags, h->refresh_flags, sizeof flags, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = mgs_fail(ctx, MGS_ERR_HIP, "mgs_hier_refresh: flag copy failed");
   if (rc == MGS_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = mgs_fail(ctx, MGS_ERR_HIP, "mgs_hier_refresh: %s", hipGetErrorString(hipGetLastError()));
   if (rc == MGS_OK && flags[1]) rc = mgs_fail(ctx, MGS_ERR_STATE, "mgs_hier_refresh: %d entries fall outside the kept coarse patterns (the fine pattern is not the one the hierarchy was built for)", flags[1]);
@@ -1169,42 +1063,10 @@ int mgs_hier_refresh_info(const mgs_hier *h, int64_t out[4]) {
   return MGS_OK;
 }
 
-int mgs_hier_fused_info(const mgs_hier *h, int level, int64_t out[6]) {
-  MGS_CHECK(h->ctx, level >= 0 && level < (int)h->lev.size(), MGS_ERR_INVALID, "mgs_hier_fused_info: level %d out of range", level);
-  const mgs_level &L = h->lev[level];
-  auto coded = [](const mgs_rowcode *c) -> int64_t { return c ? c->coded_blocks : 0; };
-  out[0] = mgs_row_blocks(L.A); out[1] = L.val_wd != nullptr; out[2] = L.col_agg != nullptr || L.AP != nullptr;
-  out[3] = coded(L.A->code); out[4] = coded(L.code_pre); out[5] = coded(L.AP ? L.code_ap : L.code_agg);
-  return MGS_OK;
-}
-
 int mgs_hier_group_info(const mgs_hier *h, int level, int64_t out[4]) {
-  MGS_CHECK(h->ctx, level >= 0 && level < (int)h->lev.size(), MGS_ERR_INVALID, "mgs_hier_group_info: level %d out of range", level);
+  MGS_TRY(mgs_level_in_range(h, level, "mgs_hier_group_info"));
   const mgs_groups *G = h->lev[level].grp;
   out[0] = G ? G->ngroups : 0; out[1] = G ? G->nblocks - G->ngroups : 0;   /* blocks merged into another block's group */ out[2] = G ? G->nstray : 0; out[3] = mgs_row_blocks(h->lev[level].A);
-  return MGS_OK;
-}
-int mgs_hier_pack_info(mgs_hier *h, int level, int64_t out[8]) {
-  MGS_CHECK(nullptr, h && out, MGS_ERR_INVALID, "mgs_hier_pack_info: NULL argument");
-  mgs_ctx *ctx = h->ctx;
-  MGS_CHECK(ctx, level >= 0 && level < (int)h->lev.size(), MGS_ERR_INVALID, "mgs_hier_pack_info: level %d out of range", level);
-  const mgs_level &L = h->lev[level];
-  for (int q = 0; q < 8; ++q) out[q] = 0;
-  out[3] = out[6] = -1;
-  const mgs_pack7 *ps[2] = {L.pk_hat, L.pk_ap};
-  for (int w = 0; w < 2; ++w) {
-    const mgs_pack7 *p = ps[w];
-    if (!p) continue;
-    std::vector<int> e0((size_t)p->nblocks);
-    MGS_HIP(ctx, hipMemcpyAsync(e0.data(), p->e0, sizeof(int) * e0.size(), hipMemcpyDeviceToHost, ctx->stream));
-    MGS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    int64_t packed = 0;
-    for (int v : e0) packed += v >= 0;
-    const bool unused = p->stale || L.op_bits != 64 || ctx->opt_valcode || !ctx->opt_pack7;      // no launch reads the copy as things stand
-    out[w ? 4 : 0] = p->nblocks; out[w ? 5 : 1] = unused ? 0 : packed; out[w ? 6 : 3] = p->ran;
-    if (!w) out[2] = p->nd ? 2 : 1;
-    out[7] += (int64_t)112 * ((p->nent + 15) / 16) + 16 + (int64_t)sizeof(int) * p->nblocks;
-  }
   return MGS_OK;
 }
 int mgs_hier_graph_info(const mgs_hier *h, int64_t out[4]) {
@@ -1239,124 +1101,6 @@ int64_t mgs_hier_vcycle_bytes(const mgs_hier *h) {
   else tot += (int64_t)h->nc * h->nc * 8 + 16 * (int64_t)h->nc;
   return tot;
 }
-
-}  // extern "C"
-
-// wd = ω·dinv of every level that can run the fused passes; allocated and filled outside any stream capture
-int mgs_prepare_fused(mgs_hier *h) {
-  mgs_ctx *ctx = h->ctx;
-  if (ctx->opt_rowcode)      // pattern codes of the level operators (a cache attached to the matrices)
-    for (mgs_level &L : h->lev)
-      if (!L.A->code_tried) { MGS_TRY(mgs_csr_optimize(const_cast<mgs_csr *>(L.A))); mgs_drop_graph(h); }
-  for (int l = h->kcycle_entry ? 0 : 1; l <= h->kcycle_levels && l < (int)h->lev.size() - 1; ++l) {
-    mgs_level &L = h->lev[l];
-    if (L.kscal) continue;
-    for (mgs_vec **q : {&L.kc1, &L.kv1, &L.kc2, &L.kv2, &L.kr}) MGS_TRY(mgs_vec_create(ctx, L.n_ext, q));
-    MGS_TRY(mgs_dev_alloc(ctx, &L.kscal, 8));
-    MGS_HIP(ctx, hipMemsetAsync(L.kscal, 0, 8 * sizeof(double), ctx->stream));      // defined before the first step (mgs_hier_kcycle_scalars)
-    mgs_drop_graph(h);
-  }
-  const bool sharded = h->halo || h->halo_begin || h->native;
-  if (!ctx->opt_fuse || h->nu1 != 1 || h->nu2 != 1 || (sharded && !h->halo_fused && !h->native)) return MGS_OK;
-  for (size_t l = 0; l + 1 < h->lev.size(); ++l) {
-    mgs_level &L = h->lev[l];
-    if (!L.T || !L.T->aggregation) continue;
-    if (L.A->rows != L.A->cols && !h->halo_fused && !L.nx) continue;
-    const bool shard = L.A->cols > L.A->rows;
-    if (!L.wd) MGS_TRY(mgs_vec_create(ctx, L.n_ext, &L.wd));
-    if (shard && !L.hbuf) MGS_TRY(mgs_vec_create(ctx, L.A->cols - L.A->rows, &L.hbuf));
-    if (shard && !L.halo_dinv) {
-      // one exchange at setup: the owners' D⁻¹ of the rows this shard sees as halo.  With it Â's halo columns are scaled like the
-      // owned ones, and what the pre pass needs from the peers per cycle is their raw right-hand side (no packed product).
-      // Collective: every rank prepares its hierarchy in its first cycle.
-      MGS_TRY(mgs_halo_exchange(h, (int)l, L.dinv->d, L.dinv->d + L.A->rows));
-      L.halo_dinv = true; L.wd_omega = 0.0; mgs_drop_graph(h);
-    }
-    if (shard && !L.cmap_ext && L.T->halo_cmap && L.T->n_halo_fine == L.A->cols - L.A->rows) {      // coarse column of every local column
-      MGS_TRY(mgs_dev_alloc(ctx, &L.cmap_ext, (size_t)L.A->cols));
-      MGS_TRY(k_concat_i32(ctx, L.T->agg, L.A->rows, L.T->halo_cmap, L.T->n_halo_fine, L.cmap_ext));
-      mgs_drop_graph(h);
-    }
-    if (shard && !L.cmap_ext) continue;      // shard not built by mgs_galerkin_shard: one kernel per step on this level
-    const bool rescale = L.wd_omega != h->omega;
-    if (rescale) { MGS_TRY(k_axpby(ctx, L.n_ext, h->omega, L.dinv->d, 0.0, L.wd->d)); L.wd_omega = h->omega; mgs_drop_graph(h); }
-    if (ctx->opt_fuse_operands) {      // derived CSR operands of the fused passes (same shape as A)
-      bool new_vals = false;
-      if (!L.val_wd) { MGS_TRY(mgs_dev_alloc(ctx, &L.val_wd, (size_t)L.A->nnz + 4)); MGS_TRY(k_scale_vals(ctx, L.A, L.wd->d, L.val_wd)); mgs_drop_graph(h); new_vals = true; }
-      else if (rescale) { MGS_TRY(k_scale_vals(ctx, L.A, L.wd->d, L.val_wd)); new_vals = true; }
-      if (new_vals) { L.nd_stale = true; if (L.pk_hat) L.pk_hat->stale = true; }
-      const int ncols_c = h->lev[l + 1].A->cols;      // coarse level's local columns: its rows + its halo slots
-      if (ctx->opt_merge_ap && !L.AP) {
-        MGS_TRY(k_build_ap(L.A, L.T, L.cmap_ext, ncols_c, &L.AP)); mgs_drop_graph(h);
-        L.AP->far_band = L.A->far_band; L.AP->far_band_max = L.A->far_band_max;     // sweep order of the launch: the band of A (AP's columns are coarse ids)
-        if (ctx->opt_rowcode)
-          MGS_TRY(mgs_build_rowcode(ctx, L.AP->rows, L.AP->rowptr, L.AP->col, L.T->agg, 0x7fffffff, &L.code_ap, ctx->opt_valcode ? L.AP->val : nullptr));
-      }
-      if (!ctx->opt_merge_ap && !L.col_agg) {
-        MGS_TRY(mgs_dev_alloc(ctx, &L.col_agg, (size_t)L.A->nnz + 4)); MGS_TRY(k_map_cols(ctx, L.A, L.cmap_ext ? L.cmap_ext : L.T->agg, L.col_agg)); mgs_drop_graph(h);
-        if (ctx->opt_rowcode)
-          MGS_TRY(mgs_build_rowcode(ctx, L.A->rows, L.A->rowptr, L.col_agg, L.T->agg, 0x7fffffff, &L.code_agg, ctx->opt_valcode ? L.A->val : nullptr));
-      }
-      if (ctx->opt_diag_from_values && !L.dpos && !ctx->opt_merge_ap) {
-        MGS_TRY(mgs_dev_alloc(ctx, &L.dpos, (size_t)L.A->rows)); MGS_TRY(k_diag_pos(L.A, L.dpos)); mgs_drop_graph(h);
-      }
-      if (ctx->opt_fuse_restrict && !L.grp_tried) {   // row-block groups of the grouped pre pass (null: level does not qualify)
-        L.grp_tried = true; MGS_TRY(mgs_build_groups(ctx, L.A, L.T, &L.grp)); mgs_drop_graph(h);
-      }
-      // codes whose tuples depend on Â's values (or, on a shard, on the halo tags) follow val_wd
-      if (new_vals && (L.code_pre || L.code_hat)) {     // whatever the options say NOW: a code built from the old Â must not survive it
-        mgs_free_rowcode(L.code_pre); L.code_pre = nullptr; mgs_free_rowcode(L.code_hat); L.code_hat = nullptr; mgs_drop_graph(h);
-      }
-      if (ctx->opt_rowcode && new_vals && (shard || ctx->opt_valcode)) {
-        mgs_drop_graph(h);
-        // on a shard the pre pass reads b (owned entries only) + the payload: halo columns need tagged table words
-        if (shard) MGS_TRY(mgs_build_rowcode(ctx, L.A->rows, L.A->rowptr, L.A->col, nullptr, L.A->rows, &L.code_pre, ctx->opt_valcode ? L.val_wd : nullptr));
-        else MGS_TRY(mgs_build_rowcode(ctx, L.A->rows, L.A->rowptr, L.A->col, nullptr, 0x7fffffff, &L.code_hat, L.val_wd));
-      }
-      MGS_TRY(level_refresh_f32(h, L, new_vals));      // FP32 copies follow their FP64 operands (a new ω rescales Â)
-    }
-  }
-  // Compact operand of the grouped pre pass (option pre_nodiag), allocated behind everything above: the other operands stay where the
-  // arena places them without it.  Eligibility is decided once per level; the values follow val_wd.
-  for (size_t l = 0; ctx->opt_fuse_operands && ctx->opt_pre_nodiag && l + 1 < h->lev.size(); ++l) {
-    mgs_level &L = h->lev[l];
-    if (!L.val_wd || !L.grp) continue;
-    if (!L.nd_tried) {
-      L.nd_tried = true;
-      int bad = 1;
-      if (L.A->cols == L.A->rows && !L.nx && L.A->max_row_len <= 64 && L.A->nnz >= L.A->rows) MGS_TRY(k_diag_count(L.A, &bad));
-      L.nd_ok = bad == 0;
-    }
-    if (!L.nd_ok) continue;
-    if (!L.val_nd) {
-      const size_t m = (size_t)(L.A->nnz - L.A->rows);
-      MGS_TRY(mgs_dev_alloc(ctx, &L.val_nd, m + 8));
-      MGS_HIP(ctx, hipMemsetAsync(L.val_nd + m, 0, 8 * sizeof(double), ctx->stream));
-      MGS_TRY(mgs_dev_alloc(ctx, &L.nd_code, (size_t)L.A->rows));
-      if (!h->nd_flag) MGS_TRY(mgs_dev_alloc(ctx, &h->nd_flag, 1));
-      L.nd_stale = true; mgs_drop_graph(h);
-    }
-    if (L.nd_stale) {      // values and the diagonal's bytes follow val_wd; a diagonal entry further from ω than a byte holds (1/a_ii under- or overflowed) ends it
-      int bad = 0;
-      MGS_HIP(ctx, hipMemsetAsync(h->nd_flag, 0, sizeof(int), ctx->stream));
-      MGS_TRY(k_drop_diag_vals(ctx, L.A, L.val_wd, L.wd_omega, L.val_nd, L.nd_code, h->nd_flag));
-      MGS_HIP(ctx, hipMemcpyAsync(&bad, h->nd_flag, sizeof bad, hipMemcpyDeviceToHost, ctx->stream));
-      MGS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      L.nd_omega = L.wd_omega; L.nd_stale = false;
-      if (bad) { L.nd_ok = false; mgs_drop_graph(h); }
-    }
-  }
-  // Packed copies of the operands' values (option pack7), allocated behind everything above for the same reason.  Unsharded FP64 levels with an
-  // aggregation transfer; the pre pass's copy is of val_nd where the level streams that, of val_wd otherwise; the values follow their sources.
-  for (size_t l = 0; ctx->opt_fuse_operands && ctx->opt_pack7 && !ctx->opt_valcode && l + 1 < h->lev.size(); ++l) {
-    mgs_level &L = h->lev[l];
-    if (!L.val_wd || !L.T || !L.T->aggregation || L.A->cols != L.A->rows || L.nx || !L.A->blkptr || L.op_bits != 64) continue;
-    MGS_TRY(level_pack7(h, L, false));
-  }
-  return MGS_OK;
-}
-
-extern "C" {
 
 // ------------------------------------------------------------------ instrumentation
 int mgs_time_kernel(const mgs_csr *A, int op, const mgs_vec *x, const mgs_vec *b, const mgs_vec *dinv, mgs_vec *out, int reps, double *ms) {

@@ -126,9 +126,10 @@ struct mgs_pack7 {
   int64_t nent = 0;                // entries of the source array
   int nblocks = 0;
   bool nd = false;                 // the source is the operand without diagonal entries (val_nd)
-  bool stale = true;               // the source array was rebuilt since
+  bool dirty = true;               // out of step with its source (the level's dirty bits, kept here because the launchers see the copy alone)
   int ran = -1;                    // the last launch that could have read it did (1) or did not (0); −1: none yet (mgs_hier_pack_info)
 };
+static inline bool mgs_pack7_serves(const mgs_pack7 *p, bool nd) { return p && !p->dirty && p->nd == nd; }      // a launch that streams val_nd (nd) or a whole operand may read this copy
 
 struct mgs_csr {
   mgs_ctx *ctx = nullptr;
@@ -285,7 +286,7 @@ struct mgs_level {
   mgs_rowcode *code_hat = nullptr;   // option valcode: pattern code of (col, val_wd) for the pre pass on Â
   // operand precision (mgs_hier_set_operand_precision): FP32 copies of the two setup-time operands' values, rounded to nearest from the
   // FP64 arrays above (which stay the source of truth and stay allocated: switching back is free and bit-identical)
-  int op_bits = 64;                  // what the level was switched to; whether a cycle really runs on the copies: mgs_level_runs_f32 (mgs_api.hip)
+  int op_bits = 64;                  // what the level was switched to; whether a cycle really runs on the copies: mgs_level_runs_f32 (hier_operands.hip)
   float *val_wd32 = nullptr;         // nnz + 8 floats
   float *ap_val32 = nullptr;         // nnz(A·P) + 8 floats
   unsigned char *dpos = nullptr;     // position of the diagonal entry inside each row (255: none / beyond 254), see mgs_csr::dpos
@@ -296,15 +297,21 @@ struct mgs_level {
   signed char *nd_code = nullptr;    // rows bytes: bit pattern of Â_ii minus bit pattern of nd_omega (a few units of the last place)
   double nd_omega = 0.0;             // ω that nd_code counts from
   bool nd_tried = false, nd_ok = false;   // eligibility, decided once: grouped, unsharded, every row holds exactly one diagonal entry
-  bool nd_stale = false;             // val_wd was rebuilt since val_nd was
   // option pack7: packed copies of the pre pass's operand (val_nd where the level streams it, val_wd otherwise) and of A·P's values
   mgs_pack7 *pk_hat = nullptr, *pk_ap = nullptr;
   mgs_vec *kc1 = nullptr, *kv1 = nullptr, *kc2 = nullptr, *kv2 = nullptr, *kr = nullptr;   // K-cycle work vectors
   double *kscal = nullptr;     // K-cycle scalars (device)
-  double wd_omega = 0.0;       // ω that wd was built with
+  unsigned dirty = ~0u;        // OPD_* bits: the derived operands that are out of step with their sources (or do not exist yet), see below
   mgs_vec *b = nullptr, *x = nullptr;  // coarse-level rhs / solution (levels >= 1)
   mgs_native_plan *nx = nullptr;       // native RCCL halo exchange of this level (row shards)
 };
+
+// The derived operands of a level's fused passes and the ONE record of "this array is out of step with its source" (hier_operands.hip allocates, fills and frees them).
+// The chain: wd = ω·D⁻¹ → val_wd = Â → val_nd + nd_code, val_wd32, the value-carrying codes; A → A·P → ap_val32; the packed copies follow val_nd / val_wd and A·P (their
+// bit is mgs_pack7::dirty).  A bit is set by mgs_operands_mark (new ω, new values, a freed array) and cleared by the one fill of its array: clear = exists and in step.
+enum : unsigned { OPD_WD = 1, OPD_HAT = 2, OPD_ND = 4, OPD_HAT32 = 8, OPD_CODES = 16, OPD_AP = 32, OPD_AP32 = 64, OPD_PACKS = 128 /* asks a fill for the packed copies */ };
+static inline bool mgs_operand_in_step(const mgs_level &L, unsigned bit) { return !(L.dirty & bit); }
+static inline bool mgs_level_nd_ready(const mgs_level &L) { return L.val_nd && L.nd_code && L.nd_ok && mgs_operand_in_step(L, OPD_ND); }      // the compact operand of the grouped pre pass can be streamed (and packed)
 
 struct mgs_hier {
   mgs_ctx *ctx = nullptr;
@@ -531,9 +538,13 @@ void mgs_free_reorder(struct mgs_reorder_plan *p);
 
 // helpers (mgs_api.hip)
 int mgs_csr_alloc(mgs_ctx *ctx, int rows, int cols, int64_t nnz, mgs_csr **out);
-int mgs_prepare_fused(mgs_hier *h);      // operands, work vectors and codes a hierarchy's cycle needs, built outside any stream capture
 void mgs_drop_graph(mgs_hier *h);        // the cached cycle graphs (whatever they recorded has changed)
+bool mgs_hier_sharded(const mgs_hier *h);   // row-sharded: halo callbacks, native plans or tail, a replaced coarse solve, or a level with halo columns
+int mgs_level_in_range(const mgs_hier *h, int level, const char *who);
+int mgs_prepare_fused(mgs_hier *h);      // (hier_operands.hip, as the three below) operands, work vectors and codes a hierarchy's cycle needs, built outside any stream capture
 bool mgs_level_runs_f32(const mgs_hier *h, int l);
+void mgs_operands_mark(mgs_level &L, unsigned bits); void mgs_operands_free(mgs_level &L);      // mark: these operands and everything derived from them are out of step
+int mgs_operands_fill(mgs_hier *h, int l, unsigned want);   // refills, in place, those of `want` that exist and are dirty
 // (cycle.hip) halo slots dst of a level-l vector (or payload buffer) from the owners' src, complete on the stream, through the hierarchy's ONE transport rule
 int mgs_halo_exchange(mgs_hier *h, int l, const double *src, double *dst, bool fused_pass = false);
 // (krylov.hip) the context's pool of work vectors for the other translation units: a vector of n entries, written before
