@@ -361,7 +361,18 @@ int mgs_vec_scatter(const mgs_vec *y, const void *idx_dev, int64_t n, int index_
  * and its number of entries; MGS_ERR_INVALID, naming the position: blocks that differ in any of these; also a NULL argument, a C that
  * mgs_csr_bmat did not build, a block of another context, a value-carrying pattern code on C (option "valcode").
  * mgs_csr_bmat_info — diagnostics: out[0] blocks that are not NULL, out[1] br, out[2] bc, out[3] longest row of C.  All four are 0 for
- * a matrix that mgs_csr_bmat did not build.  MGS_ERR_INVALID: NULL argument. */
+ * a matrix that mgs_csr_bmat did not build.  MGS_ERR_INVALID: NULL argument.
+ * mgs_csr_transpose_numeric — the values of At again, in place, from the current values of A, for an At whose pattern is the transpose
+ * of A's pattern (what mgs_csr_transpose(A) built) and an A whose values changed and whose pattern did not.  No map is kept and
+ * mgs_csr_transpose is unchanged: one entry-parallel launch over A's entries in which entry k finds its row i by bisection in A's
+ * rowptr, has column j, and finds its place by bisection of i in At's columns of row j.  The value moves as a 64-bit word (-0.0, NaN
+ * payloads); no atomics on values or places, places of distinct entries are distinct; the bits are those of a fresh mgs_csr_transpose.
+ * An entry whose place does not exist is counted and never written; nothing is ever written outside At's values.  No allocation; At's
+ * arrays do not move: follow with mgs_csr_bmat_numeric, mgs_csr_scale, mgs_csr_spgemm_numeric, ... and mgs_hier_refresh.
+ * mgs_csr_scale works in place: a transposed operand that was scaled holds unscaled values after the refill and is scaled again.
+ * misses == NULL: enqueued on the context's stream, no host wait.  misses given: the call synchronises and writes the number of entries
+ * without a place; MGS_ERR_STATE when it is not 0.  MGS_ERR_INVALID: a NULL handle; different contexts; an At that is not cols × rows
+ * of A; different entry counts; a value-carrying pattern code on At (option "valcode"). */
 #define MGS_BMAT_MAX_BLOCKS 256   /* most block positions (br·bc) one mgs_csr_bmat call takes */
 int mgs_csr_permute(const mgs_csr *A, const void *rperm_dev, const void *cperm_dev,
                     int index_bits, int keep_map, mgs_csr **C);
@@ -371,6 +382,7 @@ int mgs_csr_bmat(mgs_ctx *ctx, int br, int bc, const mgs_csr *const *blocks,
                  const int *row_sizes, const int *col_sizes, mgs_csr **C);
 int mgs_csr_bmat_numeric(mgs_csr *C, const mgs_csr *const *blocks);
 int mgs_csr_bmat_info(const mgs_csr *C, int64_t out[4]);
+int mgs_csr_transpose_numeric(const mgs_csr *A, mgs_csr *At, int64_t *misses);
 
 /* -------------------------------------------------------------------- device vectors */
 /* Eigen::VectorXd on the device (bicg.cpp:153-162).                                    */
@@ -802,6 +814,64 @@ int mgs_fgcr_plan_solve(mgs_fgcr_plan *p, mgs_vec *x, const mgs_vec *b, int ahea
 int mgs_fgcr_plan_enqueue(mgs_fgcr_plan *p, mgs_vec *x, const mgs_vec *b, int iters, double tol);
 int mgs_fgcr_plan_result(mgs_fgcr_plan *p, int *iters_done, double *resid, double *recursive_resid, int *status);
 int mgs_fgcr_plan_info(const mgs_fgcr_plan *p, int64_t out[6]);
+
+/* ------------------------------------- MINRES with device-resident scalars: enqueue-only solves, one host look per iteration */
+/* Nearest reference line: src/CPU_Matlab/solve.m:28-33; the reference has neither MINRES nor an asynchronous form.  mgs_minres forms δ, the Lanczos
+ * coefficients, the Givens rotation and the stopping estimate on the host: two host looks per iteration (q·z̃ and γn² = z̃_new·v_new), each one
+ * draining the queue behind it, and the call cannot return before the solve is over.  A plan keeps those scalars in one state block in device
+ * memory (normb, γ, γ_prev, η, κ, δ, s0, s1, c0, c1; the coefficients of the two vector passes; resid = the estimate κ·|η|/‖b‖, after INIT the
+ * initial true residual; true_resid; flags it, status (−1 running), frozen, why (the estimate fell below tol / γn == 0), wasted, apply).
+ * One-wave scalar-step kernels form every scalar with the operations, in the order, of mgs_minres's host code; the Lanczos pass reads
+ * (a, b, c) from the state block and evaluates axpbypcz's expression a·q + b·v + c·v_prev with its 16-byte and 8-byte arms, grids and store hint;
+ * the update pass reads (1/γ, a3, a2, a1, step) and evaluates the expression of mgs_minres's own pass with its two arms, launch decisions and
+ * option "minres_nt"; everything else is the very launches mgs_minres makes — so every bit of x agrees with mgs_minres's.  One iteration j is a
+ * fixed launch sequence, (v, z̃) and (w, w_prev) alternating by the parity of j:
+ *   SpMV     q = A·z̃ with q·z̃ from the same pass
+ *   LANCZOS  δ = (q·z̃)/(γ·γ); a = 1/γ, b = −(δ/γ), c = −(γ/γ_prev)
+ *   pass     v_new = a·q + b·v + c·v_prev over v_prev
+ *   cycle    z̃_new = M·v_new (a copy when h is NULL)
+ *   dot      γn² = z̃_new·v_new
+ *   ROTATE   γn² negative or not a number: frozen, status 2; a0 .. a3 as in mgs_minres; a1 == 0: frozen, status 3, x not updated; cn = a0/a1,
+ *            sn = γn/a1, step = cn·η, apply = 1; η ← −sn·η; the rotation; est = κ·|η|/‖b‖; est < tol or γn == 0: frozen, status 0, why; the post
+ *   pass     apply: w_new = ((1/γ)·z̃ − a3·w_prev − a2·w)/a1 over w_prev, x ← x + step·w_new
+ * The iteration that freezes as converged still applies its update, as mgs_minres updates x before it tests: the update pass is predicated on
+ * `apply`, which the next LANCZOS step clears, not on `frozen`.  Once `frozen` is set, the scalar steps do nothing (LANCZOS counts into
+ * `wasted`) and the two passes return at once; SpMV, cycle and folds still run.  That is not only scratch here: a frozen iteration's cycle
+ * rewrites a z̃ from its unchanged v, and every second one rewrites the live z̃ — with the same bits, because the cycle is deterministic.
+ * INIT is mgs_minres's start: ‖b‖, 0 replaced by 1; v = b − A·x; resid <= tol: frozen, status 0, iteration 0; z̃ = M·v; g2 = z̃·v, status 2
+ * unless g2 > 0; γ = √g2, γ_prev = 1, η = γ, κ = resid·‖b‖/γ; v_prev = w_prev = w = 0.
+ *   create: borrows A and h (may be NULL); both must outlive the plan.  mgs_minres's acceptance rules: nu1 == nu2, no K-cycle and no K-cycle
+ *     entry, no declared null space on A or on h's fine operator; the additive form, a correction scale and FP32 operands are allowed.  Runs
+ *     mgs_csr_optimize(A); allocates v ×2, z̃ ×2, q, w ×2 and the state block (inside the arena when one exists; not from the work-vector
+ *     pool), a ring of 1024 posted results of 64 bytes in mapped host memory, the partial-sum buffer, and runs one cycle on each (v[k], z̃[k])
+ *     pair with ones, so that the hierarchy's operands exist and both cycles are captured: two cached graphs for the life of the plan, and
+ *     no later call allocates.
+ *   solve: mgs_minres's contract and bits for every ahead >= 0 (clamped to 1022): statuses 0/1/2/3, *max_iter = the iterations done (for
+ *     statuses 2 and 3 the iteration that stopped), *tol = the TRUE relative residual on every path.  The host looks once per iteration,
+ *     BEHIND the queue: iteration k is not enqueued before the post of iteration k − 1 − ahead has been seen, and never beyond *max_iter.  On
+ *     a posted freeze with status 0 the host forms the true residual into q (a synchronising look, as in mgs_minres): below tol → 0; γn == 0
+ *     → 3; at *max_iter → 1; otherwise it enqueues the recalibration step (κ = resid·‖b‖/|η| with the true residual passed by value, frozen
+ *     cleared) and enqueues again the iterations that ran frozen.  The recurrence is never restarted.  On statuses 2 and 3 and when the
+ *     iterations are used up it forms the true residual before it returns.
+ *   enqueue: no host wait at all.  INIT, `iters` iterations, then FINAL: the true residual b − A·x into q and the status: 0 only if the solve
+ *     froze on its estimate or on γn == 0 AND the true residual is below tol (`<=` at iteration 0); 3 for γn == 0 above tol; 2 or 3 as found;
+ *     else 1.  THERE IS NO RECALIBRATION ON THE DEVICE: status 1 with iters_done < iters means the estimate ran ahead of the 2-norm — enqueue
+ *     again from x, which measures κ afresh.  tol = 0 runs exactly `iters` iterations.  x and b must stay alive and untouched until the result
+ *     is read or the stream is synchronised.
+ *   result (synchronises): of the last enqueue: *iters_done = where the solve froze, or iters; *resid = the true relative residual;
+ *     *recursive_resid (may be NULL) = the estimate; *status.  After a solve: what that solve returned.
+ *   info: out = device bytes held, solves + enqueues so far, iterations enqueued by the last call, of those the iterations that ran frozen
+ *     (known after solve / result), host waits the last call made, recalibrations in the last call.
+ * MGS_ERR_INVALID, with a message headed mgs_minres_plan_*: a NULL argument; a matrix without rows; a row shard (the criteria of
+ * mgs_pcg_plan_create); a hierarchy that is not a fixed symmetric operator; a declared null space; vectors shorter than A's rows; x aliasing
+ * b; ahead < 0; iters < 0.  MGS_ERR_STATE: the context's stream is being captured. */
+typedef struct mgs_minres_plan mgs_minres_plan;
+int mgs_minres_plan_create(const mgs_csr *A, mgs_hier *h, mgs_minres_plan **out);
+int mgs_minres_plan_destroy(mgs_minres_plan *p);
+int mgs_minres_plan_solve(mgs_minres_plan *p, mgs_vec *x, const mgs_vec *b, int ahead, int *max_iter, double *tol, int *status);
+int mgs_minres_plan_enqueue(mgs_minres_plan *p, mgs_vec *x, const mgs_vec *b, int iters, double tol);
+int mgs_minres_plan_result(mgs_minres_plan *p, int *iters_done, double *resid, double *recursive_resid, int *status);
+int mgs_minres_plan_info(const mgs_minres_plan *p, int64_t out[6]);
 
 /* ------------------------------------- projected initial guesses for successive right-hand sides */
 /* Nearest reference line: none: the reference solves one right-hand side, bicg.cpp:159-166.  A caller who solves with the same operator again and

@@ -108,6 +108,7 @@ PROTOTYPES = {
     "mgs_csr_bmat": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_void_p)]),
     "mgs_csr_bmat_numeric": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "mgs_csr_bmat_info": (C.c_int, [C.c_void_p, c_i64_p]),
+    "mgs_csr_transpose_numeric": (C.c_int, [C.c_void_p, C.c_void_p, c_i64_p]),
     "mgs_vec_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, c_i64_p]),
     "mgs_vec_scatter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, c_i64_p]),
     "mgs_vec_create": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]),
@@ -175,6 +176,12 @@ PROTOTYPES = {
     "mgs_fgcr_plan_enqueue": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double]),
     "mgs_fgcr_plan_result": (C.c_int, [C.c_void_p, c_int_p, c_dbl_p, c_dbl_p, c_int_p]),
     "mgs_fgcr_plan_info": (C.c_int, [C.c_void_p, c_i64_p]),
+    "mgs_minres_plan_create": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "mgs_minres_plan_destroy": (C.c_int, [C.c_void_p]),
+    "mgs_minres_plan_solve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, c_int_p, c_dbl_p, c_int_p]),
+    "mgs_minres_plan_enqueue": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double]),
+    "mgs_minres_plan_result": (C.c_int, [C.c_void_p, c_int_p, c_dbl_p, c_dbl_p, c_int_p]),
+    "mgs_minres_plan_info": (C.c_int, [C.c_void_p, c_i64_p]),
     "mgs_guess_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "mgs_guess_destroy": (C.c_int, [C.c_void_p]),
     "mgs_guess_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_dbl_p]),

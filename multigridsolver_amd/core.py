@@ -307,6 +307,21 @@ class Csr:
     def transpose(self):
         h = C.c_void_p(); check(lib().mgs_csr_transpose(self.h, C.byref(h)), self.ctx.h); return Csr(self.ctx, h)
 
+    def transpose_update(self, A, check=False):
+        """this matrix = A.transpose() built earlier: its values again, in place, from the current values of A with its pattern unchanged
+        (mgs_csr_transpose_numeric; one launch, no kept map); returns self.  check=False: enqueued, no host wait.  check=True: synchronises
+        and raises MgsError (MGS_ERR_STATE, .misses set) when entries of A have no place here (another pattern).  A scaling applied to
+        this matrix (scale) is gone after the refill: apply it again.  Follow with Hierarchy.refresh()."""
+        if not check:
+            _check(lib().mgs_csr_transpose_numeric(A.h, self.h, None), A.ctx.h); return self      # the call reports on A's context
+        m = C.c_int64(-1)
+        try:
+            _check(lib().mgs_csr_transpose_numeric(A.h, self.h, C.byref(m)), A.ctx.h)
+        except MgsError as e:
+            e.misses = int(m.value)
+            raise
+        return self
+
     def galerkin(self, xfer):
         h = C.c_void_p(); check(lib().mgs_csr_galerkin(self.h, xfer.h, C.byref(h)), self.ctx.h); return Csr(self.ctx, h)
 
@@ -1033,6 +1048,38 @@ class FgcrPlan(_KrylovPlan):
 
     def info(self):
         """[0] device bytes, [1] solves + enqueues, [2] iterations enqueued by the last call, [3] of those run frozen, [4] host waits, [5] restarts from the true residual"""
+        return super().info()
+
+
+class MinresPlan(_KrylovPlan):
+    """Preconditioned MINRES with device-resident scalars (mgs_minres_plan, include/mgs.h): mgs_minres's arithmetic and bits, with one host look
+    per iteration `ahead` iterations behind the queue (solve), or none at all (enqueue, then result).  hier: V(ν, ν), no K-cycle, no declared
+    null space.  A and hier must outlive the plan (they are kept referenced here)."""
+    _prefix = "minres"
+
+    def __init__(self, A, hier=None):
+        self.ctx, self.A, self.hier = A.ctx, A, hier
+        h = C.c_void_p()
+        check(lib().mgs_minres_plan_create(A.h, hier.h if hier else None, C.byref(h)), A.ctx.h)
+        self.h = h
+
+    def solve(self, x, b, max_iter=10000, tol=1e-6, ahead=1):
+        """mgs_minres's contract → (status, iterations, true relative residual), the tuple minres() returns.  ahead = 1 as for the PCG and
+        BiCGSTAB plans: against 0 it is 5 % faster where an iteration takes 0.36 ms and 0.8 % slower where it takes 2.3 ms (profiles/r23_minres_plan.md)"""
+        return super().solve(x, b, max_iter, tol, ahead)
+
+    def enqueue(self, x, b, iters, tol):
+        """INIT, `iters` iterations and the final true residual on the context's stream; no host wait.  x and b are kept referenced until
+        result().  There is no recalibration on the device: status 1 with fewer iterations done than asked for means the estimate ran
+        ahead of the 2-norm; enqueue again from x"""
+        return super().enqueue(x, b, iters, tol)
+
+    def result(self, recursive=False):
+        """of the last enqueue (synchronises) → (status, iterations done, true relative residual); recursive=True appends the estimate κ·|η|/‖b‖"""
+        return super().result(recursive)
+
+    def info(self):
+        """[0] device bytes, [1] solves + enqueues, [2] iterations enqueued by the last call, [3] of those run frozen, [4] host waits, [5] recalibrations"""
         return super().info()
 
 

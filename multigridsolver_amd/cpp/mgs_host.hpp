@@ -266,6 +266,16 @@ class DeviceMatrix {
     std::vector<const mgs_csr *> h = handles(br, bc, blocks);
     check(mgs_csr_bmat_numeric(a_.get(), h.data()), context());
   }
+  // The transpose, materialised row-major (mgs.h: mgs_csr_transpose; bicg.cpp:32).  transposeUpdate: this matrix is A.transpose() built
+  // earlier — its values again, in place, from the current values of A with its pattern unchanged (mgs_csr_transpose_numeric; one
+  // launch, no kept map).  Without `misses` the call is enqueued only; with it the call synchronises, writes the number of entries of A
+  // without a place here and throws Error(MGS_ERR_STATE) when that is not 0.  A scale() applied to this matrix is applied again afterwards.
+  DeviceMatrix transpose() const {
+    mgs_csr *p = nullptr;
+    check(mgs_csr_transpose(a_.get(), &p), context());
+    return adopt(p, cols_, rows_);
+  }
+  void transposeUpdate(const DeviceMatrix &A, int64_t *misses = nullptr) { check(mgs_csr_transpose_numeric(A.a_.get(), a_.get(), misses), context()); }
   Vector operator*(const Vector &x) const {            // bicg.cpp:57,82,107,117
     Vector y(rows_); check(mgs_spmv(a_.get(), x.handle(), y.out()), context()); return y;
   }
@@ -614,6 +624,41 @@ class FgcrPlan {
   }
   int64_t info(int i) const { int64_t o[6]; check(mgs_fgcr_plan_info(p_.get(), o), context()); return o[i]; }
   mgs_fgcr_plan *handle() const { return p_.get(); }
+};
+
+// ---------------------------------------------------------------- MINRES with device-resident scalars (mgs.h: mgs_minres_plan)
+// The reference has no MINRES (nearest line: src/CPU_Matlab/solve.m:28-33) and no asynchronous form.  mgs_minres's arithmetic and bits — symmetric
+// indefinite systems with a V(nu, nu) preconditioner — with one host look per iteration instead of two (solve), or none at all (enqueue + result):
+//   D.update_values_coo(v, nt);  Dt.transposeUpdate(D);  K.bmatUpdate(2, 2, blocks);  M.refresh();  plan.enqueue(x, b, iters, tol);  plan.result(it, resid);
+// There is no recalibration on the device: result() == 1 with it < iters means the estimate ran ahead of the 2-norm; enqueue again from x.
+// The plan keeps the DeviceMatrix and the preconditioner alive.  x and b must stay alive until result() (or a synchronisation).
+class MinresPlan {
+  DeviceMatrix A_;
+  MultiGridPrecond M_;
+  std::shared_ptr<mgs_minres_plan> p_;
+ public:
+  MinresPlan(const DeviceMatrix &A, const MultiGridPrecond &M) : A_(A), M_(M) {
+    mgs_minres_plan *p = nullptr;
+    check(mgs_minres_plan_create(A.handle(), M.use_preconditioner() ? M.handle() : nullptr, &p), context());
+    p_ = std::shared_ptr<mgs_minres_plan>(p, [](mgs_minres_plan *q) { mgs_minres_plan_destroy(q); });
+  }
+  // mgs_minres's contract: returns the status, max_iter and tol (the true relative residual) are written back; `ahead` iterations stay enqueued
+  // beyond the last outcome seen
+  int solve(Vector &x, const Vector &b, int &max_iter, double &tol, int ahead = 1) {
+    int status = -1;
+    check(mgs_minres_plan_solve(p_.get(), x.out(), b.handle(), ahead, &max_iter, &tol, &status), context());
+    return status;
+  }
+  // INIT, `iters` iterations and the final true residual, enqueued; no host wait
+  void enqueue(Vector &x, const Vector &b, int iters, double tol) { check(mgs_minres_plan_enqueue(p_.get(), x.out(), b.handle(), iters, tol), context()); }
+  // of the last enqueue (synchronises): returns the status; iterations done, the true relative residual and (optionally) the estimate
+  int result(int &iters_done, double &resid, double *recursive_resid = nullptr) {
+    int status = -1;
+    check(mgs_minres_plan_result(p_.get(), &iters_done, &resid, recursive_resid, &status), context());
+    return status;
+  }
+  int64_t info(int i) const { int64_t o[6]; check(mgs_minres_plan_info(p_.get(), o), context()); return o[i]; }
+  mgs_minres_plan *handle() const { return p_.get(); }
 };
 
 // ---------------------------------------------------------------- TicToc.cpp:18-53

@@ -474,6 +474,7 @@ int mgs_csr_bmat(mgs_ctx *ctx, int br, int bc, const mgs_csr *const *blocks, con
   return k_csr_bmat(ctx, br, bc, blocks, row_sizes, col_sizes, C);
 }
 int mgs_csr_bmat_numeric(mgs_csr *C, const mgs_csr *const *blocks) { return k_csr_bmat_numeric(C, blocks); }
+int mgs_csr_transpose_numeric(const mgs_csr *A, mgs_csr *At, int64_t *misses) { return k_csr_transpose_numeric(A, At, misses); }
 int mgs_csr_bmat_info(const mgs_csr *C, int64_t out[4]) { return k_csr_bmat_info(C, out); }
 int mgs_vec_gather(const mgs_vec *x, const void *idx_dev, int64_t n, int index_bits, mgs_vec *y, int64_t *bad) { return k_vec_gather(x, idx_dev, n, index_bits, y, bad); }
 int mgs_vec_scatter(const mgs_vec *y, const void *idx_dev, int64_t n, int index_bits, mgs_vec *x, int64_t *bad) { return k_vec_scatter(y, idx_dev, n, index_bits, x, bad); }

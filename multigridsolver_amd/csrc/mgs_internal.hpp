@@ -533,6 +533,7 @@ int k_csr_permute_numeric(const mgs_csr *A, mgs_csr *C);
 int k_csr_permute_info(const mgs_csr *C, int64_t out[4]);
 int k_csr_bmat(mgs_ctx *ctx, int br, int bc, const mgs_csr *const *blocks, const int *row_sizes, const int *col_sizes, mgs_csr **out);
 int k_csr_bmat_numeric(mgs_csr *C, const mgs_csr *const *blocks);
+int k_csr_transpose_numeric(const mgs_csr *A, mgs_csr *At, int64_t *misses);
 int k_csr_bmat_info(const mgs_csr *C, int64_t out[4]);
 void mgs_free_reorder(struct mgs_reorder_plan *p);
 

@@ -25,6 +25,9 @@
 // block rows) written to device memory → one lane per output row sums its blocks' row lengths → scan → entry-parallel fill: an output
 // entry finds its row by bisection in C's rowptr, its block row by bisection in the row offsets, its block by walking the row's
 // per-block lengths, its source position from that block's rowptr.  The values-only pass is the same kernel without the column store.
+//
+// Transpose, values again (mgs_csr_transpose_numeric): one entry-parallel launch over A's entries, two bisections per entry, no kept map;
+// places of distinct entries are distinct, so there are no atomics on values or places (the miss counter alone is one).
 #include <cstring>
 #include <vector>
 #include "mgs_internal.hpp"
@@ -198,6 +201,35 @@ __global__ void perm_numeric_kernel(long long nnz, long long a_nnz, const int *_
   if (k >= nnz) return;
   const int p = src[k];
   if (p >= 0 && p < a_nnz) cval[k] = av[p];      // always: the map was written by the fill pass of a source with a_nnz entries
+}
+
+// ------------------------------------------------------------------ transpose: values again
+// Entry k of A = (i, j, v): i by bisection in A's rowptr (the rule of scale_kernel), its place in At by bisection of i in At's columns of row
+// j (mgs_csr_transpose leaves them ascending).  No place (another pattern): counted, nothing written.  Every index is compared with its
+// bounds before it is an address; the only store is tval[p] with t_rp[j] ≤ p < t_rp[j + 1] ≤ nnz.
+__global__ void transpose_numeric_kernel(long long nnz, int rows, int t_rows, const int *__restrict__ arp, const int *__restrict__ aci, const u64 *__restrict__ av,
+                                         const int *__restrict__ trp, const int *__restrict__ tci, u64 *__restrict__ tval, u64 *__restrict__ miss) {
+  const long long k = (long long)blockIdx.x * TB + threadIdx.x;
+  if (k >= nnz) return;
+  int lo = 0, hi = rows;      // the entry's row: the last i with arp[i] ≤ k (empty rows share their successor's start and are passed over)
+  while (hi - lo > 1) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if ((long long)arp[mid] <= k) lo = mid; else hi = mid;
+  }
+  const int i = lo, j = aci[k];
+  bool placed = false;
+  if (j >= 0 && j < t_rows) {
+    const int b = trp[j], e = trp[j + 1];
+    if (b >= 0 && b <= e && (long long)e <= nnz) {      // always: At's rowptr is a scan over nnz entries
+      int p = b, q = e;      // the first p in [b, e) with tci[p] ≥ i
+      while (p < q) {
+        const int mid = p + ((q - p) >> 1);
+        if (tci[mid] < i) p = mid + 1; else q = mid;
+      }
+      if (p < e && tci[p] == i) { tval[p] = av[k]; placed = true; }
+    }
+  }
+  if (!placed && miss) atomicAdd(miss, 1ull);
 }
 
 void perm_message(mgs_ctx *ctx, const char *who, const char *list, const char *kind, const void *dev, int bits, u64 word, int n, const unsigned *inv) {
@@ -439,6 +471,38 @@ int k_csr_permute_numeric(const mgs_csr *A, mgs_csr *C) {
   MGS_CHECK(ctx, !(C->code && C->code->vtab), MGS_ERR_INVALID, "%s: C carries a value-carrying pattern code (option valcode): permute the matrix again instead", who);
   if (C->nnz) hipLaunchKernelGGL(perm_numeric_kernel, dim3(mgs_grid(C->nnz, TB)), dim3(TB), 0, ctx->stream, (long long)C->nnz, (long long)A->nnz, pl->src, (const u64 *)A->val, (u64 *)C->val);
   MGS_HIP(ctx, hipGetLastError());
+  return MGS_OK;
+}
+
+int k_csr_transpose_numeric(const mgs_csr *A, mgs_csr *At, int64_t *misses) {
+  const char *who = "mgs_csr_transpose_numeric";
+  MGS_CHECK(A ? A->ctx : (At ? At->ctx : nullptr), A && At, MGS_ERR_INVALID, "%s: NULL argument", who);
+  mgs_ctx *ctx = A->ctx;
+  MGS_CHECK(ctx, At->ctx == ctx, MGS_ERR_INVALID, "%s: At belongs to a different context", who);
+  MGS_CHECK(ctx, At->rows == A->cols && At->cols == A->rows, MGS_ERR_INVALID, "%s: A is %d x %d, At is %d x %d, not %d x %d", who, A->rows, A->cols, At->rows, At->cols, A->cols,
+            A->rows);
+  MGS_CHECK(ctx, At->nnz == A->nnz, MGS_ERR_INVALID, "%s: A holds %lld entries, At holds %lld", who, (long long)A->nnz, (long long)At->nnz);
+  MGS_CHECK(ctx, !(At->code && At->code->vtab), MGS_ERR_INVALID, "%s: At carries a value-carrying pattern code (option valcode): transpose the matrix again instead", who);
+  if (misses) *misses = 0;
+  if (!A->nnz || !A->rows) return MGS_OK;
+  DevBuf miss;
+  if (misses) {
+    MGS_TRY(dalloc<u64>(ctx, miss, 1));
+    MGS_HIP(ctx, hipMemsetAsync(miss.p, 0, sizeof(u64), ctx->stream));
+  }
+  SyncUnlessDone guard{ctx->stream};
+  guard.done = !misses;      // nothing to release behind an enqueue-only call
+  hipLaunchKernelGGL(transpose_numeric_kernel, dim3(mgs_grid(A->nnz, TB)), dim3(TB), 0, ctx->stream, (long long)A->nnz, A->rows, At->rows, A->rowptr, A->col, (const u64 *)A->val,
+                     At->rowptr, At->col, (u64 *)At->val, miss.as<u64>());
+  MGS_HIP(ctx, hipGetLastError());
+  if (!misses) return MGS_OK;
+  u64 h = 0;
+  MGS_HIP(ctx, hipMemcpyAsync(&h, miss.p, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+  MGS_TRY(finish(ctx, who));
+  guard.done = true;
+  *misses = (int64_t)h;
+  MGS_CHECK(ctx, h == 0, MGS_ERR_STATE, "%s: %llu of A's %lld entries have no place in At: its pattern is not the transpose of A's (nothing was written for them)", who, h,
+            (long long)A->nnz);
   return MGS_OK;
 }
 

@@ -25,7 +25,7 @@ def main(argv=None):
     ap.add_argument("--tol", type=float, default=1e-6)           # bicg.cpp:148
     ap.add_argument("--max-iter", type=int, default=10000)       # bicg.cpp:164
     ap.add_argument("--solver", choices=["bicgstab", "fgcr", "pcg", "minres"], default=None,
-                    help="default: bicgstab; minres: symmetric indefinite systems with a V(nu, nu) preconditioner, single GPU only")
+                    help="default: bicgstab; minres: symmetric indefinite systems with a V(nu, nu) preconditioner, single GPU only (its plan: --minres-ahead)")
     ap.add_argument("--pcg-flexible", action="store_true", help="--solver pcg: flexible β, for a preconditioner that is not a fixed symmetric operator (--nu1 != --nu2, --kcycle)")
     ap.add_argument("--ahead", type=int, default=None, metavar="N",
                     help="--solver pcg or --solver bicgstab, named on the command line: solve through a PcgPlan resp. BicgstabPlan (scalars stay on the "
@@ -36,6 +36,9 @@ def main(argv=None):
                     help="--solver fgcr: solve through an FgcrPlan (coefficients stay on the device, one host look per iteration) that keeps N iterations "
                          "enqueued beyond the last outcome seen; same result as without the flag; single GPU only")
     ap.add_argument("--kcycle-energy", action="store_true", help="K-cycle coefficients from energy inner products (flexible-CG form; symmetric positive definite operators only)")
+    ap.add_argument("--minres-ahead", type=int, default=None, metavar="N",
+                    help="--solver minres: solve through a MinresPlan (scalars stay on the device, one host look per iteration instead of two) that keeps N "
+                         "iterations enqueued beyond the last outcome seen; same result as without the flag; single GPU only")
     ap.add_argument("--omega", type=float, default=0.6)
     ap.add_argument("--nu1", type=int, default=1)
     ap.add_argument("--nu2", type=int, default=1)
@@ -57,9 +60,11 @@ def main(argv=None):
     if args.ahead is not None and (args.solver not in ("pcg", "bicgstab") or world > 1 or args.ahead < 0):
         raise SystemExit("--ahead N (N >= 0) goes with --solver pcg or --solver bicgstab, named explicitly, on a single GPU")
     if args.solver == "minres" and (args.ahead is not None or world > 1):
-        raise SystemExit("--solver minres runs on a single GPU and has no plan (--ahead goes with --solver pcg or --solver bicgstab)")
+        raise SystemExit("--solver minres runs on a single GPU; its plan is chosen with --minres-ahead N (--ahead goes with --solver pcg or --solver bicgstab)")
     if args.fgcr_ahead is not None and (args.solver != "fgcr" or world > 1 or args.fgcr_ahead < 0):
         raise SystemExit("--fgcr-ahead N (N >= 0) goes with --solver fgcr on a single GPU")
+    if args.minres_ahead is not None and (args.solver != "minres" or world > 1 or args.minres_ahead < 0):
+        raise SystemExit("--minres-ahead N (N >= 0) goes with --solver minres on a single GPU")
     if args.solver is None:
         args.solver = "bicgstab"
     if world > 1:
@@ -90,9 +95,12 @@ def main(argv=None):
             plan = mg.PcgPlan(A, h, args.pcg_flexible) if args.solver == "pcg" else mg.BicgstabPlan(A, h)
         if args.fgcr_ahead is not None:
             plan = mg.FgcrPlan(A, h, 10)
+        if args.minres_ahead is not None:
+            plan = mg.MinresPlan(A, h)
         ctx.sync(); t0 = time.perf_counter()
         if plan is not None:
-            st, it, tol = plan.solve(x, b, args.max_iter, args.tol, args.ahead if args.fgcr_ahead is None else args.fgcr_ahead)
+            ahead = next(a for a in (args.ahead, args.fgcr_ahead, args.minres_ahead) if a is not None)
+            st, it, tol = plan.solve(x, b, args.max_iter, args.tol, ahead)
         elif args.solver == "pcg":
             st, it, tol = mg.pcg(A, x, b, h, args.max_iter, args.tol, args.pcg_flexible)
         elif args.solver == "minres":
