@@ -166,6 +166,34 @@ int mgs_csr_coo_info(const mgs_csr *A, int64_t out[4]);
 int mgs_csr_set_nullspace(mgs_csr *A, int kind);
 int mgs_csr_nullspace(const mgs_csr *A, int *kind);
 int mgs_csr_nullspace_defect(const mgs_csr *A, double out[2]);
+/* ---- field-wise constant null space (enclosed Stokes / Darcy flow, graph Laplacians with several components) ----
+ * MGS_NULLSPACE_FIELDS: the declared null space is the span of up to MGS_NULLSPACE_MAX_FIELDS indicator vectors z_f of disjoint row sets
+ * ("fields").  labels_dev: A->rows entries of index_bits (32 or 64) bits in DEVICE memory; a label f in [0, nfields) puts the row in field f,
+ * −1 puts it in no field; the numbering may be interleaved.  The declaration asserts A·z_f = 0 and z_fᵀ·A = 0 for every field — the pressure
+ * constant of K = [[L, Dᵀ], [D, −C]] with velocity prescribed on the whole boundary, one constant per connected component of a graph
+ * Laplacian.  Like the constant kind it is the caller's responsibility and is NOT verified; mgs_csr_nullspace_defect is the net (on a fields
+ * matrix: the maximum over the fields of ‖A·z_f‖∞ / ‖|A|·z_f‖∞, and the same for Aᵀ; one SpMV per field and side).  Nearest reference line:
+ * none (bicg.cpp:35-36 fails on such a matrix).
+ * The labels are range-checked on the device before anything uses them (64-bit entries are compared as 64-bit values: 2³² does not alias 0),
+ * narrowed into an int8 array the matrix owns (mgs_csr_destroy frees it, and so does a later mgs_csr_set_nullspace(A, MGS_NULLSPACE_NONE)),
+ * and counted per field on the host side.  The call synchronises.  This kind is entered through this call only: mgs_csr_set_nullspace(A, 2)
+ * stays MGS_ERR_INVALID.  mgs_csr_nullspace reports MGS_NULLSPACE_FIELDS.
+ * MGS_ERR_INVALID, the matrix keeping the declaration it had: a NULL argument; index_bits neither 32 nor 64; nfields outside
+ * 1..MGS_NULLSPACE_MAX_FIELDS; a matrix that is not square; a row shard; a label outside [−1, nfields) (the lowest offending row and its
+ * value are named); a field without rows (named).
+ * What acts on the declaration:
+ *   - mgs_hier_finalize / mgs_hier_refresh: see there (coarse labels from the aggregation, A_c + Σ_f (s/n_cf)·z_cf·z_cfᵀ at the coarsest level).
+ *   - mgs_minres, mgs_minres_plan_* and mgs_pcg solve A·x = Πb with Π = I − Σ_f z_f·z_fᵀ/n_f and return the x whose fields have zero mean.
+ *     When A carries fields, the hierarchy's fine operator must carry MGS_NULLSPACE_FIELDS with the same nfields and the same per-field
+ *     counts; that the two label ARRAYS agree is the caller's responsibility (the projections read A's, the coarsest solve follows h's).
+ *   - every other solver (mgs_bicgstab, mgs_fgcr, mgs_pcg_plan_*, mgs_bicgstab_plan_*, mgs_fgcr_plan_*, mgs_guess_*) refuses the kind with
+ *     MGS_ERR_INVALID and a message naming mgs_minres / mgs_pcg.
+ * mgs_csr_nullspace_fields: *nfields (0 when the matrix carries another kind) and the rows of every field (0 beyond nfields).
+ * MGS_ERR_INVALID: NULL argument. */
+#define MGS_NULLSPACE_FIELDS 2
+#define MGS_NULLSPACE_MAX_FIELDS 8
+int mgs_csr_set_nullspace_fields(mgs_csr *A, const void *labels_dev, int index_bits, int nfields);
+int mgs_csr_nullspace_fields(const mgs_csr *A, int *nfields, int64_t counts[MGS_NULLSPACE_MAX_FIELDS]);
 /* Synthetic operator generated on device: 7-point 3-D Poisson on an
  * N^3 grid, 3-D extension of src/common/poisson.cpp:11-33 (diag 6, off-diagonals −1,
  * row e=(i*N+j)*N+k, ascending columns).  Rows of planes [plane_lo, plane_hi) only
@@ -442,6 +470,16 @@ int mgs_axpbypcz(double a, const mgs_vec *x, double b, const mgs_vec *y, double 
  * shift pass — so the result is bit-reproducible from run to run; 16-byte accesses when v is 16-byte aligned.  mean (may be NULL): the m that was subtracted, read back; nrm2 (may be NULL): ‖v − m‖₂ from the shift pass.  Synchronises when
  * either is asked for.  MGS_ERR_INVALID: v NULL. */
 int mgs_vec_project_const(mgs_vec *v, double *mean, double *nrm2);
+/* v ← Πv, Π = I − Σ_f z_f·z_fᵀ/n_f with the fields A declared (mgs_csr_set_nullspace_fields): v_i ← v_i − m[label_i] for label_i ≥ 0, rows
+ * labelled −1 keep their bits.  Two streaming launches beside the fold: a label-segmented sum pass (one walk over v and the int8 labels, one
+ * accumulator per field and lane, an entry added only to its own field's; partials in a fixed [nfields][workgroups] layout, no atomics),
+ * a fold per field in index order (behind a chunk stage above about two million entries) that stores m_f = sum_f/n_f in device slots the
+ * MATRIX owns (two matrices on one context do not collide), and the shift pass.  16-byte accesses with the labels of a pair loaded together
+ * when v is 16-byte aligned; the `nt` store hint under option nt_store.  The contract: every labelled entry comes out as fl(v_i − m_f) for
+ * the device's own m_f; |m_f − mean_f| <= n_f·ε·max|v|; two identical calls give identical bits.
+ * means (may be NULL): the nfields values m_f that were subtracted, read back; nrm2 (may be NULL): ‖Πv‖₂ over ALL rows, from the shift pass.
+ * Synchronises when either is asked for.  MGS_ERR_INVALID: v or A NULL, A without MGS_NULLSPACE_FIELDS, v shorter than A's rows. */
+int mgs_vec_project_fields(mgs_vec *v, const mgs_csr *A, double *means /* nfields or NULL */, double *nrm2 /* or NULL */);
 
 /* ------------------------------------------- L3 preconditioner: multilevel V-cycle (★) */
 /* MultiGridPrecond(A, P) — bicg.cpp:19-62.  A is borrowed (must outlive the hierarchy).
@@ -477,7 +515,15 @@ int mgs_hier_coarsen(mgs_hier *h, double ktg, int npass, double tou, int coarse_
  * general P, when a transfer leaves a row outside every aggregate, or when the hierarchy is row-sharded (halo columns, halo callbacks,
  * native plans or tail) — structural checks without a tolerance, made before anything is launched.  A one-level hierarchy is the
  * regularised dense solve alone; the smoothed coarsest form needs no change.  mgs_vcycle itself is not projected: its output on such a
- * hierarchy may carry a constant component, which the Krylov solvers remove.                                                 */
+ * hierarchy may carry a constant component, which the Krylov solvers remove.
+ * Fine operator declared MGS_NULLSPACE_FIELDS (mgs_csr_set_nullspace_fields): coarse labels are built once per level from the aggregation —
+ * an aggregate takes the label of its first member — by a kernel that also checks that all members of an aggregate share one label and
+ * that every row with a label >= 0 lies inside an aggregate (rows labelled −1 may stay outside).  MGS_ERR_INVALID names the level and the
+ * lowest offending fine row; the structural refusals of the constant kind (a general P, a row shard) apply unchanged.  The dense solve
+ * inverts A_c + Σ_f (s/n_cf)·z_cf·z_cfᵀ, s = max|a_ij| of A_c, n_cf the coarsest rows of field f.  Labels depend on the pattern only:
+ * mgs_hier_refresh keeps them (and the cached graphs) and only repeats the regularised inverse.  mgs_vcycle stays unprojected.
+ * New labels on a matrix that a finalized hierarchy already uses take effect at the next mgs_hier_finalize; mgs_hier_refresh works with the
+ * coarse labels it has (MGS_ERR_STATE when the hierarchy was finalized before any fields were declared, or for another number of them). */
 int mgs_hier_finalize(mgs_hier *h);
 int mgs_hier_set_smoother(mgs_hier *h, double omega, int nu1, int nu2);
 /* Values changed, pattern did not (time stepping, Picard / Newton iterations, parameter sweeps): recomputes everything in h
@@ -647,7 +693,13 @@ int mgs_pcg(const mgs_csr *A, mgs_vec *x, const mgs_vec *b, mgs_hier *h, int fle
  * MGS_ERR_INVALID, with a message: a NULL out parameter; vectors shorter than A's rows; x aliasing b; a hierarchy that is not a fixed
  * symmetric operator (nu1 != nu2, or a K-cycle set through mgs_hier_set_kcycle / mgs_hier_set_kcycle_entry; the additive form, a correction
  * scale and FP32 operands are allowed, as for mgs_pcg with flexible = 0); a row shard (the criteria of mgs_pcg_plan_create); an A or a
- * hierarchy with a declared null space (the constant vector is not the null space of a saddle system).
+ * hierarchy that declares MGS_NULLSPACE_CONSTANT (the constant vector is not the null space of a saddle system).
+ * A declared MGS_NULLSPACE_FIELDS (enclosed flow: the pressure constant) is served: the system solved is A·x = Πb, Π = I − Σ_f z_f·z_fᵀ/n_f.
+ *   normb = ‖Πb‖ (1 if that is 0); the caller's b is only read.  x ← Πx before EVERY true residual (at the start, at every check, at the
+ *   final one), and every true residual is Π(b − A·x); z̃ ← Π(M·v) after every preconditioner application (h = NULL included), so the
+ *   preconditioner seen is ΠMΠ and every Lanczos vector stays in the range.  Status 0 is still decided only on the true residual of the
+ *   returned x, whose fields have zero mean.  The hierarchy's fine operator must carry the same nfields and counts (see
+ *   mgs_csr_set_nullspace_fields); one more projection per iteration is the only difference in launches.
  * Option "minres_nt" (default 0): the update pass stores its direction vector with the `nt` hint on operators nt_store covers (A/B knob). */
 int mgs_minres(const mgs_csr *A, mgs_vec *x, const mgs_vec *b, mgs_hier *h,
                int *max_iter, double *tol, int *status);
@@ -841,7 +893,8 @@ int mgs_fgcr_plan_info(const mgs_fgcr_plan *p, int64_t out[6]);
  * INIT is mgs_minres's start: ‖b‖, 0 replaced by 1; v = b − A·x; resid <= tol: frozen, status 0, iteration 0; z̃ = M·v; g2 = z̃·v, status 2
  * unless g2 > 0; γ = √g2, γ_prev = 1, η = γ, κ = resid·‖b‖/γ; v_prev = w_prev = w = 0.
  *   create: borrows A and h (may be NULL); both must outlive the plan.  mgs_minres's acceptance rules: nu1 == nu2, no K-cycle and no K-cycle
- *     entry, no declared null space on A or on h's fine operator; the additive form, a correction scale and FP32 operands are allowed.  Runs
+ *     entry, no MGS_NULLSPACE_CONSTANT on A or on h's fine operator (MGS_NULLSPACE_FIELDS is served as in mgs_minres: the same projections at
+ *     the same places, as enqueued launches with the means on the device, no host read added); the additive form, a correction scale and FP32 operands are allowed.  Runs
  *     mgs_csr_optimize(A); allocates v ×2, z̃ ×2, q, w ×2 and the state block (inside the arena when one exists; not from the work-vector
  *     pool), a ring of 1024 posted results of 64 bytes in mapped host memory, the partial-sum buffer, and runs one cycle on each (v[k], z̃[k])
  *     pair with ones, so that the hierarchy's operands exist and both cycles are captured: two cached graphs for the life of the plan, and
@@ -863,7 +916,7 @@ int mgs_fgcr_plan_info(const mgs_fgcr_plan *p, int64_t out[6]);
  *   info: out = device bytes held, solves + enqueues so far, iterations enqueued by the last call, of those the iterations that ran frozen
  *     (known after solve / result), host waits the last call made, recalibrations in the last call.
  * MGS_ERR_INVALID, with a message headed mgs_minres_plan_*: a NULL argument; a matrix without rows; a row shard (the criteria of
- * mgs_pcg_plan_create); a hierarchy that is not a fixed symmetric operator; a declared null space; vectors shorter than A's rows; x aliasing
+ * mgs_pcg_plan_create); a hierarchy that is not a fixed symmetric operator; a declared constant null space; vectors shorter than A's rows; x aliasing
  * b; ahead < 0; iters < 0.  MGS_ERR_STATE: the context's stream is being captured. */
 typedef struct mgs_minres_plan mgs_minres_plan;
 int mgs_minres_plan_create(const mgs_csr *A, mgs_hier *h, mgs_minres_plan **out);

@@ -84,6 +84,9 @@ PROTOTYPES = {
     "mgs_csr_nullspace": (C.c_int, [C.c_void_p, c_int_p]),
     "mgs_csr_nullspace_defect": (C.c_int, [C.c_void_p, c_dbl_p]),
     "mgs_vec_project_const": (C.c_int, [C.c_void_p, c_dbl_p, c_dbl_p]),
+    "mgs_csr_set_nullspace_fields": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "mgs_csr_nullspace_fields": (C.c_int, [C.c_void_p, c_int_p, c_i64_p]),
+    "mgs_vec_project_fields": (C.c_int, [C.c_void_p, C.c_void_p, c_dbl_p, c_dbl_p]),
     "mgs_csr_destroy": (C.c_int, [C.c_void_p]),
     "mgs_csr_device_ptrs": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "mgs_csr_poisson3d": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),

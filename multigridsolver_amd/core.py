@@ -104,7 +104,9 @@ def write_mtx(path, rows, cols, rowptr, col, val):
     check(lib().mgs_mtx_write(path.encode(), rows, cols, len(col), _ip(rowptr), _ip(col), _dp(val)))
 
 
-_NULLSPACE = {None: 0, "constant": 1}      # MGS_NULLSPACE_NONE / MGS_NULLSPACE_CONSTANT
+_NULLSPACE = {None: 0, "constant": 1}      # MGS_NULLSPACE_NONE / MGS_NULLSPACE_CONSTANT (what set_nullspace takes)
+_NULLSPACE_NAMES = {0: None, 1: "constant", 2: "fields"}      # ... and MGS_NULLSPACE_FIELDS, entered through set_nullspace_fields only
+NULLSPACE_MAX_FIELDS = 8
 _INDEX_BITS = {"int32": 32, "int64": 64, "<i4": 32, "<i8": 64}
 _FLOAT64 = ("float64", "<f8")
 
@@ -289,12 +291,38 @@ class Csr:
         check(lib().mgs_csr_set_nullspace(self.h, _NULLSPACE[kind]), self.ctx.h); return self
 
     def nullspace(self):
-        """what set_nullspace declared: "constant" or None"""
+        """what set_nullspace / set_nullspace_fields declared: "constant", "fields" or None"""
         k = C.c_int(); check(lib().mgs_csr_nullspace(self.h, C.byref(k)), self.ctx.h)
-        return {v: n for n, v in _NULLSPACE.items()}[k.value]
+        return _NULLSPACE_NAMES[k.value]
+
+    def set_nullspace_fields(self, labels, nfields=None):
+        """declare a field-wise constant null space (mgs_csr_set_nullspace_fields): labels holds one entry per row, f in [0, nfields)
+        puts the row in field f, −1 in no field; asserted (not verified): A·z_f = 0 and z_fᵀ·A = 0 for the indicator z_f of every field —
+        the pressure constant of enclosed Stokes flow, one constant per component of a graph Laplacian.  labels: a torch int32 / int64
+        tensor on the context's device (made visible first) or a numpy integer array (uploaded here); nfields defaults to max + 1.
+        Range-checked on the device; served by minres, MinresPlan and pcg.  Returns self."""
+        if isinstance(labels, np.ndarray):
+            import torch
+            if labels.dtype.kind not in "iu":
+                raise TypeError(f"set_nullspace_fields: labels of dtype {labels.dtype}, integers expected")
+            labels = torch.from_numpy(np.ascontiguousarray(labels, dtype=np.int64)).to(f"cuda:{self.ctx.device}")
+            torch.cuda.synchronize(self.ctx.device)
+        ptr, n, bits = _dev_array(self.ctx, labels, "labels", True)
+        if n != self.shape[0]:
+            raise ValueError(f"set_nullspace_fields: labels holds {n} entries, the matrix has {self.shape[0]} rows")
+        if nfields is None:
+            nfields = int(labels.max()) + 1 if n else 0
+        check(lib().mgs_csr_set_nullspace_fields(self.h, C.c_void_p(ptr), bits, int(nfields)), self.ctx.h); return self
+
+    def nullspace_fields(self):
+        """(nfields, rows of every field) of a set_nullspace_fields declaration; (0, []) for any other kind"""
+        nf = C.c_int(); cnt = (C.c_int64 * NULLSPACE_MAX_FIELDS)()
+        check(lib().mgs_csr_nullspace_fields(self.h, C.byref(nf), cnt), self.ctx.h)
+        return nf.value, [int(cnt[k]) for k in range(nf.value)]
 
     def nullspace_defect(self):
-        """(‖A·1‖∞ / ‖|A|·1‖∞, the same for Aᵀ): how far the matrix is from the "constant" declaration; a diagnostic, synchronises"""
+        """(‖A·1‖∞ / ‖|A|·1‖∞, the same for Aᵀ): how far the matrix is from the "constant" declaration — on a "fields" matrix the maximum
+        over the fields of the same quotients with the field's indicator in the place of 1; a diagnostic, synchronises"""
         out = (C.c_double * 2)(); check(lib().mgs_csr_nullspace_defect(self.h, out), self.ctx.h)
         return float(out[0]), float(out[1])
 
@@ -615,6 +643,15 @@ class Vec:
         m, s = C.c_double(), C.c_double()
         check(lib().mgs_vec_project_const(self.h, C.byref(m), C.byref(s) if nrm2 else None), self.ctx.h)
         return (m.value, s.value) if nrm2 else m.value
+
+    def project_fields(self, A, nrm2=False):
+        """self ← Πself for the fields A declared (mgs_vec_project_fields): every labelled entry minus its field's mean → the means that
+        were subtracted (numpy, one per field), read back; nrm2=True: (means, ‖Πself‖₂ over all rows from the same pass)"""
+        nf = A.nullspace_fields()[0]
+        m = (C.c_double * max(nf, 1))(); s = C.c_double()
+        check(lib().mgs_vec_project_fields(self.h, A.h, m, C.byref(s) if nrm2 else None), self.ctx.h)
+        means = np.array([m[k] for k in range(nf)], dtype=np.float64)
+        return (means, s.value) if nrm2 else means
 
     def axpby(self, a, x, b):
         """self = a·x + b·self"""
@@ -1054,7 +1091,8 @@ class FgcrPlan(_KrylovPlan):
 class MinresPlan(_KrylovPlan):
     """Preconditioned MINRES with device-resident scalars (mgs_minres_plan, include/mgs.h): mgs_minres's arithmetic and bits, with one host look
     per iteration `ahead` iterations behind the queue (solve), or none at all (enqueue, then result).  hier: V(ν, ν), no K-cycle, no declared
-    null space.  A and hier must outlive the plan (they are kept referenced here)."""
+    constant null space; a field-wise one (Csr.set_nullspace_fields on A and on hier's matrix) is served as in minres().  A and hier must
+    outlive the plan (they are kept referenced here)."""
     _prefix = "minres"
 
     def __init__(self, A, hier=None):
@@ -1110,7 +1148,9 @@ def minres(A, x, b, hier=None, max_iter=10000, tol=1e-6):
     """preconditioned MINRES for symmetric A that may be indefinite (saddle-point systems), hier a symmetric positive definite preconditioner:
     V(ν, ν), no K-cycle (reference src/CPU_Matlab/solve.m:28-33 chooses between pcg and bicgstab; it has no MINRES) → (status, iterations, resid);
     resid is the true relative residual whatever the status; status 0 converged on the true residual / 1 max_iter / 2 z̃·v negative or not a
-    number (preconditioner not positive definite) / 3 Krylov space exhausted above the tolerance (singular, inconsistent system)"""
+    number (preconditioner not positive definite) / 3 Krylov space exhausted above the tolerance (singular, inconsistent system).
+    A with Csr.set_nullspace_fields (enclosed flow: the pressure constant; hier's matrix declared alike): solves A·x = Πb, resid is
+    ‖Π(b − A·x)‖/‖Πb‖, b is only read, the fields of x come back with zero mean"""
     mi, t, st = C.c_int(max_iter), C.c_double(tol), C.c_int(-1)
     check(lib().mgs_minres(A.h, x.h, b.h, hier.h if hier else None, C.byref(mi), C.byref(t), C.byref(st)), A.ctx.h)
     return st.value, mi.value, t.value

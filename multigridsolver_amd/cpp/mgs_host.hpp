@@ -171,6 +171,16 @@ class DeviceMatrix {
   // solve A·x = Πb and return the x of zero mean.  Copies of a DeviceMatrix share the device matrix and with it the declaration.
   void setNullspaceConstant(bool on) { check(mgs_csr_set_nullspace(a_.get(), on ? MGS_NULLSPACE_CONSTANT : MGS_NULLSPACE_NONE), context()); }
   bool nullspaceConstant() const { int k = 0; check(mgs_csr_nullspace(a_.get(), &k), context()); return k == MGS_NULLSPACE_CONSTANT; }
+  // Declares a field-wise constant null space (mgs.h: mgs_csr_set_nullspace_fields): labels_dev holds rows() entries of index_bits (32 or
+  // 64) bits in DEVICE memory, f in [0, nfields) puts the row in field f, −1 in no field — the pressure constant of enclosed Stokes flow,
+  // one constant per component of a graph Laplacian.  Checked on the device and copied; served by MINRESiml / MinresPlan and CGiml.
+  // setNullspaceConstant(false) takes the declaration back.  nullspaceFields(): the rows of every declared field (empty: another kind).
+  void setNullspaceFields(const void *labels_dev, int index_bits, int nfields) { check(mgs_csr_set_nullspace_fields(a_.get(), labels_dev, index_bits, nfields), context()); }
+  std::vector<int64_t> nullspaceFields() const {
+    int nf = 0; int64_t cnt[MGS_NULLSPACE_MAX_FIELDS];
+    check(mgs_csr_nullspace_fields(a_.get(), &nf, cnt), context());
+    return std::vector<int64_t>(cnt, cnt + nf);
+  }
   // New values, same pattern, in place (mgs.h: mgs_csr_update_values; the reference would upload a new matrix).  The pattern of A is
   // compared with the device copy's on the host: a different rowptr / col throws Error(MGS_ERR_INVALID).
   void update_values(const SMatrix &A) {

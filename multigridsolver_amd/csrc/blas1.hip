@@ -1,5 +1,5 @@
 // blas1.hip — vector updates and deterministic reductions: axpby / axpbypcz, dot, dot2, update + dot2, the PCG passes, sum / mean / shift for the
-// constant null space, several inner products in one pass (mdot), the multi-axpy with two sums (maxpy), the K-cycle's orthogonalised pair, and
+// constant null space, the label-segmented sum / shift for the field-wise one, several inner products in one pass (mdot), the multi-axpy with two sums (maxpy), the K-cycle's orthogonalised pair, and
 // the host half of every reduction: partial buffers, the staged fold, results posted to the host.  gfx950 only.
 // Every reduction pass leaves one partial (pair) per workgroup in a fixed layout and ends in the folds of blas1.hpp; the 8- and 16-byte forms
 // of a pass are separate kernels, their summation orders differ on purpose (tests/blas1_ref.py restates both).
@@ -301,6 +301,150 @@ __global__ __launch_bounds__(TB) void shift_const_vec_kernel(int64_t n, double *
     if (NRM) { s0 += o.x * o.x; s0 += o.y * o.y; }
   }
   if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) { const double o = v[n - 1] - m; if (STORE) v[n - 1] = o; if (NRM) s0 += o * o; }
+  if (!NRM) return;
+  BLAS1_FOLD1(s0, sh, part, true);
+}
+
+// ------------------------------------------------------------------ field-wise constant null space: v_i ← v_i − m[label_i] (k_project_fields)
+// The same two launches beside the fold with a label per row (int8, −1 = in no field).  Sum pass: one walk over v and the labels, one
+// accumulator per field and lane, an entry added only to the accumulator of its own label (an unlabelled NaN poisons nothing); partials in a
+// fixed [nf][gridDim.x] layout, no atomics; fields_mean_final_kernel folds each field's partials in index order and stores m_f = sum_f/n_f
+// in the matrix's own slots.  A pair (or entry) without a labelled row is not loaded at all: on a saddle system only the pressure rows are
+// streamed.  Shift pass: the means sit in LDS, rows labelled −1 keep their bits (a pair without a labelled row is not stored); NRM adds
+// ‖Πv‖² over ALL rows (partial pair per workgroup); STORE = false leaves v as it is.  25 B per labelled row for the pair of passes.
+constexpr int NSF = MGS_NULLSPACE_MAX_FIELDS;
+struct FieldCounts { double n[NSF]; };
+typedef signed char lab2 __attribute__((ext_vector_type(2)));
+// the end of the sum pass: every lane's NSF accumulators → part[f][blockIdx.x], waves added in wave order from 0.0
+#define FIELDS_FOLD(s, nf, sh, part)                                                                                       \
+  do {                                                                                                                     \
+    _Pragma("unroll") for (int k = 0; k < NSF; ++k) {                                                                      \
+      if (k < nf) {                                                                                                        \
+        double t = s[k];                                                                                                   \
+        for (int off = 32; off > 0; off >>= 1) t += __shfl_down(t, off);                                                   \
+        if ((threadIdx.x & 63) == 0) sh[k][threadIdx.x >> 6] = t;                                                          \
+      }                                                                                                                    \
+    }                                                                                                                      \
+    __syncthreads();                                                                                                       \
+    if ((int)threadIdx.x < nf) {                                                                                           \
+      double t = 0.0;                                                                                                      \
+      for (int q = 0; q < TB / 64; ++q) t += sh[threadIdx.x][q];                                                           \
+      part[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = t;                                                              \
+    }                                                                                                                      \
+  } while (0)
+__global__ __launch_bounds__(TB) void fields_sum_kernel(int64_t n, int nf, const double *__restrict__ v, const signed char *__restrict__ lab, double *__restrict__ part) {
+  __shared__ double sh[NSF][TB / 64];
+  double s[NSF];
+#pragma unroll
+  for (int k = 0; k < NSF; ++k) s[k] = 0.0;
+  int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * TB;
+  for (; i < n; i += stride) {
+    const int l = lab[i];
+    if (l < 0) continue;
+    const double x = v[i];
+#pragma unroll
+    for (int k = 0; k < NSF; ++k) if (l == k) s[k] += x;
+  }
+  FIELDS_FOLD(s, nf, sh, part);
+}
+// 16-byte form: the labels of a pair are one 2-byte load (lane t adds its pair x then y, a fixed order)
+__global__ __launch_bounds__(TB) void fields_sum_vec_kernel(int64_t n, int nf, const double *__restrict__ v, const signed char *__restrict__ lab, double *__restrict__ part) {
+  __shared__ double sh[NSF][TB / 64];
+  double s[NSF];
+#pragma unroll
+  for (int k = 0; k < NSF; ++k) s[k] = 0.0;
+  const int64_t n2 = n >> 1;
+  const vd2 *__restrict__ vv = reinterpret_cast<const vd2 *>(v);
+  const lab2 *__restrict__ lv = reinterpret_cast<const lab2 *>(lab);
+  const int64_t stride = (int64_t)gridDim.x * TB;
+  for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < n2; i += stride) {
+    const lab2 l = lv[i];
+    const int lx = l.x, ly = l.y;
+    if (lx < 0 && ly < 0) continue;
+    const vd2 p = vv[i];
+#pragma unroll
+    for (int k = 0; k < NSF; ++k) { if (lx == k) s[k] += p.x; if (ly == k) s[k] += p.y; }
+  }
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+    const int l = lab[n - 1];
+    if (l >= 0) {
+      const double x = v[n - 1];
+#pragma unroll
+      for (int k = 0; k < NSF; ++k) if (l == k) s[k] += x;
+    }
+  }
+  FIELDS_FOLD(s, nf, sh, part);
+}
+#undef FIELDS_FOLD
+// middle stage for long partial arrays, one row of workgroups per field (dot2_mid_kernel's chunks): out [nf][gridDim.x]
+__global__ __launch_bounds__(TB) void fields_mid_kernel(int nb, int chunk, const double *__restrict__ part, double *__restrict__ out) {
+  __shared__ double sh[TB / 64];
+  const int lo = blockIdx.x * chunk, hi = min(lo + chunk, nb);
+  const double *__restrict__ p = part + (size_t)blockIdx.y * nb;
+  double *__restrict__ o = out + (size_t)blockIdx.y * gridDim.x;
+  double s = 0.0;
+  for (int i = lo + threadIdx.x; i < hi; i += TB) s += p[i];
+  BLAS1_FOLD1(s, sh, o, false);
+}
+__global__ __launch_bounds__(TB) void fields_mean_final_kernel(int nb, int nf, const double *__restrict__ part, const FieldCounts cnt, double *__restrict__ means) {
+  __shared__ double sh[TB];
+  for (int k = 0; k < nf; ++k) {
+    const double r = final_fold(nb, part + (size_t)k * nb, sh);
+    if (threadIdx.x == 0) means[k] = r / cnt.n[k];
+    __syncthreads();
+  }
+}
+template <bool STORE, bool NRM>
+__global__ __launch_bounds__(TB) void fields_shift_kernel(int64_t n, int nf, double *__restrict__ v, const signed char *__restrict__ lab, const double *__restrict__ means,
+                                                          double *__restrict__ part) {
+  __shared__ double sh[TB / 64];
+  __shared__ double sm[NSF];
+  if ((int)threadIdx.x < NSF) sm[threadIdx.x] = (int)threadIdx.x < nf ? means[threadIdx.x] : 0.0;
+  __syncthreads();
+  double s0 = 0.0;
+  int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * TB;
+  for (; i < n; i += stride) {
+    const int l = lab[i];
+    if (!NRM && l < 0) continue;
+    double o = v[i];
+    if (l >= 0) { o = o - sm[l & (NSF - 1)]; if (STORE) v[i] = o; }
+    if (NRM) s0 += o * o;
+  }
+  if (!NRM) return;
+  BLAS1_FOLD1(s0, sh, part, true);
+}
+// 16-byte form (same per-element expression: same bits)
+template <bool STORE, bool NRM>
+__global__ __launch_bounds__(TB) void fields_shift_vec_kernel(int64_t n, int nf, double *__restrict__ v, const signed char *__restrict__ lab, const double *__restrict__ means,
+                                                              double *__restrict__ part, int nts) {
+  __shared__ double sh[TB / 64];
+  __shared__ double sm[NSF];
+  if ((int)threadIdx.x < NSF) sm[threadIdx.x] = (int)threadIdx.x < nf ? means[threadIdx.x] : 0.0;
+  __syncthreads();
+  const int64_t n2 = n >> 1;
+  vd2 *__restrict__ vv = reinterpret_cast<vd2 *>(v);
+  const lab2 *__restrict__ lv = reinterpret_cast<const lab2 *>(lab);
+  double s0 = 0.0;
+  const int64_t stride = (int64_t)gridDim.x * TB;
+  for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < n2; i += stride) {
+    const lab2 l = lv[i];
+    const int lx = l.x, ly = l.y;
+    const bool any = lx >= 0 || ly >= 0;
+    if (!NRM && !any) continue;
+    vd2 o = vv[i];
+    if (lx >= 0) o.x = o.x - sm[lx & (NSF - 1)];
+    if (ly >= 0) o.y = o.y - sm[ly & (NSF - 1)];
+    if (STORE && any) st2(vv + i, o, nts != 0);
+    if (NRM) { s0 += o.x * o.x; s0 += o.y * o.y; }
+  }
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+    const int l = lab[n - 1];
+    double o = v[n - 1];
+    if (l >= 0) { o = o - sm[l & (NSF - 1)]; if (STORE) v[n - 1] = o; }
+    if (NRM) s0 += o * o;
+  }
   if (!NRM) return;
   BLAS1_FOLD1(s0, sh, part, true);
 }
@@ -687,6 +831,55 @@ int k_project_const_mean(mgs_ctx *ctx, double *mean_host) {
   MGS_HIP(ctx, hipMemcpyAsync(mean_host, ctx->red_dev + MEAN_SLOT, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   MGS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return MGS_OK;
+}
+// ---- field-wise constant null space: v_i ← v_i − m[label_i]
+// The launch decisions of project_const_impl: the 16-byte arm when v is 16-byte aligned (the labels array is the matrix's own allocation, so a
+// pair's two labels are one aligned 2-byte load), the same grids, the `nt` hint under nts_of, fold_mid's chunk stage above 4096 workgroups.
+// The partials ([nf][nb], then the shift pass's pair [2][nb]) live in red_dev while they fit, else in the grown scratch.
+int k_project_fields(mgs_ctx *ctx, const mgs_nsfields *F, int64_t n, double *v, bool store, bool nrm, double *out_host2) {
+  if (n <= 0) { if (out_host2) out_host2[0] = out_host2[1] = 0.0; return MGS_OK; }
+  const int nf = F->nfields;
+  const bool vec = ctx->opt_blas1_vec && al16(v);
+  const int nts = nts_of(ctx, n);
+  const int nb = vec ? grid_vec((n + 1) / 2, ctx) : grid_cap(n, DOT_BLOCKS / NSF);
+  // sum pass with more than two fields: nf pairs per lane instead of one, so that the nf wave folds at a workgroup's end are paid once per nf pairs
+  // (measured with 8 fields at 256³, tools/ab_nullspace_fields.py: profiles/r24_nullspace_fields.md)
+  const int nbs = vec && nf > 2 ? (nb + nf - 1) / nf : nb;
+  double *part;
+  MGS_TRY(part_buf(ctx, std::max((int64_t)nf * nbs, 2 * (int64_t)nb), &part));
+  hipStream_t s = ctx->stream;
+  if (vec) hipLaunchKernelGGL(fields_sum_vec_kernel, dim3(nbs), dim3(TB), 0, s, n, nf, v, F->labels, part);
+  else hipLaunchKernelGGL(fields_sum_kernel, dim3(nbs), dim3(TB), 0, s, n, nf, v, F->labels, part);
+  const double *fold = part; int nfold = nbs;
+  if (nbs > 4096) {      // (the partials are in the grown scratch then: red_dev is free for the chunk sums)
+    const int groups = 256, chunk = (nbs + groups - 1) / groups;
+    hipLaunchKernelGGL(fields_mid_kernel, dim3(groups, nf), dim3(TB), 0, s, nbs, chunk, part, ctx->red_dev);
+    fold = ctx->red_dev; nfold = groups;
+  }
+  FieldCounts cnt;
+  for (int k = 0; k < NSF; ++k) cnt.n[k] = k < nf ? (double)F->counts[k] : 1.0;
+  hipLaunchKernelGGL(fields_mean_final_kernel, dim3(1), dim3(TB), 0, s, nfold, nf, fold, cnt, F->means);
+#define SHIFT_(ST, NR)                                                                                                                  \
+  do {                                                                                                                                  \
+    if (vec) hipLaunchKernelGGL((fields_shift_vec_kernel<ST, NR>), dim3(nb), dim3(TB), 0, s, n, nf, v, F->labels, F->means, part, nts);  \
+    else hipLaunchKernelGGL((fields_shift_kernel<ST, NR>), dim3(nb), dim3(TB), 0, s, n, nf, v, F->labels, F->means, part);               \
+  } while (0)
+  if (store && nrm) SHIFT_(true, true); else if (store) SHIFT_(true, false); else if (nrm) SHIFT_(false, true);
+#undef SHIFT_
+  MGS_HIP(ctx, hipGetLastError());
+  return nrm ? k_dot2_finish(ctx, nb, part, out_host2) : MGS_OK;
+}
+// the one dispatch on the matrix's null-space record
+int k_ns_project(const mgs_csr *A, int64_t n, double *v) {
+  return A->nullspace == MGS_NULLSPACE_FIELDS ? k_project_fields(A->ctx, A->nsf, n, v, true, false, nullptr) : k_project_const(A->ctx, n, v);
+}
+int k_ns_project_nrm2(const mgs_csr *A, int64_t n, double *v, double *out_host2) {
+  if (A->nullspace == MGS_NULLSPACE_FIELDS) return k_project_fields(A->ctx, A->nsf, n, v, true, true, out_host2);
+  return out_host2 ? k_project_const_nrm2(A->ctx, n, v, out_host2) : k_project_const_nrm2_fold(A->ctx, n, v);
+}
+int k_ns_dev_nrm2(const mgs_csr *A, int64_t n, const double *v, double *out_host2) {
+  if (A->nullspace == MGS_NULLSPACE_FIELDS) return k_project_fields(A->ctx, A->nsf, n, const_cast<double *>(v), false, true, out_host2);
+  return out_host2 ? k_const_dev_nrm2(A->ctx, n, v, out_host2) : k_const_dev_nrm2_fold(A->ctx, n, v);
 }
 // workgroups of a multi-vector reduction pass: one-shot at small sizes, a few elements per lane at large ones (partials stay short)
 static int mdot_grid(int64_t n) {

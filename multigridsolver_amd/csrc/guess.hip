@@ -261,6 +261,7 @@ int mgs_guess_create(const mgs_csr *A, int kind, int capacity, mgs_guess **out) 
   MGS_CHECK(ctx, A, MGS_ERR_INVALID, "mgs_guess_create: NULL matrix");
   MGS_CHECK(ctx, A->rows == A->cols, MGS_ERR_INVALID, "mgs_guess_create: the matrix is %d x %d (%s)", A->rows, A->cols,
             A->cols > A->rows ? "halo columns: a row shard" : "not square");
+  MGS_CHECK(ctx, A->nullspace != MGS_NULLSPACE_FIELDS, MGS_ERR_INVALID, "mgs_guess_create: a field-wise null space (MGS_NULLSPACE_FIELDS) is declared; it is served by mgs_minres / mgs_pcg");
   mgs_guess *g = new mgs_guess();
   g->ctx = ctx; g->A = A; g->kind = kind; g->capacity = capacity; g->n = A->rows;
   g->stride = ((g->n + 31) / 32) * 32; if (g->stride == 0) g->stride = 32;          // every slot 256-byte aligned
@@ -337,6 +338,7 @@ static int guess_update(mgs_guess *g, const double *x, int *added) {
   const bool restart = g->size == g->capacity;
   const int K = restart ? 0 : g->size, slot = K;
   const int energy = g->kind == MGS_GUESS_ENERGY;
+  MGS_CHECK(ctx, g->A->nullspace != MGS_NULLSPACE_FIELDS, MGS_ERR_INVALID, "mgs_guess_update: a field-wise null space (MGS_NULLSPACE_FIELDS) is declared; it is served by mgs_minres / mgs_pcg");
   const bool ns = g->A->nullspace == MGS_NULLSPACE_CONSTANT;
   mgs_vec *xs = nullptr, *w = nullptr;
   struct Guard { mgs_ctx *c; mgs_vec **a, **b; ~Guard() { mgs_ws_put(c, *a); mgs_ws_put(c, *b); } } guard{ctx, &xs, &w};

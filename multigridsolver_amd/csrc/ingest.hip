@@ -309,3 +309,50 @@ int k_csr_update_values_coo(mgs_csr *A, const void *val_dev) {
   MGS_HIP(ctx, hipGetLastError());
   return MGS_OK;
 }
+
+// ------------------------------------------------------------------ null-space labels (mgs_csr_set_nullspace_fields): check + narrow + count
+// A label is compared with its bounds as a 64-bit value before it is narrowed (2³² does not alias 0); the lowest offending row comes back through
+// one 64-bit atomicMin word; a refused label is narrowed to −1.  Rows per field: one integer atomicAdd per wave and field (the result does not
+// depend on how they were scheduled).
+namespace {
+template <class I>
+__global__ __launch_bounds__(TB) void labels_kernel(long long rows, int nf, const I *__restrict__ in, signed char *__restrict__ out, unsigned long long *__restrict__ st /* [0] bad row, [1 + f] rows of f */) {
+  const long long i = (long long)blockIdx.x * TB + threadIdx.x;
+  long long v = -1;
+  if (i < rows) {
+    v = (long long)in[i];
+    if (v < -1 || v >= nf) { atomicMin(&st[0], (unsigned long long)i); v = -1; }
+    out[i] = (signed char)v;
+  }
+  for (int f = 0; f < nf; ++f) {
+    const unsigned long long m = __ballot(v == f);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(&st[1 + f], (unsigned long long)__popcll(m));
+  }
+}
+}   // namespace
+int k_labels_from_device(mgs_ctx *ctx, int64_t rows, const void *labels_dev, int index_bits, int nfields, signed char **lab_out, int64_t *counts, int64_t *bad_row, long long *bad_val) {
+  hipStream_t s = ctx->stream;
+  DevBuf st, lab;
+  unsigned long long h[1 + MGS_NULLSPACE_MAX_FIELDS];
+  MGS_TRY(dalloc<unsigned long long>(ctx, st, 1 + MGS_NULLSPACE_MAX_FIELDS));
+  MGS_TRY(dalloc<signed char>(ctx, lab, (size_t)rows + 2));
+  MGS_HIP(ctx, hipMemsetAsync(st.p, 0, sizeof h, s));
+  MGS_HIP(ctx, hipMemsetAsync(st.p, 0xff, sizeof(unsigned long long), s));
+  if (rows) {
+    if (index_bits == 64) hipLaunchKernelGGL(labels_kernel<long long>, dim3(mgs_grid(rows, TB)), dim3(TB), 0, s, (long long)rows, nfields, (const long long *)labels_dev, lab.as<signed char>(), st.as<unsigned long long>());
+    else hipLaunchKernelGGL(labels_kernel<int>, dim3(mgs_grid(rows, TB)), dim3(TB), 0, s, (long long)rows, nfields, (const int *)labels_dev, lab.as<signed char>(), st.as<unsigned long long>());
+  }
+  MGS_HIP(ctx, hipGetLastError());
+  MGS_HIP(ctx, hipMemcpyAsync(h, st.p, sizeof h, hipMemcpyDeviceToHost, s));
+  MGS_HIP(ctx, hipStreamSynchronize(s));
+  *bad_row = -1; *bad_val = 0;
+  if (h[0] != NO_ERR) {
+    *bad_row = (int64_t)h[0];
+    if (index_bits == 64) { long long v = 0; MGS_HIP(ctx, hipMemcpy(&v, (const long long *)labels_dev + h[0], sizeof v, hipMemcpyDeviceToHost)); *bad_val = v; }
+    else { int v = 0; MGS_HIP(ctx, hipMemcpy(&v, (const int *)labels_dev + h[0], sizeof v, hipMemcpyDeviceToHost)); *bad_val = v; }
+    return MGS_OK;
+  }
+  for (int f = 0; f < MGS_NULLSPACE_MAX_FIELDS; ++f) counts[f] = (int64_t)h[1 + f];
+  *lab_out = lab.as<signed char>(); lab.p = nullptr;
+  return MGS_OK;
+}

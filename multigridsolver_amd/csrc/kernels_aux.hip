@@ -314,6 +314,39 @@ __global__ void dense_reg_const_kernel(int n, double *__restrict__ W, const unsi
   int i = blockIdx.y;
   if (j < n) W[(size_t)i * 2 * n + j] += __longlong_as_double((long long)amax_bits[0]) / (double)n;
 }
+// Field-wise constant null space (mgs_csr_set_nullspace_fields): A_c + Σ_f (s/n_f)·z_f·z_fᵀ — s/n_f is added where row and column carry the same
+// label f >= 0 (lab: the coarsest level's labels, cnt: its rows per field).  For a symmetric A_c whose null space is span{z_f} the inverse is
+// A_c⁺ + Σ_f (1/s)·z_f·z_fᵀ/n_f: exactly A_c⁺·b on a right-hand side orthogonal to every z_f.
+struct DenseFieldCounts { double n[MGS_NULLSPACE_MAX_FIELDS]; };
+__global__ void dense_reg_fields_kernel(int n, double *__restrict__ W, const unsigned long long *__restrict__ amax_bits, const signed char *__restrict__ lab, const DenseFieldCounts cnt) {
+  int j = blockIdx.x * blockDim.x + threadIdx.x;
+  int i = blockIdx.y;
+  if (j >= n) return;
+  const int li = lab[i], lj = lab[j];
+  if (li < 0 || li != lj) return;
+  double nf = 1.0;
+#pragma unroll
+  for (int k = 0; k < MGS_NULLSPACE_MAX_FIELDS; ++k) if (li == k) nf = cnt.n[k];
+  W[(size_t)i * 2 * n + j] += __longlong_as_double((long long)amax_bits[0]) / nf;
+}
+// Coarse labels of a level under a field-wise null space, and the two checks that make the coarse indicators P-images of the fine ones: fine row i
+// with aggregate a compares its label with that of a's first member (which writes the aggregate's label); a labelled row outside every
+// aggregate is refused.  bad: min over (row << 1 | kind) — the lowest offending fine row, deterministic.
+__global__ void coarse_labels_kernel(int n, const int *__restrict__ agg, const int *__restrict__ cptr, const int *__restrict__ members, const signed char *__restrict__ lab,
+                                     signed char *__restrict__ clab, unsigned long long *__restrict__ bad) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int a = agg[i], l = lab[i];
+  if (a < 0) { if (l >= 0) atomicMin(bad, ((unsigned long long)i << 1) | 1ull); return; }
+  const int first = members[cptr[a]];
+  if (i == first) clab[a] = (signed char)l;
+  else if (lab[first] != l) atomicMin(bad, (unsigned long long)i << 1);
+}
+// z_f as a vector: 1.0 where the row carries label f, 0.0 elsewhere (mgs_csr_nullspace_defect on a fields matrix)
+__global__ void label_indicator_kernel(int n, const signed char *__restrict__ lab, int f, double *__restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = lab[i] == f ? 1.0 : 0.0;
+}
 // Singularity rule: the operator is refused (piv[1] = 1) when a pivot is not greater than GJ_SINGULAR_FACTOR·n·DBL_EPSILON·max|a_ij|.
 // Written as !(|pivot| > threshold) so that a NaN pivot and a NaN or Inf scale are refused as well.  Basis of the constant (NumPy model
 // of this algorithm, FP64): singular weighted graph Laplacians of n = 4..500 end with a pivot <= 0.31·n·eps·max|a|; regular matrices of
@@ -600,6 +633,16 @@ int k_absmax_dev(mgs_ctx *ctx, int64_t n, const double *v, unsigned long long *a
   MGS_HIP(ctx, hipGetLastError());
   return MGS_OK;
 }
+int k_label_indicator(mgs_ctx *ctx, int n, const signed char *lab, int f, double *out) {
+  if (n) hipLaunchKernelGGL(label_indicator_kernel, dim3(mgs_grid(n, TB)), dim3(TB), 0, ctx->stream, n, lab, f, out);
+  MGS_HIP(ctx, hipGetLastError());
+  return MGS_OK;
+}
+int k_coarse_labels(mgs_ctx *ctx, const mgs_xfer *T, const signed char *lab, signed char *clab, unsigned long long *bad_dev) {
+  if (T->n_fine) hipLaunchKernelGGL(coarse_labels_kernel, dim3(mgs_grid(T->n_fine, TB)), dim3(TB), 0, ctx->stream, T->n_fine, T->agg, T->cptr, T->members, lab, clab, bad_dev);
+  MGS_HIP(ctx, hipGetLastError());
+  return MGS_OK;
+}
 int k_kc_update_r(mgs_ctx *ctx, int n, const double *scal, const double *r, const double *v1, double *rp) {
   if (n) hipLaunchKernelGGL(kc_update_r_kernel, dim3(mgs_grid(n, TB)), dim3(TB), 0, ctx->stream, n, scal, r, v1, rp);
   MGS_HIP(ctx, hipGetLastError());
@@ -620,8 +663,9 @@ int k_dense_gemv(mgs_ctx *ctx, int n, const double *M, const double *b, double *
 // *inv_out == NULL: the n·n result is allocated here (and released again on failure); else it is written into the caller's buffer
 // (mgs_hier_refresh: the cached graphs hold that pointer), which stays the caller's whatever happens.  MGS_ERR_NUMERIC: a pivot not
 // greater than 8·n·DBL_EPSILON·max|a_ij| (see gj_pivot_kernel), which also refuses NaN and Inf among the values.  The work buffers are
-// released on every exit.  reg_const != 0: A + (max|a_ij|/n)·1·1ᵀ is inverted (constant null space declared; dense_reg_const_kernel).
-int k_dense_inverse(mgs_ctx *ctx, const mgs_csr *A, double **inv_out, int reg_const) {
+// released on every exit.  reg_const == 1: A + (max|a_ij|/n)·1·1ᵀ is inverted (constant null space declared; dense_reg_const_kernel); 2: A + Σ_f (max|a_ij|/n_f)·z_f·z_fᵀ
+// for the labels lab (device) with fcount[f] rows each (field-wise null space; dense_reg_fields_kernel).
+int k_dense_inverse(mgs_ctx *ctx, const mgs_csr *A, double **inv_out, int reg_const, const signed char *lab, const double *fcount) {
   const int n = A->rows;
   double *const into = *inv_out;
   MGS_CHECK(ctx, A->cols == n, MGS_ERR_INVALID, "coarsest operator is not square (%d x %d)", A->rows, A->cols);
@@ -640,7 +684,12 @@ int k_dense_inverse(mgs_ctx *ctx, const mgs_csr *A, double **inv_out, int reg_co
     MGS_HIP(ctx, hipMemsetAsync(amax, 0, sizeof(unsigned long long), s));
     if (A->nnz) hipLaunchKernelGGL(dense_absmax_kernel, dim3(mgs_blas1_grid_capped(ctx, A->nnz)), dim3(TB), 0, s, (int64_t)A->nnz, A->val, amax);
     if (n) hipLaunchKernelGGL(dense_scatter_kernel, dim3(mgs_grid(n, TB)), dim3(TB), 0, s, n, A->rowptr, A->col, A->val, W);
-    if (n && reg_const) hipLaunchKernelGGL(dense_reg_const_kernel, dim3(mgs_grid(n, TB), n), dim3(TB), 0, s, n, W, amax);
+    if (n && reg_const == 1) hipLaunchKernelGGL(dense_reg_const_kernel, dim3(mgs_grid(n, TB), n), dim3(TB), 0, s, n, W, amax);
+    if (n && reg_const == 2) {
+      DenseFieldCounts fc;
+      for (int k = 0; k < MGS_NULLSPACE_MAX_FIELDS; ++k) fc.n[k] = fcount[k] > 0.0 ? fcount[k] : 1.0;
+      hipLaunchKernelGGL(dense_reg_fields_kernel, dim3(mgs_grid(n, TB), n), dim3(TB), 0, s, n, W, amax, lab, fc);
+    }
     for (int k = 0; k < n; ++k) {
       hipLaunchKernelGGL(gj_pivot_kernel, dim3(1), dim3(TB), 0, s, n, k, W, piv, colk + n, amax);
       hipLaunchKernelGGL(gj_swap_scale_kernel, dim3(mgs_grid(2 * n, TB)), dim3(TB), 0, s, n, k, W, piv, colk + n);

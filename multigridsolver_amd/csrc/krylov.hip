@@ -27,12 +27,25 @@ void mgs_ws_put(mgs_ctx *ctx, mgs_vec *v) {
 
 // A declared MGS_NULLSPACE_CONSTANT: the solvers below solve A·x = Πb, Π = I − 1·1ᵀ/n (k_project_const), and return the x of zero mean.
 // *ns_out = whether to project.  Refused: a declared row shard; a hierarchy whose fine operator carries another kind than A.
-int mgs_krylov_nullspace(const mgs_csr *A, const mgs_hier *h, const char *who, bool *ns_out) {
+// A declared MGS_NULLSPACE_FIELDS: served by the callers that say so (mgs_minres, mgs_minres_plan, mgs_pcg: Π = I − Σ_f z_f·z_fᵀ/n_f through the
+// dispatch k_ns_project*), refused by every other one.  The hierarchy's fine operator must then carry the same number of fields with the same
+// rows per field; that the two label arrays agree entry by entry is the caller's responsibility (mgs.h).
+int mgs_krylov_nullspace(const mgs_csr *A, const mgs_hier *h, const char *who, bool *ns_out, bool serves_fields) {
   mgs_ctx *ctx = A->ctx;
-  const bool ns = A->nullspace == MGS_NULLSPACE_CONSTANT;
-  MGS_CHECK(ctx, !ns || (A->cols == A->rows && !ctx->ncomm && !ctx->allreduce), MGS_ERR_INVALID, "%s: constant null space declared on a row shard", who);
+  const bool fields = A->nullspace == MGS_NULLSPACE_FIELDS;
+  const bool hfields = h && h->lev[0].A->nullspace == MGS_NULLSPACE_FIELDS;
+  MGS_CHECK(ctx, serves_fields || !(fields || hfields), MGS_ERR_INVALID, "%s: a field-wise null space (MGS_NULLSPACE_FIELDS) is declared; it is served by mgs_minres / mgs_pcg", who);
+  const bool ns = fields || A->nullspace == MGS_NULLSPACE_CONSTANT;
+  MGS_CHECK(ctx, !ns || (A->cols == A->rows && !ctx->ncomm && !ctx->allreduce), MGS_ERR_INVALID, "%s: %s null space declared on a row shard", who, fields ? "field-wise" : "constant");
   MGS_CHECK(ctx, !h || h->lev[0].A->nullspace == A->nullspace, MGS_ERR_INVALID,
             "%s: the hierarchy's fine operator carries null-space kind %d, A carries %d (a hierarchy built for a regular twin of A?)", who, h->lev[0].A->nullspace, A->nullspace);
+  if (fields && h) {
+    const mgs_nsfields *a = A->nsf, *b = h->lev[0].A->nsf;
+    MGS_CHECK(ctx, a->nfields == b->nfields, MGS_ERR_INVALID, "%s: A declares %d fields, the hierarchy's fine operator %d", who, a->nfields, b->nfields);
+    for (int f = 0; f < a->nfields; ++f)
+      MGS_CHECK(ctx, a->counts[f] == b->counts[f], MGS_ERR_INVALID, "%s: field %d has %lld rows on A and %lld on the hierarchy's fine operator", who, f, (long long)a->counts[f],
+                (long long)b->counts[f]);
+  }
   *ns_out = ns;
   return MGS_OK;
 }
@@ -118,24 +131,24 @@ int mgs_pcg(const mgs_csr *A, mgs_vec *x, const mgs_vec *b, mgs_hier *h, int fle
   MGS_CHECK(ctx, flexible || !h || (h->nu1 == h->nu2 && h->kcycle_levels <= 0 && !h->kcycle_entry), MGS_ERR_INVALID,
             "mgs_pcg: flexible = 0 needs a fixed symmetric preconditioner (nu1 == nu2, no K-cycle); pass flexible = 1");
   bool ns = false;
-  MGS_TRY(mgs_krylov_nullspace(A, h, "mgs_pcg", &ns));
+  MGS_TRY(mgs_krylov_nullspace(A, h, "mgs_pcg", &ns, true));
   MGS_TRY(mgs_csr_optimize(const_cast<mgs_csr *>(A)));
   const int n = A->rows, next = A->cols > n ? A->cols : n;
   MGS_CHECK(ctx, x->n >= n && b->n >= n, MGS_ERR_INVALID, "mgs_pcg: vectors shorter than %d", n);
   mgs_vec *r = 0, *z = 0, *p = 0, *q = 0, *xe = 0;
-  krylov_frame f{ctx, h, n, ns, true, {}};      // returned last-taken-first so that the next solve takes the same vectors in the same roles
+  krylov_frame f{ctx, h, n, ns, true, {}, A};      // returned last-taken-first so that the next solve takes the same vectors in the same roles
   for (mgs_vec **w : {&r, &z, &p, &q}) MGS_TRY(f.take(w, w == &p ? next : n));
   mgs_vec xv = f.view(x), bv = f.view(b), pv = f.view(p);
   if (x->n < next) MGS_TRY(f.take(&xe, next));
   double normb = 0, resid = 0, rho = 0, rho_prev = 0, alpha = 0, beta = 0, d2[2] = {0, 0};
   bool pending = false;                                    // x is one step behind: x += alpha·p not applied yet
-  bool x_mean = ns;                                        // constant null space: x may carry a constant component (the guess's, or an update's rounding)
+  bool x_mean = ns;                                        // declared null space (constant or field-wise, one dispatch: k_ns_project): x may carry a constant component (the guess's, or an update's rounding)
   auto flush = [&]() -> int {
     if (pending) { MGS_TRY(mgs_axpby(alpha, &pv, 1.0, &xv)); pending = false; }
     return MGS_OK;
   };
   auto project_x = [&]() -> int {                         // x ← Πx (x flushed by the caller): after the last update, before the final true residual
-    if (x_mean) { MGS_TRY(k_project_const(ctx, n, xv.d)); x_mean = false; }
+    if (x_mean) { MGS_TRY(k_ns_project(A, n, xv.d)); x_mean = false; }
     return MGS_OK;
   };
   auto true_residual = [&]() -> int {                     // r = b − A·x (x flushed by the caller), resid = ‖r‖/‖b‖; constant null space: r = Π(b − A·x), ‖r‖/‖Πb‖
@@ -144,7 +157,7 @@ int mgs_pcg(const mgs_csr *A, mgs_vec *x, const mgs_vec *b, mgs_hier *h, int fle
     MGS_TRY(f.halo(xin));
     MGS_TRY(mgs_residual(A, xin, &bv, r));
     double s = 0;
-    if (ns) { double s2[2]; MGS_TRY(k_project_const_nrm2(ctx, n, r->d, s2)); s = s2[0]; }
+    if (ns) { double s2[2]; MGS_TRY(k_ns_project_nrm2(A, n, r->d, s2)); s = s2[0]; }
     else MGS_TRY(k_dot(ctx, n, r->d, r->d, &s));
     resid = std::sqrt(s) / normb;
     return MGS_OK;
@@ -160,7 +173,7 @@ int mgs_pcg(const mgs_csr *A, mgs_vec *x, const mgs_vec *b, mgs_hier *h, int fle
   bool restart = true;                                     // the next direction is p = z
   for (int i = 1; i <= maxit; ++i) {
     if (h) MGS_TRY(mgs_vcycle(h, r, z, 1)); else MGS_TRY(mgs_vec_copy(r, z));
-    if (ns) MGS_TRY(k_project_const(ctx, n, z->d));        // z ← Πz: the preconditioner seen is ΠMΠ
+    if (ns) MGS_TRY(k_ns_project(A, n, z->d));        // z ← Πz: the preconditioner seen is ΠMΠ
     if (flexible && !restart) { MGS_TRY(k_dot2(ctx, n, r->d, z->d, q->d, z->d, d2)); rho = d2[0]; }
     else MGS_TRY(k_dot(ctx, n, r->d, z->d, &rho));
     if (!(rho > 0)) return done(i, 2);                     // preconditioner not positive definite (or not a number)

@@ -74,8 +74,8 @@ struct Plan {
     return MGS_OK;
   }
   // create, behind validate: the null-space rule, then nvec vectors (256-byte aligned) and the state in one zeroed device block, and the host ring
-  int allocate(const char *who, int nvec) {
-    MGS_TRY(mgs_krylov_nullspace(A, h, who, &ns));
+  int allocate(const char *who, int nvec, bool serves_fields = false) {
+    MGS_TRY(mgs_krylov_nullspace(A, h, who, &ns, serves_fields));
     MGS_TRY(mgs_csr_optimize(const_cast<mgs_csr *>(A)));
     stride = (((int64_t)n + 31) / 32) * 32;
     const size_t nstate = (sizeof(State) + 255) / 256 * 32;                                // doubles

@@ -370,6 +370,7 @@ int mgs_csr_destroy(mgs_csr *A) {
   mgs_free_add(A->addp);
   mgs_free_extract(A->extp);
   mgs_free_reorder(A->reop);
+  mgs_free_nsfields(A->nsf);
   delete A;
   return MGS_OK;
 }
@@ -396,7 +397,41 @@ int mgs_csr_set_nullspace(mgs_csr *A, int kind) {
   MGS_CHECK(A->ctx, kind == MGS_NULLSPACE_NONE || kind == MGS_NULLSPACE_CONSTANT, MGS_ERR_INVALID, "mgs_csr_set_nullspace: unknown kind %d", kind);
   MGS_CHECK(A->ctx, A->rows == A->cols, MGS_ERR_INVALID, "mgs_csr_set_nullspace: the matrix is %d x %d (%s)", A->rows, A->cols,
             A->cols > A->rows ? "halo columns: a row shard" : "not square");
+  if (A->nsf) { hipStreamSynchronize(A->ctx->stream); mgs_free_nsfields(A->nsf); A->nsf = nullptr; }      // an enqueued projection may still read the labels
   A->nullspace = kind;
+  return MGS_OK;
+}
+// field-wise constant null space: labels from device memory, checked and narrowed before anything uses them (ingest.hip); the matrix keeps the
+// declaration it had on every refusal
+int mgs_csr_set_nullspace_fields(mgs_csr *A, const void *labels_dev, int index_bits, int nfields) {
+  MGS_CHECK(nullptr, A, MGS_ERR_INVALID, "mgs_csr_set_nullspace_fields: NULL matrix");
+  mgs_ctx *ctx = A->ctx;
+  MGS_CHECK(ctx, labels_dev, MGS_ERR_INVALID, "mgs_csr_set_nullspace_fields: NULL labels");
+  MGS_CHECK(ctx, index_bits == 32 || index_bits == 64, MGS_ERR_INVALID, "mgs_csr_set_nullspace_fields: index_bits = %d, expected 32 or 64", index_bits);
+  MGS_CHECK(ctx, nfields >= 1 && nfields <= MGS_NULLSPACE_MAX_FIELDS, MGS_ERR_INVALID, "mgs_csr_set_nullspace_fields: nfields = %d outside 1..%d", nfields, MGS_NULLSPACE_MAX_FIELDS);
+  MGS_CHECK(ctx, A->rows == A->cols && !mgs_csr_is_shard(A), MGS_ERR_INVALID, "mgs_csr_set_nullspace_fields: the matrix is %d x %d (%s)", A->rows, A->cols,
+            A->cols > A->rows ? "halo columns: a row shard" : "not square");
+  MGS_CHECK(ctx, !ctx->ncomm && !ctx->allreduce, MGS_ERR_INVALID, "mgs_csr_set_nullspace_fields: the context sums over ranks (a row shard)");
+  signed char *lab = nullptr; int64_t counts[MGS_NULLSPACE_MAX_FIELDS] = {0}, bad_row = -1; long long bad_val = 0;
+  MGS_TRY(k_labels_from_device(ctx, A->rows, labels_dev, index_bits, nfields, &lab, counts, &bad_row, &bad_val));
+  MGS_CHECK(ctx, bad_row < 0, MGS_ERR_INVALID, "mgs_csr_set_nullspace_fields: row %lld carries label %lld outside [-1, %d)", (long long)bad_row, bad_val, nfields);
+  for (int f = 0; f < nfields; ++f)
+    if (counts[f] == 0) { mgs_hip_free(lab); return mgs_fail(ctx, MGS_ERR_INVALID, "mgs_csr_set_nullspace_fields: field %d has no rows", f); }
+  mgs_nsfields *F = new mgs_nsfields();
+  F->nfields = nfields; F->labels = lab;
+  for (int f = 0; f < nfields; ++f) F->counts[f] = counts[f];
+  int rc = mgs_dev_alloc(ctx, &F->means, (size_t)MGS_NULLSPACE_MAX_FIELDS);
+  if (rc == MGS_OK && hipMemsetAsync(F->means, 0, sizeof(double) * MGS_NULLSPACE_MAX_FIELDS, ctx->stream) != hipSuccess) rc = mgs_fail(ctx, MGS_ERR_HIP, "mgs_csr_set_nullspace_fields: hipMemsetAsync failed");
+  if (rc != MGS_OK) { mgs_free_nsfields(F); return rc; }
+  if (A->nsf) { hipStreamSynchronize(ctx->stream); mgs_free_nsfields(A->nsf); }
+  A->nsf = F; A->nullspace = MGS_NULLSPACE_FIELDS;
+  return MGS_OK;
+}
+int mgs_csr_nullspace_fields(const mgs_csr *A, int *nfields, int64_t counts[MGS_NULLSPACE_MAX_FIELDS]) {
+  MGS_CHECK(nullptr, A && nfields && counts, MGS_ERR_INVALID, "mgs_csr_nullspace_fields: NULL argument");
+  const bool f = A->nullspace == MGS_NULLSPACE_FIELDS && A->nsf;
+  *nfields = f ? A->nsf->nfields : 0;
+  for (int k = 0; k < MGS_NULLSPACE_MAX_FIELDS; ++k) counts[k] = f ? A->nsf->counts[k] : 0;
   return MGS_OK;
 }
 int mgs_csr_nullspace(const mgs_csr *A, int *kind) {
@@ -414,6 +449,43 @@ int mgs_csr_nullspace_defect(const mgs_csr *A, double out[2]) {
   const int64_t nmax = A->rows > A->cols ? A->rows : A->cols;
   mgs_vec *ones = nullptr, *y = nullptr; mgs_csr *At = nullptr, *Aa = nullptr; unsigned long long *mx = nullptr;
   unsigned long long hm[4] = {0, 0, 0, 0};
+  if (A->nullspace == MGS_NULLSPACE_FIELDS && A->nsf) {      // the maximum over the fields of the same two quotients with z_f in the place of 1: one SpMV per field and matrix
+    std::vector<unsigned long long> hf(4 * (size_t)A->nsf->nfields, 0ull);
+    auto runf = [&]() -> int {
+      MGS_TRY(mgs_vec_create(ctx, nmax, &ones)); MGS_TRY(mgs_vec_create(ctx, nmax, &y));
+      MGS_TRY(mgs_dev_alloc(ctx, &mx, hf.size()));
+      MGS_HIP(ctx, hipMemsetAsync(mx, 0, sizeof(unsigned long long) * hf.size(), ctx->stream));
+      MGS_TRY(mgs_csr_transpose(A, &At));
+      for (int f = 0; f < A->nsf->nfields; ++f) {
+        MGS_TRY(k_label_indicator(ctx, A->rows, A->nsf->labels, f, ones->d));
+        MGS_TRY(mgs_spmv(A, ones, y));  MGS_TRY(k_absmax_dev(ctx, A->rows, y->d, mx + 4 * f + 0));
+        MGS_TRY(mgs_spmv(At, ones, y)); MGS_TRY(k_absmax_dev(ctx, At->rows, y->d, mx + 4 * f + 2));
+      }
+      MGS_TRY(k_abs_inplace(ctx, At->nnz, At->val));
+      MGS_TRY(mgs_csr_transpose(At, &Aa));
+      for (int f = 0; f < A->nsf->nfields; ++f) {
+        MGS_TRY(k_label_indicator(ctx, A->rows, A->nsf->labels, f, ones->d));
+        MGS_TRY(mgs_spmv(At, ones, y)); MGS_TRY(k_absmax_dev(ctx, At->rows, y->d, mx + 4 * f + 3));
+        MGS_TRY(mgs_spmv(Aa, ones, y)); MGS_TRY(k_absmax_dev(ctx, Aa->rows, y->d, mx + 4 * f + 1));
+      }
+      MGS_HIP(ctx, hipMemcpyAsync(hf.data(), mx, sizeof(unsigned long long) * hf.size(), hipMemcpyDeviceToHost, ctx->stream));
+      MGS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+      return MGS_OK;
+    };
+    const int rcf = runf();
+    if (rcf != MGS_OK) hipStreamSynchronize(ctx->stream);
+    mgs_vec_destroy(ones); mgs_vec_destroy(y); mgs_csr_destroy(At); mgs_csr_destroy(Aa);
+    if (mx) mgs_hip_free(mx);
+    if (rcf != MGS_OK) return rcf;
+    for (int f = 0; f < A->nsf->nfields; ++f) {
+      double v[4];
+      for (int q = 0; q < 4; ++q) memcpy(&v[q], &hf[4 * (size_t)f + q], sizeof(double));
+      const double d0 = v[1] != 0.0 ? v[0] / v[1] : 0.0, d1 = v[3] != 0.0 ? v[2] / v[3] : 0.0;
+      if (!(d0 <= out[0])) out[0] = d0;      // (a NaN wins)
+      if (!(d1 <= out[1])) out[1] = d1;
+    }
+    return MGS_OK;
+  }
   auto run = [&]() -> int {
     MGS_TRY(mgs_vec_create(ctx, nmax, &ones)); MGS_TRY(mgs_vec_create(ctx, nmax, &y));
     MGS_TRY(mgs_dev_alloc(ctx, &mx, 4));
@@ -592,6 +664,20 @@ int mgs_vec_project_const(mgs_vec *v, double *mean, double *nrm2) {
   if (mean) { *mean = 0.0; if (v->n > 0) MGS_TRY(k_project_const_mean(v->ctx, mean)); }
   return MGS_OK;
 }
+int mgs_vec_project_fields(mgs_vec *v, const mgs_csr *A, double *means, double *nrm2) {
+  MGS_CHECK(nullptr, v && A, MGS_ERR_INVALID, "mgs_vec_project_fields: NULL argument");
+  mgs_ctx *ctx = A->ctx;
+  MGS_CHECK(ctx, A->nullspace == MGS_NULLSPACE_FIELDS && A->nsf, MGS_ERR_INVALID, "mgs_vec_project_fields: the matrix carries null-space kind %d, not MGS_NULLSPACE_FIELDS", A->nullspace);
+  MGS_CHECK(ctx, v->ctx == ctx && v->n >= A->rows, MGS_ERR_INVALID, "mgs_vec_project_fields: a vector of %lld entries (or of another context), the matrix has %d rows", (long long)v->n, A->rows);
+  double d2[2] = {0.0, 0.0};
+  MGS_TRY(k_project_fields(ctx, A->nsf, A->rows, v->d, true, nrm2 != nullptr, nrm2 ? d2 : nullptr));
+  if (nrm2) *nrm2 = std::sqrt(d2[0]);
+  if (means) {
+    MGS_HIP(ctx, hipMemcpyAsync(means, A->nsf->means, sizeof(double) * (size_t)A->nsf->nfields, hipMemcpyDeviceToHost, ctx->stream));
+    MGS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return MGS_OK;
+}
 int mgs_halo_pack(mgs_ctx *ctx, const mgs_vec *x, const int *send_idx_dev, int64_t n_send, double *send_buf_dev) {
   return k_gather(ctx, x->d, send_idx_dev, n_send, send_buf_dev);
 }
@@ -642,6 +728,7 @@ static void level_free(mgs_level &L) {
   if (L.nx) { if (L.nx->send_idx) mgs_hip_free(L.nx->send_idx); if (L.nx->sendbuf) mgs_hip_free(L.nx->sendbuf); delete L.nx; L.nx = nullptr; }
   mgs_vec_destroy(L.kc1); mgs_vec_destroy(L.kv1); mgs_vec_destroy(L.kc2); mgs_vec_destroy(L.kv2); mgs_vec_destroy(L.kr);
   if (L.kscal) mgs_hip_free(L.kscal);
+  if (L.ns_lab) mgs_hip_free(L.ns_lab);
   L = mgs_level();
 }
 void mgs_drop_graph(mgs_hier *h) {
@@ -979,11 +1066,70 @@ static int nullspace_check(mgs_hier *h, const char *who) {
   return MGS_OK;
 }
 
+// Field-wise null space declared on the fine operator: the structural refusals of the constant kind without the "every row aggregated" rule (rows
+// labelled −1 may stay outside), then — build = true — the coarse labels level by level with their check kernel (k_coarse_labels) and the
+// coarsest level's rows per field.  mgs_hier_refresh keeps the labels (they depend on the pattern only) and checks the structure alone.
+static bool hier_nullspace_fields(const mgs_hier *h) { return h->lev[0].A->nullspace == MGS_NULLSPACE_FIELDS && h->lev[0].A->nsf; }
+static int nullspace_fields_prepare(mgs_hier *h, const char *who, bool build) {
+  mgs_ctx *ctx = h->ctx;
+  const int nl = (int)h->lev.size();
+  const mgs_nsfields *F = h->lev[0].A->nsf;
+  MGS_CHECK(ctx, !(h->halo || h->halo_begin || h->halo_fused || h->native || h->ntail || h->coarse), MGS_ERR_INVALID,
+            "%s: field-wise null space declared on a row-sharded hierarchy (halo callbacks, native plans or tail)", who);
+  for (int l = 0; l < nl; ++l) {
+    const mgs_level &L = h->lev[l];
+    MGS_CHECK(ctx, L.A->cols == L.A->rows && !L.nx, MGS_ERR_INVALID, "%s: field-wise null space declared, level %d is a row shard (halo columns or a native plan)", who, l);
+    MGS_CHECK(ctx, l + 1 >= nl || (L.T && L.T->aggregation), MGS_ERR_INVALID, "%s: field-wise null space declared, the transfer of level %d is a general P, not an aggregation", who, l);
+  }
+  if (!build) {
+    for (int l = 1; l < nl; ++l) MGS_CHECK(ctx, h->lev[l].ns_lab, MGS_ERR_STATE, "%s: the field labels of level %d were never built (declare the fields before mgs_hier_finalize)", who, l);
+    MGS_CHECK(ctx, h->ns_nf == F->nfields, MGS_ERR_STATE, "%s: the hierarchy was finalized for %d fields, the fine operator declares %d", who, h->ns_nf, F->nfields);
+    return MGS_OK;
+  }
+  unsigned long long *bad = nullptr;
+  std::vector<unsigned long long> hb((size_t)nl, ~0ull);
+  std::vector<signed char> hl;
+  auto run = [&]() -> int {
+    MGS_TRY(mgs_dev_alloc(ctx, &bad, (size_t)nl));
+    MGS_HIP(ctx, hipMemsetAsync(bad, 0xff, sizeof(unsigned long long) * (size_t)nl, ctx->stream));
+    const signed char *lab = F->labels;
+    for (int l = 0; l + 1 < nl; ++l) {
+      mgs_level &C = h->lev[l + 1];
+      if (C.ns_lab) { MGS_HIP(ctx, hipStreamSynchronize(ctx->stream)); mgs_hip_free(C.ns_lab); C.ns_lab = nullptr; }
+      MGS_TRY(mgs_dev_alloc(ctx, &C.ns_lab, (size_t)h->lev[l].T->n_coarse + 2));
+      MGS_HIP(ctx, hipMemsetAsync(C.ns_lab, 0xff, (size_t)h->lev[l].T->n_coarse + 2, ctx->stream));
+      MGS_TRY(k_coarse_labels(ctx, h->lev[l].T, lab, C.ns_lab, bad + l));
+      lab = C.ns_lab;
+    }
+    hl.resize((size_t)h->lev.back().A->rows);
+    MGS_HIP(ctx, hipMemcpyAsync(hb.data(), bad, sizeof(unsigned long long) * (size_t)nl, hipMemcpyDeviceToHost, ctx->stream));
+    if (!hl.empty()) MGS_HIP(ctx, hipMemcpyAsync(hl.data(), lab, hl.size(), hipMemcpyDeviceToHost, ctx->stream));
+    MGS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return MGS_OK;
+  };
+  const int rc = run();
+  if (rc != MGS_OK) hipStreamSynchronize(ctx->stream);
+  if (bad) mgs_hip_free(bad);
+  MGS_TRY(rc);
+  for (int l = 0; l + 1 < nl; ++l) {
+    if (hb[l] == ~0ull) continue;
+    const long long row = (long long)(hb[l] >> 1);
+    if (hb[l] & 1ull) return mgs_fail(ctx, MGS_ERR_INVALID, "%s: field-wise null space declared, row %lld of level %d carries a label and lies outside every aggregate", who, row, l);
+    return mgs_fail(ctx, MGS_ERR_INVALID, "%s: field-wise null space declared, row %lld of level %d shares an aggregate with a row of another label", who, row, l);
+  }
+  h->ns_nf = F->nfields;
+  for (int f = 0; f < MGS_NULLSPACE_MAX_FIELDS; ++f) h->ns_ccount[f] = 0.0;
+  for (signed char c : hl) if (c >= 0 && c < MGS_NULLSPACE_MAX_FIELDS) h->ns_ccount[(int)c] += 1.0;
+  return MGS_OK;
+}
+static const signed char *coarsest_labels(const mgs_hier *h) { return h->lev.size() > 1 ? h->lev.back().ns_lab : h->lev[0].A->nsf->labels; }
+
 int mgs_hier_finalize(mgs_hier *h) {
   mgs_ctx *ctx = h->ctx;
   const mgs_csr *Ac = h->lev.back().A;
-  const bool ns = hier_nullspace_const(h);
+  const bool ns = hier_nullspace_const(h), nsf = hier_nullspace_fields(h);
   if (ns) MGS_TRY(nullspace_check(h, "mgs_hier_finalize"));
+  if (nsf) MGS_TRY(nullspace_fields_prepare(h, "mgs_hier_finalize", true));
   MGS_CHECK(ctx, Ac->rows == Ac->cols, MGS_ERR_STATE, "coarsest operator is not square");
   if (h->inv) { mgs_hip_free(h->inv); h->inv = nullptr; }
   h->nc = Ac->rows;
@@ -998,7 +1144,8 @@ int mgs_hier_finalize(mgs_hier *h) {
     h->finalized = true; mgs_drop_graph(h);
     return MGS_OK;
   }
-  MGS_TRY(k_dense_inverse(ctx, Ac, &h->inv, ns ? 1 : 0));
+  if (nsf) MGS_TRY(k_dense_inverse(ctx, Ac, &h->inv, 2, coarsest_labels(h), h->ns_ccount));
+  else MGS_TRY(k_dense_inverse(ctx, Ac, &h->inv, ns ? 1 : 0));
   h->finalized = true; mgs_drop_graph(h);
   return MGS_OK;
 }
@@ -1021,8 +1168,9 @@ int mgs_hier_refresh(mgs_hier *h) {
     MGS_CHECK(ctx, !(L.A->code && L.A->code->vtab) && !L.code_hat && !(L.code_ap && L.code_ap->vtab), MGS_ERR_INVALID,
               "mgs_hier_refresh: level %d carries a value-carrying pattern code (built under option valcode)", l);
   }
-  const bool ns = hier_nullspace_const(h);
+  const bool ns = hier_nullspace_const(h), nsf = hier_nullspace_fields(h);
   if (ns) MGS_TRY(nullspace_check(h, "mgs_hier_refresh"));
+  if (nsf) MGS_TRY(nullspace_fields_prepare(h, "mgs_hier_refresh", false));
   bool kept = true;
   if (!h->refresh_flags) MGS_TRY(mgs_dev_alloc(ctx, &h->refresh_flags, 2));
   MGS_HIP(ctx, hipMemsetAsync(h->refresh_flags, 0, 2 * sizeof(int), ctx->stream));
@@ -1048,7 +1196,7 @@ int mgs_hier_refresh(mgs_hier *h) {
   }
   if (rc == MGS_OK && !h->coarse_sweeps) {      // coarsest dense inverse, into the buffer the cached graphs know
     if (!h->inv) { kept = false; mgs_drop_graph(h); }
-    rc = k_dense_inverse(ctx, h->lev.back().A, &h->inv, ns ? 1 : 0);
+    rc = nsf ? k_dense_inverse(ctx, h->lev.back().A, &h->inv, 2, coarsest_labels(h), h->ns_ccount) : k_dense_inverse(ctx, h->lev.back().A, &h->inv, ns ? 1 : 0);
   }
   if (rc != MGS_OK) {      // half-refreshed state must not be replayed: no cycle until a later refresh (or finalize) succeeds
     h->finalized = false; h->refresh_failed = true; h->refresh_kept_graphs = 0; mgs_drop_graph(h);

@@ -131,6 +131,15 @@ struct mgs_pack7 {
 };
 static inline bool mgs_pack7_serves(const mgs_pack7 *p, bool nd) { return p && !p->dirty && p->nd == nd; }      // a launch that streams val_nd (nd) or a whole operand may read this copy
 
+// Field-wise constant null space (MGS_NULLSPACE_FIELDS, mgs_csr_set_nullspace_fields): the span of the indicators of up to 8 disjoint row sets.
+// Owned by its matrix.  means: where the projection's sum pass leaves m_f = sum_f / n_f on the device (one set of slots per matrix, not per
+// context: two matrices on one context do not collide).
+struct mgs_nsfields {
+  int nfields = 0;
+  int64_t counts[MGS_NULLSPACE_MAX_FIELDS] = {0, 0, 0, 0, 0, 0, 0, 0};   // rows per field
+  signed char *labels = nullptr;   // device, rows entries: the field of every row, −1 = in no field
+  double *means = nullptr;         // device, MGS_NULLSPACE_MAX_FIELDS slots
+};
 struct mgs_csr {
   mgs_ctx *ctx = nullptr;
   int rows = 0, cols = 0;
@@ -168,6 +177,7 @@ struct mgs_csr {
   int64_t coo_ntrip = 0;
   int coo_max_row = 0;      // most triples one row received
   int nullspace = MGS_NULLSPACE_NONE;   // mgs_csr_set_nullspace: what the caller declared (hierarchies and Krylov solvers act on it)
+  mgs_nsfields *nsf = nullptr;          // nullspace == MGS_NULLSPACE_FIELDS: the labels, the counts and the means' device slots (owned)
   struct mgs_spgemm_plan *spg = nullptr;   // matrices built by mgs_csr_spgemm (spgemm.hip; owned): the row bins its numeric pass launches over
   struct mgs_add_plan *addp = nullptr;     // matrices built by mgs_csr_add (csr_algebra.hip; owned): the row bins mgs_csr_add_numeric launches over
   struct mgs_extract_plan *extp = nullptr; // matrices built by mgs_csr_extract (extract.hip; owned): the bins it counted and, with keep_map, the source position of every entry
@@ -304,6 +314,7 @@ struct mgs_level {
   unsigned dirty = ~0u;        // OPD_* bits: the derived operands that are out of step with their sources (or do not exist yet), see below
   mgs_vec *b = nullptr, *x = nullptr;  // coarse-level rhs / solution (levels >= 1)
   mgs_native_plan *nx = nullptr;       // native RCCL halo exchange of this level (row shards)
+  signed char *ns_lab = nullptr;       // levels >= 1 under a fine operator with MGS_NULLSPACE_FIELDS: the field of every row (an aggregate takes its first member's), owned
 };
 
 // The derived operands of a level's fused passes and the ONE record of "this array is out of step with its source" (hier_operands.hip allocates, fills and frees them).
@@ -328,6 +339,8 @@ struct mgs_hier {
   // coarsest direct solve
   int nc = 0;
   double *inv = nullptr;  // nc*nc dense inverse (row-major)
+  int ns_nf = 0;                                       // MGS_NULLSPACE_FIELDS: fields and rows per field of the coarsest level (mgs_hier_finalize counts them,
+  double ns_ccount[MGS_NULLSPACE_MAX_FIELDS] = {0};    // mgs_hier_refresh regularises with the same)
   int coarse_sweeps = 0;  // > 0: coarsening stalled above the dense limit → the coarsest level is smoothed, not solved
   mgs_halo_fn halo = nullptr;
   void *halo_user = nullptr;
@@ -367,6 +380,12 @@ struct mgs_hier {
 // one (default) they are hipMalloc / hipFree.  Why: DESIGN.md §5 "process to process".
 hipError_t mgs_hip_malloc(void **p, size_t bytes);
 hipError_t mgs_hip_free(void *p);
+static inline void mgs_free_nsfields(mgs_nsfields *F) {      // the record of a field-wise null space with its two device arrays (NULL: nothing)
+  if (!F) return;
+  if (F->labels) mgs_hip_free(F->labels);
+  if (F->means) mgs_hip_free(F->means);
+  delete F;
+}
 
 // ------------------------------------------------------------------ error plumbing
 extern thread_local std::string g_mgs_last_error;
@@ -476,7 +495,12 @@ int k_maxpy_dot2(mgs_ctx *ctx, int64_t n, int K, const double *x, const double *
 int k_kc_update_r(mgs_ctx *ctx, int n, const double *scal, const double *r, const double *v1, double *rp);
 int k_kc_orth_dots(mgs_ctx *ctx, int n, bool energy, double *scal, const double *c1, const double *c2, const double *v1, const double *v2, const double *rp);
 int k_kc_combine(mgs_ctx *ctx, int n, const double *scal, const double *c1, const double *c2, double *x);
-int k_dense_inverse(mgs_ctx *ctx, const mgs_csr *A, double **inv_out, int reg_const = 0);   // *inv_out != NULL on entry: written in place; reg_const: A + (max|a_ij|/n)·1·1ᵀ
+// *inv_out != NULL on entry: written in place; reg 1: A + (max|a_ij|/n)·1·1ᵀ; reg 2: A + Σ_f (max|a_ij|/n_f)·z_f·z_fᵀ for the fields of lab (device, n entries) with fcount rows each
+int k_dense_inverse(mgs_ctx *ctx, const mgs_csr *A, double **inv_out, int reg = 0, const signed char *lab = nullptr, const double *fcount = nullptr);
+// field-wise constant null space on a hierarchy: coarse labels from the aggregation (an aggregate takes its first member's label), checked in the same launch.
+// *bad_dev (the caller sets it to ~0): min over (row << 1 | kind), kind 0 = the row's label differs from its aggregate's first member's, 1 = a labelled row outside every aggregate
+int k_coarse_labels(mgs_ctx *ctx, const mgs_xfer *T, const signed char *lab, signed char *clab, unsigned long long *bad_dev);
+int k_label_indicator(mgs_ctx *ctx, int n, const signed char *lab, int f, double *out);   // out_i = 1.0 where lab_i == f, else 0.0
 // constant null space (MGS_NULLSPACE_CONSTANT): v ← v − mean(v), two launches, the mean stays on the device; _nrm2: out_host2[0] = ‖v − mean‖² from the
 // shift pass; k_const_dev_nrm2: the same norm of a vector that is only read (‖Πb‖ of the caller's right-hand side)
 int k_project_const(mgs_ctx *ctx, int64_t n, double *v);
@@ -485,6 +509,15 @@ int k_const_dev_nrm2(mgs_ctx *ctx, int64_t n, const double *v, double *out_host2
 int k_project_const_nrm2_fold(mgs_ctx *ctx, int64_t n, double *v);         // ... the norm² stays in red_dev[MGS_DOT_BLOCKS]: enqueued only
 int k_const_dev_nrm2_fold(mgs_ctx *ctx, int64_t n, const double *v);
 int k_project_const_mean(mgs_ctx *ctx, double *mean_host);   // the mean the last projection subtracted (synchronises)
+// field-wise constant null space (MGS_NULLSPACE_FIELDS): v_i ← v_i − m[label_i] for label_i ≥ 0, m_f = (Σ_{label_i = f} v_i)/n_f left in F->means.  store = false:
+// v is only read (‖Πb‖).  nrm: ‖Πv‖² over all rows is folded into red_dev[MGS_DOT_BLOCKS] and, with out_host2, fetched (out_host2[1] = 0).  Enqueue-only without out_host2.
+int k_project_fields(mgs_ctx *ctx, const mgs_nsfields *F, int64_t n, double *v, bool store, bool nrm, double *out_host2);
+// the ONE dispatch on a matrix's null-space record (kind 1: k_project_const*, kind 2: k_project_fields; the matrix must carry one of them)
+int k_ns_project(const mgs_csr *A, int64_t n, double *v);
+int k_ns_project_nrm2(const mgs_csr *A, int64_t n, double *v, double *out_host2);       // out_host2 = NULL: the norm² stays on the device
+int k_ns_dev_nrm2(const mgs_csr *A, int64_t n, const double *v, double *out_host2);      // v only read; out_host2 = NULL: the norm² stays on the device
+// (ingest.hip) labels in device memory → checked int8 copy + rows per field; *bad_row >= 0: the lowest row whose label lies outside [−1, nfields), *bad_val its value
+int k_labels_from_device(mgs_ctx *ctx, int64_t rows, const void *labels_dev, int index_bits, int nfields, signed char **lab_out, int64_t *counts, int64_t *bad_row, long long *bad_val);
 int k_abs_inplace(mgs_ctx *ctx, int64_t n, double *v);
 int k_absmax_dev(mgs_ctx *ctx, int64_t n, const double *v, unsigned long long *amax_bits_dev);
 int k_poisson3d(mgs_ctx *ctx, int N, int plane_lo, int plane_hi, int local_cols, mgs_csr **out);
@@ -550,14 +583,15 @@ int mgs_operands_fill(mgs_hier *h, int l, unsigned want);   // refills, in place
 int mgs_halo_exchange(mgs_hier *h, int l, const double *src, double *dst, bool fused_pass = false);
 // (krylov.hip) the context's pool of work vectors for the other translation units: a vector of n entries, written before
 // it is read by whoever takes it; mgs_ws_put(NULL) does nothing — and the Krylov solvers' null-space rule
-int mgs_krylov_nullspace(const mgs_csr *A, const mgs_hier *h, const char *who, bool *ns_out);
+int mgs_krylov_nullspace(const mgs_csr *A, const mgs_hier *h, const char *who, bool *ns_out, bool serves_fields = false);
 int mgs_ws_get(mgs_ctx *ctx, int64_t n, int64_t owned, mgs_vec **out);
 void mgs_ws_put(mgs_ctx *ctx, mgs_vec *v);
 // What the host-driven solvers share (krylov.hip, minres.hip).  Work vectors are taken from the pool in the order the solver asks and go back when the solve ends, first-taken-first
 // or (reverse) last-taken-first: the next solve must find the same vectors in the same roles (graph slots are keyed by their addresses).
 struct krylov_frame {
-  mgs_ctx *ctx; mgs_hier *h; int n; bool ns, reverse;      // n: owned rows; ns: constant null space declared
+  mgs_ctx *ctx; mgs_hier *h; int n; bool ns, reverse;      // n: owned rows; ns: a null space is declared (constant, or field-wise on nsA)
   std::vector<mgs_vec *> taken;
+  const mgs_csr *nsA = nullptr;                            // the matrix whose null-space record the projections dispatch on (NULL: the constant kind)
   ~krylov_frame() {
     hipStreamSynchronize(ctx->stream);
     if (reverse) std::reverse(taken.begin(), taken.end());
@@ -570,7 +604,8 @@ struct krylov_frame {
   // ‖b‖ (bicg.cpp:80), of a zero vector 1 (:85-86); constant null space: ‖Πb‖, b only read
   int norm_b(const mgs_vec &bv, double *normb) const {
     double d2[2];
-    if (ns) { MGS_TRY(k_const_dev_nrm2(ctx, n, bv.d, d2)); *normb = std::sqrt(d2[0]); }
+    if (ns && nsA) { MGS_TRY(k_ns_dev_nrm2(nsA, n, bv.d, d2)); *normb = std::sqrt(d2[0]); }
+    else if (ns) { MGS_TRY(k_const_dev_nrm2(ctx, n, bv.d, d2)); *normb = std::sqrt(d2[0]); }
     else MGS_TRY(mgs_nrm2(&bv, normb));
     if (*normb == 0.0) *normb = 1;
     return MGS_OK;

@@ -97,21 +97,34 @@ int mgs_minres(const mgs_csr *A, mgs_vec *x, const mgs_vec *b, mgs_hier *h, int 
     MGS_CHECK(ctx, h->ctx == ctx && !h->lev.empty() && h->lev[0].n == A->rows, MGS_ERR_INVALID, "mgs_minres: the hierarchy's fine level has %d rows, A has %d",
               h->lev.empty() ? 0 : h->lev[0].n, A->rows);
   }
-  MGS_CHECK(ctx, A->nullspace == MGS_NULLSPACE_NONE && (!h || h->lev[0].A->nullspace == MGS_NULLSPACE_NONE), MGS_ERR_INVALID,
-            "mgs_minres: a declared null space is not served (the constant vector is not the null space of a saddle system)");
+  MGS_CHECK(ctx, A->nullspace != MGS_NULLSPACE_CONSTANT && (!h || h->lev[0].A->nullspace != MGS_NULLSPACE_CONSTANT), MGS_ERR_INVALID,
+            "mgs_minres: a declared constant null space is not served (the constant vector is not the null space of a saddle system; declare the fields: mgs_csr_set_nullspace_fields)");
+  bool ns = false;                                         // MGS_NULLSPACE_FIELDS: K·x = Πb, every projection through the dispatch on A's record
+  MGS_TRY(mgs_krylov_nullspace(A, h, "mgs_minres", &ns, true));
   const int n = A->rows;
   MGS_CHECK(ctx, x->n >= n && b->n >= n, MGS_ERR_INVALID, "mgs_minres: vectors shorter than %d", n);
   MGS_CHECK(ctx, x->d != b->d, MGS_ERR_INVALID, "mgs_minres: x must not alias b");
   MGS_TRY(mgs_csr_optimize(const_cast<mgs_csr *>(A)));
   mgs_vec *v[2] = {0, 0}, *zt[2] = {0, 0}, *q = 0, *w[2] = {0, 0};
-  krylov_frame f{ctx, h, n, false, true, {}};      // returned last-taken-first: the next solve takes the same vectors in the same roles
+  krylov_frame f{ctx, h, n, ns, true, {}, A};      // returned last-taken-first: the next solve takes the same vectors in the same roles
   for (mgs_vec **t : {&v[0], &zt[0], &v[1], &zt[1], &q, &w[0], &w[1]}) MGS_TRY(f.take(t, n));
   mgs_vec xv = f.view(x), bv = f.view(b);
   double normb = 0, resid = 0, s = 0, d2[2] = {0, 0};
-  auto precond = [&](const mgs_vec *in, mgs_vec *out) -> int { return h ? mgs_vcycle(h, in, out, 1) : mgs_vec_copy(in, out); };
-  auto true_residual = [&](mgs_vec *into) -> int {        // into = b − A·x, resid = ‖into‖/‖b‖
-    MGS_TRY(mgs_residual(A, &xv, &bv, into));
-    MGS_TRY(k_dot(ctx, n, into->d, into->d, &s));
+  auto precond = [&](const mgs_vec *in, mgs_vec *out) -> int {      // z̃ = M·v; fields: z̃ = Π(M·v), the preconditioner seen is ΠMΠ
+    MGS_TRY(h ? mgs_vcycle(h, in, out, 1) : mgs_vec_copy(in, out));
+    return ns ? k_ns_project(A, n, out->d) : MGS_OK;
+  };
+  auto true_residual = [&](mgs_vec *into) -> int {        // into = b − A·x, resid = ‖into‖/‖b‖; fields: x ← Πx first, into = Π(b − A·x), resid = ‖into‖/‖Πb‖
+    if (ns) {
+      double s2[2];
+      MGS_TRY(k_ns_project(A, n, xv.d));
+      MGS_TRY(mgs_residual(A, &xv, &bv, into));
+      MGS_TRY(k_ns_project_nrm2(A, n, into->d, s2));
+      s = s2[0];
+    } else {
+      MGS_TRY(mgs_residual(A, &xv, &bv, into));
+      MGS_TRY(k_dot(ctx, n, into->d, into->d, &s));
+    }
     resid = std::sqrt(s) / normb;
     return MGS_OK;
   };

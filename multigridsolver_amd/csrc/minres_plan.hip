@@ -273,16 +273,26 @@ int launch_update(mgs_minres_plan *P, const double *z, double *w_prev, const dou
   MGS_HIP(ctx, hipGetLastError());
   return MGS_OK;
 }
-int precond(mgs_minres_plan *P, const mgs_vec *in, mgs_vec *out) { return P->h ? mgs_vcycle(P->h, in, out, 1) : mgs_vec_copy(in, out); }
-// into = b − A·x with ‖into‖² folded into red_dev[RED]
-int launch_true_residual(mgs_minres_plan *P, const mgs_vec *xv, const mgs_vec *bv, mgs_vec *into) {
+// z̃ = M·v; MGS_NULLSPACE_FIELDS (P->ns): z̃ = Π(M·v), the projection enqueued behind the cycle with its means on the device, as in mgs_minres
+int precond(mgs_minres_plan *P, const mgs_vec *in, mgs_vec *out) {
+  MGS_TRY(P->h ? mgs_vcycle(P->h, in, out, 1) : mgs_vec_copy(in, out));
+  return P->ns ? k_ns_project(P->A, P->n, out->d) : MGS_OK;
+}
+// into = b − A·x with ‖into‖² folded into red_dev[RED]; fields: x ← Πx first, into = Π(b − A·x), its norm² from the shift pass.  host2: fetch (a synchronising look)
+int launch_true_residual(mgs_minres_plan *P, mgs_vec *xv, const mgs_vec *bv, mgs_vec *into, double *host2 = nullptr) {
+  if (P->ns) {
+    MGS_TRY(k_ns_project(P->A, P->n, xv->d));
+    MGS_TRY(mgs_residual(P->A, xv, bv, into));
+    return k_ns_project_nrm2(P->A, P->n, into->d, host2);
+  }
   MGS_TRY(mgs_residual(P->A, xv, bv, into));
-  return k_dot(P->ctx, P->n, into->d, into->d, nullptr);
+  return k_dot(P->ctx, P->n, into->d, into->d, host2);
 }
 // INIT: mgs_minres's start.  Nothing behind the first freeze test depends on the host: a start that is frozen runs the cycle and the fills all the same
-int enqueue_init(mgs_minres_plan *P, const mgs_vec *xv, const mgs_vec *bv, double tol, bool post) {
+int enqueue_init(mgs_minres_plan *P, mgs_vec *xv, const mgs_vec *bv, double tol, bool post) {
   mgs_ctx *ctx = P->ctx; const int64_t n = P->n;
-  MGS_TRY(k_dot(ctx, n, bv->d, bv->d, nullptr));
+  if (P->ns) MGS_TRY(k_ns_dev_nrm2(P->A, n, bv->d, nullptr));      // ‖Πb‖², b only read
+  else MGS_TRY(k_dot(ctx, n, bv->d, bv->d, nullptr));
   MGS_TRY(step(P, STEP_NORMB, 0, 0.0, false));
   MGS_TRY(launch_true_residual(P, xv, bv, &P->v[0]));                                 // v = b − A·x
   MGS_TRY(step(P, STEP_INIT_RES, 0, tol, false));
@@ -323,15 +333,15 @@ int mgs_minres_plan_create(const mgs_csr *A, mgs_hier *h, mgs_minres_plan **out)
             "mgs_minres_plan_create: needs a fixed symmetric preconditioner (nu1 == nu2, no K-cycle)");
   mgs_minres_plan *P = new mgs_minres_plan();
   int rc = P->validate(A, h, "mgs_minres_plan_create", "row shards are served by mgs_bicgstab");
-  if (rc == MGS_OK && !(A->nullspace == MGS_NULLSPACE_NONE && (!h || h->lev[0].A->nullspace == MGS_NULLSPACE_NONE)))
-    rc = mgs_fail(ctx, MGS_ERR_INVALID, "mgs_minres_plan_create: a declared null space is not served (the constant vector is not the null space of a saddle system)");
-  if (rc == MGS_OK) rc = P->allocate("mgs_minres_plan_create", 7);
+  if (rc == MGS_OK && !(A->nullspace != MGS_NULLSPACE_CONSTANT && (!h || h->lev[0].A->nullspace != MGS_NULLSPACE_CONSTANT)))
+    rc = mgs_fail(ctx, MGS_ERR_INVALID, "mgs_minres_plan_create: a declared constant null space is not served (the constant vector is not the null space of a saddle system; declare the fields: mgs_csr_set_nullspace_fields)");
+  if (rc == MGS_OK) rc = P->allocate("mgs_minres_plan_create", 7, true);
   if (rc != MGS_OK) { mgs_minres_plan_destroy(P); return rc; }
   mgs_vec *vs[7] = {&P->v[0], &P->zt[0], &P->v[1], &P->zt[1], &P->q, &P->w[0], &P->w[1]};
   for (int k = 0; k < 7; ++k) *vs[k] = P->view(k);
   // the partial sums of every reduction a solve launches, and the hierarchy's operands and both captured cycles (v[k] → z̃[k] on ones): no later call allocates
   const int64_t nb = std::max<int64_t>(mgs_row_blocks(A), mgs_blas1_grid(ctx, ((int64_t)P->n + 1) / 2));
-  rc = mgs_ensure_dot_part(ctx, 2 * std::max<int64_t>(nb, 1));
+  if (rc == MGS_OK) rc = mgs_ensure_dot_part(ctx, (P->ns ? MGS_NULLSPACE_MAX_FIELDS : 2) * std::max<int64_t>(nb, 1));      // (fields: [nfields][workgroups] partials of the projection's sum pass)
   for (int k = 0; k < 2 && h; ++k) {
     if (rc == MGS_OK) rc = k_fill(ctx, P->v[k].d, P->n, 1.0);
     if (rc == MGS_OK) rc = mgs_vcycle(h, &P->v[k], &P->zt[k], 1);
@@ -372,7 +382,6 @@ int mgs_minres_plan_solve(mgs_minres_plan *P, mgs_vec *x, const mgs_vec *b, int 
   mgs_ctx *ctx = P->ctx;
   MGS_CHECK(ctx, ahead >= 0, MGS_ERR_INVALID, "mgs_minres_plan_solve: ahead = %d < 0", ahead);
   MGS_TRY(P->check_call(x, b, "mgs_minres_plan_solve"));
-  const int n = P->n;
   mgs_vec xv, bv;
   P->begin_call(x, b, &xv, &bv, false);
   const int maxit = *max_iter;
@@ -388,10 +397,9 @@ int mgs_minres_plan_solve(mgs_minres_plan *P, mgs_vec *x, const mgs_vec *b, int 
     return MGS_OK;
   };
   auto true_residual = [&](double normb, double *resid) -> int {      // q = b − A·x, *resid = ‖q‖/‖b‖: a synchronising look, as in mgs_minres
-    double s = 0;
-    MGS_TRY(mgs_residual(P->A, &xv, &bv, &P->q));
-    MGS_TRY(k_dot(ctx, n, P->q.d, P->q.d, &s));
-    *resid = std::sqrt(s) / normb;
+    double s2[2] = {0, 0};
+    MGS_TRY(launch_true_residual(P, &xv, &bv, &P->q, s2));
+    *resid = std::sqrt(s2[0]) / normb;
     return MGS_OK;
   };
   MGS_TRY(enqueue_init(P, &xv, &bv, tl, true));

@@ -3,6 +3,9 @@ configs[4] is generated on the device by `mgs_csr_poisson3d`).
 
 `neumann3d(N)`: the 7-point Laplacian with natural boundary rows — singular, constant null space (Csr.set_nullspace("constant")).
 
+`enclosed_stokes(N)`: the blocks and row labels of a model of enclosed Stokes flow, K = [[L, Dᵀ], [D, 0]] — singular, the pressure constant
+its one null vector (Csr.set_nullspace_fields); `stokes_divergence(N)` is its D alone.
+
 `convdiff3d(N)`: a labelled STAND-IN for the reference's `matvf3dSky*` / `CSky3d*` problem class (the paper's nonsymmetric
 convection-diffusion with "skyscraper" coefficient jumps, docs/AGMG_For_Convection_Diffusion.pdf §5; matrices/CSky3d30.mtx is the 30^3
 member bundled with the reference, the 80^3 one is absent — /root/reference/.MISSING_LARGE_BLOBS).  It is NOT one of those matrices:
@@ -119,7 +122,46 @@ def neumann3d(N):
     return rowptr.astype(np.int32), cand_col[present].astype(np.int32), cand_val[present]
 
 
-CSKY_ROWSUM_MARGIN = 2.86e-6      # the bundled CSky3d30's printed interior row sums, relative to the diagonal (median; 95 % of its interior rows)
+def _poisson3d_dirichlet(N):
+    """7-point Dirichlet Poisson matrix of N^3 (diagonal 6, −1 towards every neighbour inside the grid), rows e = (i*N + j)*N + k"""
+    rp, ci, v = neumann3d(N)
+    v = v.copy(); v[ci == np.repeat(np.arange(N ** 3), np.diff(rp))] = 6.0
+    return rp, ci, v
+
+
+def stokes_divergence(N):
+    """D = [I − Z₁, I − Z_N, I − Z_{N²}] of enclosed_stokes(N) alone, m × 3m in CSR form (rowptr i32, col i32, val f64), sorted columns"""
+    if N < 2:
+        raise ValueError("stokes_divergence: N >= 2 (at N = 1 the shifts are the identity)")
+    m = N ** 3
+    rows = np.arange(m, dtype=np.int64)
+    cols = np.empty((m, 6), dtype=np.int64); vals = np.empty((m, 6))
+    for q, k in enumerate((1, N, N * N)):
+        cols[:, 2 * q] = q * m + rows; vals[:, 2 * q] = 1.0
+        cols[:, 2 * q + 1] = q * m + (rows + k) % m; vals[:, 2 * q + 1] = -1.0
+    order = np.argsort(cols, axis=1, kind="stable")
+    cols = np.take_along_axis(cols, order, axis=1); vals = np.take_along_axis(vals, order, axis=1)
+    return np.arange(0, 6 * m + 1, 6, dtype=np.int32), cols.reshape(-1).astype(np.int32), vals.reshape(-1)
+
+
+def enclosed_stokes(N):
+    """A model of enclosed Stokes flow (velocity prescribed on the whole boundary): K = [[L, Dᵀ], [D, 0]] with L = block_diag(P, P, P),
+    P the 7-point Dirichlet Poisson matrix of N³, and D = [I − Z₁, I − Z_N, I − Z_{N²}] (m × 3m, m = N³, Z_k the cyclic shift by k
+    positions: (Z_k x)_i = x_{(i+k) mod m}).  Every column of D sums to 0, so K·(0, 1_p) = 0: the pressure is fixed up to a constant,
+    K has exactly that one null vector, and S = D·diag(L)⁻¹·Dᵀ is a 7-point periodic Laplacian divided by 6 with the same one.
+    Returns a dict of host blocks in CSR form (rowptr i32, col i32, val f64) — "P", "L", "D" — with "m", "n" = 4m and "labels"
+    (int64, −1 on the 3m velocity rows, 0 on the m pressure rows: Csr.set_nullspace_fields on K and on block_diag(L, S))."""
+    m = N ** 3
+    P = _poisson3d_dirichlet(N)
+    prp, pci, pv = P
+    L = (np.concatenate([prp[:-1].astype(np.int64) + q * len(pci) for q in range(3)] + [[3 * len(pci)]]).astype(np.int32),
+         np.concatenate([pci.astype(np.int64) + q * m for q in range(3)]).astype(np.int32), np.tile(pv, 3))
+    D = stokes_divergence(N)
+    labels = np.concatenate([np.full(3 * m, -1, dtype=np.int64), np.zeros(m, dtype=np.int64)])
+    return {"P": P, "L": L, "D": D, "m": m, "n": 4 * m, "labels": labels}
+
+
+CSKY_ROWSUM_MARGIN = 2.86e-6     # the bundled CSky3d30's printed interior row sums, relative to the diagonal (median; 95 % of its interior rows)
 
 
 def csky3d(N, velocity=1000.0, workers=None, digits=6, rowsum_floor=None):
