@@ -1195,6 +1195,61 @@ int mgs_hier_post_pass(mgs_hier *h, int level, const mgs_vec *bvec, const mgs_ve
  * kernel starts, which then hides behind the fine level's pre pass, and a flexible Krylov method's ten direction vectors no longer overrun the (b, x) cache.  Same kernels, same bits. */
 int mgs_hier_graph_info(const mgs_hier *h, int64_t out[4]);
 
+/* ---- block vectors: two tall-skinny passes over lists of columns (blockvec.hip) --------------------------------------------------------
+ * Nearest reference line: none — the reference works on one vector at a time (bicg.cpp:64-72).  A block is a list of mgs_vec columns; there
+ * is no container type, and mgs_spmv, mgs_vcycle and the projections keep working on each column.  n: the leading entries of every column
+ * that take part.
+ * mgs_vecs_gram: G[a·q + b] = Σ_{i<n} U_a[i]·V_b[i], G on the host, row-major p × q; synchronises.  One streaming pass per tile of at most
+ *   8 × 8 entries reads the tile's at most 16 columns once — 16 bytes per lane and stream where every column of the call starts on 16 bytes
+ *   (and option "blas1_vec" is on), 8 bytes otherwise, an odd last element on one lane.  Every product and every sum is rounded on its own;
+ *   partials lie in a fixed [tile entries][workgroups] layout, no atomics, folded lanes → wave → workgroup → one workgroup per entry: two
+ *   identical calls give identical bits (tests/eig_ref.py restates them).  With the same list on both sides (p == q, the same vectors in the
+ *   same order) only the tiles on and above the diagonal are computed and mirrored: G is symmetric bit for bit.
+ * mgs_vecs_combine: Y_j[i] = Σ_{a<k} C[a·q + j]·S_a[i] for i < n, C on the host, row-major k × q, copied asynchronously into a slot the
+ *   context owns (C itself is read before the call returns: the caller may reuse or free it at once); enqueued, no host wait.  Y_j[i] = fl(…fl(fl(C[0][j]·S_0[i]) + fl(C[1][j]·S_1[i])) + …), a ascending.  One pass reads the k
+ *   columns and writes the q.  An output may be the same vector as an input (the same start address): every input element of a row is
+ *   loaded before any output of that row is stored.
+ * mgs_vecs_info: the launch decisions of the last of the two calls on ctx — out[0] workgroups of a pass, out[1] / out[2] the tile's rows /
+ *   columns (combine: k / q), out[3] = 1 for the 16-byte path, out[4] passes launched (Gram: tiles), out[5] = 1 when a Gram call took the
+ *   symmetric route, out[6] = 1 after a Gram call and 2 after a combine, out[7] = 0.
+ * MGS_ERR_INVALID, with a message, nothing launched: a NULL argument or a NULL column; p or q outside 1..MGS_VECS_MAX (combine: k outside
+ *   1..MGS_VECS_MAX, q outside 1..16); a column shorter than n or of another context; n < 1; combine: two outputs that overlap or are the
+ *   same vector, an output that overlaps an input without being that vector. */
+#define MGS_VECS_MAX 24
+int mgs_vecs_gram(mgs_ctx *ctx, int64_t n, int p, const mgs_vec *const *U, int q, const mgs_vec *const *V, double *G);
+int mgs_vecs_combine(mgs_ctx *ctx, int64_t n, int k, const mgs_vec *const *S, int q, mgs_vec *const *Y, const double *C);
+int mgs_vecs_info(const mgs_ctx *ctx, int64_t out[8]);
+
+/* ---- the m smallest eigenpairs of a symmetric operator: LOBPCG with the cycle as preconditioner (eig.hip) -------------------------------
+ * Nearest reference line: none — the reference solves linear systems only.  Method: Knyazev, SISC 23 (2001), with soft locking.
+ * A is symmetric (the caller's responsibility, as in mgs_pcg).  X: m start vectors on entry, the Ritz vectors on return — orthonormal,
+ * ordered by ascending theta.  resid[j] = ‖A·x_j − θ_j·x_j‖₂ / ‖A‖∞, ‖A‖∞ the largest row sum of |a_ij| (computed once on the device); what
+ * is returned is formed from a fresh A·X after the last update, never from the recurrences.  *tol in: the bar every resid[j] must stay
+ * below; out: the largest resid[j].  *max_iter in: the cap; out: the iterations done.
+ * *status: 0 all m residuals below the bar (decided on the true residuals); 1 max_iter reached; 2 the start block is rank deficient — a
+ * Cholesky pivot of XᵀX is not greater than 8·m·DBL_EPSILON·max diag (the dense coarse solve's rule with m for n) — 0 iterations, X untouched
+ * (with a declared null space the rule is applied to (ΠX)ᵀ(ΠX), formed on copies); 3 the trial basis was still rank deficient by that rule after P was dropped,
+ * or a NaN or Inf appeared.
+ * One iteration: R_j = A·x_j − θ_j·x_j; columns below the bar are soft-locked (they stay in X, get no W or P column); W_j = M·R_j for the
+ * others, W ← W − X·(XᵀW), Cholesky QR on W, and on P on its own (the pivot rule on the Gram matrix of the
+ * normalised columns: residual columns differ in length by orders of magnitude, which is no rank deficiency); A·W by SpMV, A·X and A·P carried by the combine that updates X and P;
+ * SᵀAS and SᵀS for S = [X W P] through mgs_vecs_gram; the generalised problem of order at most 24 on the host (Cholesky, cyclic Jacobi; no
+ * LAPACK); one coefficient matrix gives the new X, P, A·X and A·P.  When SᵀS fails the pivot rule the iteration is redone on [X W].
+ * h: NULL (M = I) or a hierarchy that is a fixed symmetric operator, by mgs_pcg's rule with flexible = 0.  The cycle is applied to every
+ * column through one fixed (residual, result) pair of work vectors, so it replays from one cached graph whatever m and the iteration count.
+ * Work vectors: 5m + 2 from the context's pool.
+ * A declared MGS_NULLSPACE_CONSTANT or MGS_NULLSPACE_FIELDS: X ← ΠX first, W_j ← Π(M·R_j) after every preconditioner application (h = NULL
+ * included); the m smallest eigenpairs on the complement come back.  The hierarchy must carry the same kind, by mgs_pcg's rule.
+ * mgs_eig_info, of the last call on ctx: out[0] iterations, out[1] cycles applied, out[2] SpMVs, out[3] restarts without P, out[4] columns
+ * locked at the end, out[5] work vectors taken, out[6] hipGraph captures made during the call, out[7] = 0.
+ * MGS_ERR_INVALID, with a message, nothing launched: a NULL argument; m outside 1..MGS_EIG_MAX_BLOCK; rows < 3m + the declared null
+ * vectors; a matrix that is not square; a row shard (the criteria of mgs_pcg_plan_create); columns of X that are the same vector, overlap,
+ * or are shorter than A's rows; nu1 != nu2 or a K-cycle; a hierarchy whose null-space kind differs from A's.
+ * Not served: A·x = λ·B·x, the largest eigenvalues, row shards, a device-resident Rayleigh–Ritz, null vectors that are not indicators. */
+#define MGS_EIG_MAX_BLOCK 8
+int mgs_eig_lobpcg(const mgs_csr *A, mgs_hier *h, int m, mgs_vec *const *X, double *theta, double *resid, int *max_iter, double *tol, int *status);
+int mgs_eig_info(const mgs_ctx *ctx, int64_t out[8]);
+
 /* kernel-variant knobs for A/B measurements (initial values of every context: environment MGS_OPTIONS="key=value,...").  key: "spmv_variant", "xcd_remap", "nontemporal",
  * "graph", "strip", "fuse", "nt_store" (smallest operator, in rows, whose row-block kernels store their outputs with the `nt` hint; default 1000000,
  * 0 = never), "stage_unroll" (row-block kernels stage their value slice without a loop in front of the barrier; default 1), "rowptr_scan" (pattern-coded row blocks take a row's

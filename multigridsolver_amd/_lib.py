@@ -21,6 +21,8 @@ HALO_FUSED_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, c_dbl_p, C.c_int)
 P2P_HANDLE_BYTES = 96          # MGS_P2P_HANDLE_BYTES
 MGS_SPGEMM_MAX_ROW = 8192      # most distinct columns one row of a product may hold
+MGS_VECS_MAX = 24              # most columns of one side of mgs_vecs_gram / inputs of mgs_vecs_combine (its outputs: 16)
+MGS_EIG_MAX_BLOCK = 8          # most eigenpairs of one mgs_eig_lobpcg call
 
 # name -> (restype, argtypes); every symbol declared in include/mgs.h
 PROTOTYPES = {
@@ -185,6 +187,11 @@ PROTOTYPES = {
     "mgs_minres_plan_enqueue": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double]),
     "mgs_minres_plan_result": (C.c_int, [C.c_void_p, c_int_p, c_dbl_p, c_dbl_p, c_int_p]),
     "mgs_minres_plan_info": (C.c_int, [C.c_void_p, c_i64_p]),
+    "mgs_vecs_gram": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), c_dbl_p]),
+    "mgs_vecs_combine": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), c_dbl_p]),
+    "mgs_vecs_info": (C.c_int, [C.c_void_p, c_i64_p]),
+    "mgs_eig_lobpcg": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_dbl_p, c_dbl_p, c_int_p, c_dbl_p, c_int_p]),
+    "mgs_eig_info": (C.c_int, [C.c_void_p, c_i64_p]),
     "mgs_guess_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "mgs_guess_destroy": (C.c_int, [C.c_void_p]),
     "mgs_guess_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_dbl_p]),

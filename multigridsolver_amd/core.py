@@ -1154,3 +1154,52 @@ def minres(A, x, b, hier=None, max_iter=10000, tol=1e-6):
     mi, t, st = C.c_int(max_iter), C.c_double(tol), C.c_int(-1)
     check(lib().mgs_minres(A.h, x.h, b.h, hier.h if hier else None, C.byref(mi), C.byref(t), C.byref(st)), A.ctx.h)
     return st.value, mi.value, t.value
+
+
+def _handles(vecs):
+    return (C.c_void_p * max(len(vecs), 1))(*[v.h for v in vecs])
+
+
+def vecs_gram(U, V, n=None):
+    """G = UᵀV for two lists of Vec columns (mgs_vecs_gram) → numpy (len(U), len(V)); one pass per 8 × 8 tile, bit-reproducible; the same
+    list on both sides gives a G that is symmetric bit for bit.  n: leading entries that take part (default: len(U[0]))"""
+    ctx = U[0].ctx
+    n = len(U[0]) if n is None else n
+    G = np.empty((len(U), len(V)))
+    check(lib().mgs_vecs_gram(ctx.h, n, len(U), _handles(U), len(V), _handles(V), _dp(G)), ctx.h)
+    return G
+
+
+def vecs_combine(S, Cm, out, n=None):
+    """out_j = Σ_a Cm[a, j]·S_a for lists of Vec columns (mgs_vecs_combine), added in ascending a, each product and sum rounded on its own;
+    an output may be one of the inputs (the whole vector).  Enqueued, no host wait.  → out"""
+    ctx = S[0].ctx
+    n = len(S[0]) if n is None else n
+    Cm = np.ascontiguousarray(Cm, dtype=np.float64).reshape(len(S), len(out))
+    check(lib().mgs_vecs_combine(ctx.h, n, len(S), _handles(S), len(out), _handles(out), _dp(Cm)), ctx.h)
+    return out
+
+
+def vecs_info(ctx):
+    """launch decisions of the last vecs_gram / vecs_combine: [0] workgroups, [1] [2] tile rows / columns (combine: inputs / outputs),
+    [3] 16-byte path, [4] passes, [5] symmetric route, [6] 1 Gram / 2 combine, [7] 0"""
+    out = (C.c_int64 * 8)(); check(lib().mgs_vecs_info(ctx.h, out), ctx.h); return [int(v) for v in out]
+
+
+def lobpcg(A, X, hier=None, max_iter=200, tol=1e-6):
+    """the len(X) smallest eigenpairs of the symmetric A by LOBPCG with hier's cycle as preconditioner (mgs_eig_lobpcg) →
+    (status, iterations, theta, resid).  X: list of Vec, start vectors in, orthonormal Ritz vectors out (ascending theta);
+    resid[j] = ‖A·x_j − θ_j·x_j‖₂/‖A‖∞ from a fresh A·X; status 0 all below tol / 1 max_iter / 2 start block rank deficient /
+    3 trial basis rank deficient or not a number.  A declared null space (Csr.set_nullspace / set_nullspace_fields): the eigenpairs on its
+    complement"""
+    m = len(X)
+    th, rs = np.zeros(max(m, 1)), np.zeros(max(m, 1))
+    mi, t, st = C.c_int(max_iter), C.c_double(tol), C.c_int(-1)
+    check(lib().mgs_eig_lobpcg(A.h, hier.h if hier else None, m, _handles(X), _dp(th), _dp(rs), C.byref(mi), C.byref(t), C.byref(st)), A.ctx.h)
+    return st.value, mi.value, th[:m].copy(), rs[:m].copy()
+
+
+def eig_info(ctx):
+    """counters of the last lobpcg on ctx: [0] iterations, [1] cycles, [2] SpMVs, [3] restarts without P, [4] columns locked at the end,
+    [5] work vectors, [6] hipGraph captures made during the call, [7] 0"""
+    out = (C.c_int64 * 8)(); check(lib().mgs_eig_info(ctx.h, out), ctx.h); return [int(v) for v in out]

@@ -507,6 +507,42 @@ inline int MINRESiml(const SMatrix &, Vector &x, const Vector &b, const MultiGri
   return MINRESiml(M.matrix(), x, b, M, max_iter, tol);
 }
 
+// ---------------------------------------------------------------- block vectors and the smallest eigenpairs (mgs.h: mgs_vecs_*, mgs_eig_lobpcg)
+// No reference counterpart: the reference solves linear systems, one vector at a time.  A block is a std::vector<Vector>.
+// G = UᵀV, row-major U.size() × V.size(), bit-reproducible; the same block on both sides gives a G that is symmetric bit for bit
+inline std::vector<double> vecsGram(const std::vector<Vector> &U, const std::vector<Vector> &V) {
+  std::vector<const mgs_vec *> u, v;
+  for (const Vector &c : U) u.push_back(c.handle());
+  for (const Vector &c : V) v.push_back(c.handle());
+  std::vector<double> G(U.size() * V.size());
+  check(mgs_vecs_gram(context(), U.empty() ? 0 : U[0].size(), (int)u.size(), u.data(), (int)v.size(), v.data(), G.data()), context());
+  return G;
+}
+// Y_j = Σ_a C[a·Y.size() + j]·S_a, added in ascending a; Y may be S itself (or share whole columns with it)
+inline void vecsCombine(const std::vector<Vector> &S, const std::vector<double> &C, std::vector<Vector> &Y) {
+  if (C.size() != S.size() * Y.size()) throw Error(MGS_ERR_INVALID, "vecsCombine: C is not S.size() x Y.size()");
+  std::vector<const mgs_vec *> s;
+  std::vector<mgs_vec *> y;
+  for (const Vector &c : S) s.push_back(c.handle());
+  for (Vector &c : Y) y.push_back(c.out());
+  check(mgs_vecs_combine(context(), S.empty() ? 0 : S[0].size(), (int)s.size(), s.data(), (int)y.size(), y.data(), C.data()), context());
+}
+// The X.size() smallest eigenpairs of the symmetric A (mgs_eig_lobpcg), in the calling shape of CGiml: X holds the start vectors and comes back with
+// the orthonormal Ritz vectors, theta ascending, max_iter and tol are written back (tol: the largest ‖A·x_j − θ_j·x_j‖₂/‖A‖∞), the status is returned
+// (0 converged / 1 max_iter / 2 start block rank deficient / 3 trial basis rank deficient or not a number).  M: NULL for none.
+inline int LOBPCGiml(const DeviceMatrix &A, std::vector<Vector> &X, std::vector<double> &theta, std::vector<double> &resid, const MultiGridPrecond *M, int &max_iter, double &tol) {
+  std::vector<mgs_vec *> x;
+  for (Vector &c : X) x.push_back(c.out());
+  theta.assign(X.size(), 0.0); resid.assign(X.size(), 0.0);
+  int status = -1;
+  check(mgs_eig_lobpcg(A.handle(), M && M->use_preconditioner() ? M->handle() : nullptr, (int)x.size(), x.data(), theta.data(), resid.data(), &max_iter, &tol, &status), context());
+  return status;
+}
+inline int LOBPCGiml(const DeviceMatrix &A, std::vector<Vector> &X, std::vector<double> &theta, const MultiGridPrecond &M, int &max_iter, double &tol) {
+  std::vector<double> resid;
+  return LOBPCGiml(A, X, theta, resid, &M, max_iter, tol);
+}
+
 // ---------------------------------------------------------------- projected initial guesses (mgs.h: mgs_guess)
 // No reference counterpart: the reference solves one right-hand side (bicg.cpp:159-166).  For a caller who solves with the same operator
 // again and again:   SolutionGuess guess(A, MGS_GUESS_ENERGY);   per step:  guess.apply(b, x);  CGiml(A, x, b, M, it, tol);  guess.update(x);

@@ -1,4 +1,4 @@
-// blas1.hpp — what every BLAS-1 pass and deterministic reduction is built from (blas1.hip, the Krylov plans through krylov_plan.hpp, guess.hip):
+// blas1.hpp — what every BLAS-1 pass and deterministic reduction is built from (blas1.hip, the Krylov plans through krylov_plan.hpp, guess.hip, the block passes of blockvec.hip):
 // the 16-byte lane type with its streaming store, the alignment and store-mode predicates of the launchers, and the folds that decide the bits
 // of every sum — lanes → wave → workgroup partial, and partials → result.  Each fold is written here once; a kernel brings its own loop.
 //

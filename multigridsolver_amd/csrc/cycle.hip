@@ -446,6 +446,7 @@ static int capture_exec(mgs_hier *h, hipGraphExec_t *exec, int *rc, hipError_t *
   hipGraph_t g = nullptr;
   MGS_HIP(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
   h->capturing = true;
+  ++ctx->graph_captures;
   *rc = body();
   h->capturing = false;
   *e = hipStreamEndCapture(ctx->stream, &g);

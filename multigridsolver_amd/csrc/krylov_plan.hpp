@@ -58,18 +58,8 @@ struct Plan {
 
   // create: a square unsharded operator, a finalized hierarchy of the same kind on the same context
   int validate(const mgs_csr *A_, mgs_hier *h_, const char *who, const char *served_by) {
+    MGS_TRY(mgs_check_unsharded(A_, h_, who, served_by));
     mgs_ctx *c = A_->ctx;
-    MGS_CHECK(c, A_->rows == A_->cols && !c->ncomm && !c->allreduce, MGS_ERR_INVALID, "%s: the matrix is %d x %d%s (%s)", who, A_->rows, A_->cols,
-              A_->cols > A_->rows ? ", halo columns: a row shard" : (A_->rows == A_->cols ? ", on a context that sums over ranks" : ", not square"), served_by);
-    MGS_CHECK(c, A_->rows > 0, MGS_ERR_INVALID, "%s: the matrix has no rows", who);
-    if (h_) {
-      bool shard = h_->halo || h_->halo_begin || h_->halo_end || h_->halo_fused || h_->coarse || h_->native || h_->ntail;
-      for (const mgs_level &L : h_->lev) shard = shard || L.nx || (L.A && L.A->cols > L.A->rows);
-      MGS_CHECK(c, !shard, MGS_ERR_INVALID, "%s: the hierarchy has halo columns, exchange callbacks, native plans or a tail (%s)", who, served_by);
-      MGS_CHECK(c, h_->ctx == c && !h_->lev.empty() && h_->lev[0].n == A_->rows, MGS_ERR_INVALID, "%s: the hierarchy's fine level has %d rows, A has %d", who,
-                h_->lev.empty() ? 0 : h_->lev[0].n, A_->rows);
-      MGS_CHECK(c, h_->finalized, MGS_ERR_STATE, "%s: call mgs_hier_finalize first", who);
-    }
     ctx = c; A = A_; h = h_; n = A_->rows;
     return MGS_OK;
   }

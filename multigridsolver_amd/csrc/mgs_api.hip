@@ -161,6 +161,9 @@ int mgs_ctx_destroy(mgs_ctx *c) {
   c->ws_free.clear();
   if (c->red_dev) mgs_hip_free(c->red_dev);
   if (c->dot_part) mgs_hip_free(c->dot_part);
+  if (c->vecs_dev) mgs_hip_free(c->vecs_dev);
+  if (c->vecs_host) hipHostFree(c->vecs_host);
+  for (hipEvent_t e : c->vecs_ev) if (e) hipEventDestroy(e);
   if (c->red_host) hipHostFree(c->red_host);
   if (c->own_stream) hipStreamDestroy(c->stream);
   if (c->comm_stream) hipStreamDestroy(c->comm_stream);

@@ -30,6 +30,9 @@ constexpr int MGS_RED_VALS = 32;   // results one reduction can hand to the host
 // (the first one: the mean of the last k_project_const)
 constexpr int MGS_DOT_BLOCKS = 4096;
 constexpr int MGS_RED_CAP = MGS_DOT_BLOCKS + 2 * MGS_RED_VALS;
+constexpr int MGS_ABSMAX_SLOT = MGS_DOT_BLOCKS + MGS_RED_VALS + 8;   // a device-only scalar: the bits of max_i Σ_j |a_ij| while mgs_eig_lobpcg forms ‖A‖∞ (eig.hip)
+static_assert(MGS_ABSMAX_SLOT > MGS_DOT_BLOCKS + MGS_RED_VALS && MGS_ABSMAX_SLOT < MGS_RED_CAP, "the ‖A‖∞ slot lies among the device-only scalars of mgs_ctx::red_dev, behind the mean of k_project_const");
+constexpr int MGS_VECS_RING = 8;     // pinned staging slots for the coefficients of mgs_vecs_combine (blockvec.hip)
 struct mgs_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -102,6 +105,14 @@ struct mgs_ctx {
   mgs_allreduce_fn allreduce = nullptr;
   void *allreduce_user = nullptr;
   mgs_launch_report *report = nullptr;   // diagnostics (mgs_hier_post_pass, mgs_hier_pre_pass_info): the next fused-pass launch describes itself here; NULL in every cycle
+  // block-vector passes (blockvec.hip): the device slot for a Gram matrix's folded entries and a combine's coefficients, allocated at the first call
+  double *vecs_dev = nullptr;
+  double *vecs_host = nullptr;                       // MGS_VECS_RING pinned slots: a combine copies the caller's coefficients here before it returns, the device copy reads the slot
+  hipEvent_t vecs_ev[MGS_VECS_RING] = {};            // recorded behind each slot's device copy; waited for before the slot is written again
+  int vecs_next = 0;
+  int64_t vecs_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // mgs_vecs_info: launch decisions of the last mgs_vecs_gram / mgs_vecs_combine
+  int64_t eig_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};    // mgs_eig_info: counters of the last mgs_eig_lobpcg (eig.hip)
+  int64_t graph_captures = 0;                        // whole-cycle hipGraph captures made on this context (cycle.hip: capture_exec)
 };
 // the one statement that fills mgs_launch_report: what a fused-pass launcher launched (NULL in every cycle: nothing written)
 static inline void report_launch(const mgs_ctx *ctx, int kernel, int u, int flags, int capv, int capi, int bits = 0, const int *tptr = nullptr) {
@@ -611,6 +622,23 @@ struct krylov_frame {
     return MGS_OK;
   }
 };
+// What the solvers that serve no row shard check first (the Krylov plans through krylov_plan.hpp, mgs_eig_lobpcg): a square matrix on a context that does not
+// sum over ranks, and a finalized hierarchy of its size on the same context without halo columns, exchange callbacks, native plans or a tail.
+static inline int mgs_check_unsharded(const mgs_csr *A, const mgs_hier *h, const char *who, const char *served_by) {
+  mgs_ctx *c = A->ctx;
+  MGS_CHECK(c, A->rows == A->cols && !c->ncomm && !c->allreduce, MGS_ERR_INVALID, "%s: the matrix is %d x %d%s (%s)", who, A->rows, A->cols,
+            A->cols > A->rows ? ", halo columns: a row shard" : (A->rows == A->cols ? ", on a context that sums over ranks" : ", not square"), served_by);
+  MGS_CHECK(c, A->rows > 0, MGS_ERR_INVALID, "%s: the matrix has no rows", who);
+  if (h) {
+    bool shard = h->halo || h->halo_begin || h->halo_end || h->halo_fused || h->coarse || h->native || h->ntail;
+    for (const mgs_level &L : h->lev) shard = shard || L.nx || (L.A && L.A->cols > L.A->rows);
+    MGS_CHECK(c, !shard, MGS_ERR_INVALID, "%s: the hierarchy has halo columns, exchange callbacks, native plans or a tail (%s)", who, served_by);
+    MGS_CHECK(c, h->ctx == c && !h->lev.empty() && h->lev[0].n == A->rows, MGS_ERR_INVALID, "%s: the hierarchy's fine level has %d rows, A has %d", who,
+              h->lev.empty() ? 0 : h->lev[0].n, A->rows);
+    MGS_CHECK(c, h->finalized, MGS_ERR_STATE, "%s: call mgs_hier_finalize first", who);
+  }
+  return MGS_OK;
+}
 template <class T>
 static inline int mgs_dev_alloc(mgs_ctx *ctx, T **p, size_t count) {
   *p = nullptr;

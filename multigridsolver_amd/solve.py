@@ -50,6 +50,10 @@ def main(argv=None):
     ap.add_argument("--nullspace", choices=["none", "constant"], default="none",
                     help="constant: A·1 = 0 and 1ᵀ·A = 0 (pure-Neumann operators, graph Laplacians) — regularised coarsest solve, projected Krylov method, "
                          "zero-mean solution; single GPU only")
+    ap.add_argument("--eigs", type=int, default=0, metavar="K",
+                    help="instead of a solve: the K smallest eigenpairs of the symmetric A by LOBPCG (K <= 8) with the hierarchy the other options describe "
+                         "as preconditioner (V(nu, nu), no K-cycle), from random start vectors; --tol bounds |A x - theta x|/|A|_inf; no right-hand side; "
+                         "single GPU only")
     ap.add_argument("--dump-x", default=None, help="write the solution (rank order, raw little-endian f64)")
     args = ap.parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1")); rank = int(os.environ.get("RANK", "0"))
@@ -65,6 +69,8 @@ def main(argv=None):
         raise SystemExit("--fgcr-ahead N (N >= 0) goes with --solver fgcr on a single GPU")
     if args.minres_ahead is not None and (args.solver != "minres" or world > 1 or args.minres_ahead < 0):
         raise SystemExit("--minres-ahead N (N >= 0) goes with --solver minres on a single GPU")
+    if args.eigs and (world > 1 or args.eigs < 0 or args.solver is not None):
+        raise SystemExit("--eigs K (K >= 1) runs on a single GPU and takes no --solver")
     if args.solver is None:
         args.solver = "bicgstab"
     if world > 1:
@@ -89,6 +95,18 @@ def main(argv=None):
         h.coarsen(args.ktg, args.npass, args.tou).finalize().set_kcycle(args.kcycle)
         if args.operand_bits != 64:
             h.set_operand_precision(args.operand_bits)
+        if args.eigs:
+            X = [ctx.vec(rows).rand(1, j * rows) for j in range(args.eigs)]
+            ctx.sync(); t0 = time.perf_counter()
+            st, it, theta, resid = mg.lobpcg(A, X, h, args.max_iter, args.tol)
+            ctx.sync(); dt = time.perf_counter() - t0
+            sys.stderr.write("    \033[1;34m[time] \033[0m%-42s : %f.\n" % ("LOBPCG_SolveTimer", dt))
+            for j in range(args.eigs):
+                print("    \033[32m\033[1m[info] \033[00m%-42s : %.12g (residual %.3g)." % ("Eigenvalue %d " % j, theta[j], resid[j]))
+            print("    \033[32m\033[1m[info] \033[00m%-42s : %d (status %d)." % ("Number of iterations LOBPCG", it, st))
+            if args.dump_x:
+                np.concatenate([v.numpy() for v in X]).astype("<f8").tofile(args.dump_x)
+            return 0 if st == 0 else 3
         x, b = ctx.vec(rows), ctx.vec(bg)
         plan = None                                                                         # allocations and the cycles' capture: outside the timer
         if args.ahead is not None:
