@@ -1245,9 +1245,35 @@ int mgs_vecs_info(const mgs_ctx *ctx, int64_t out[8]);
  * MGS_ERR_INVALID, with a message, nothing launched: a NULL argument; m outside 1..MGS_EIG_MAX_BLOCK; rows < 3m + the declared null
  * vectors; a matrix that is not square; a row shard (the criteria of mgs_pcg_plan_create); columns of X that are the same vector, overlap,
  * or are shorter than A's rows; nu1 != nu2 or a K-cycle; a hierarchy whose null-space kind differs from A's.
- * Not served: A·x = λ·B·x, the largest eigenvalues, row shards, a device-resident Rayleigh–Ritz, null vectors that are not indicators. */
+ * Not served: the largest eigenvalues, row shards, a device-resident Rayleigh–Ritz, null vectors that are not indicators.
+ *
+ * mgs_eig_lobpcg_gen: the m smallest eigenpairs of A·x = λ·B·x (vibration modes K·x = λ·M·x, the normalised Laplacian L·x = λ·D·x).  The
+ * contract is that of mgs_eig_lobpcg with these differences.
+ *   A and B are symmetric (the caller's responsibility) and B is positive definite; the pivot rule on XᵀBX and SᵀBS enforces the latter as
+ *   far as it is seen: *status 2 also covers a start block whose XᵀBX fails the rule (an indefinite B, for one); 3 is unchanged.
+ *   X returns B-orthonormal (XᵀBX = I), theta ascending.
+ *   resid[j] = ‖A·x_j − θ_j·B·x_j‖₂ / (‖A‖∞ + |θ_j|·‖B‖∞), formed from a fresh A·X and B·X; both norms from the same row-sum kernel.
+ *   One iteration: R_j = AX_j − θ_j·BX_j (mgs_eig_residual); W_j = M·R_j for the active columns; W ← W − X·((BX)ᵀW); BW = B·W by SpMV;
+ *   Cholesky QR of W on ½(WᵀBW + its transpose) — the normalised-column pivot rule, the factor applied to W and BW —; AW = A·W; P is
+ *   B-orthonormalised on its own from PᵀBP, the factor applied to P, AP and BP; Rayleigh–Ritz with GA = SᵀAS and GB = ½(Sᵀ(BS) + (Sᵀ(BS))ᵀ)
+ *   through mgs_vecs_gram on (S, AS) and (S, BS); one coefficient matrix updates X, P, AX, AP, BX and BP in three mgs_vecs_combine calls.
+ *   When the rule refuses GB, P is dropped and the iteration is redone on [X W].
+ *   Work vectors: 8m + 2 (the staging pair, then AX, BX, W, AW, BW, P, AP, BP); the staging pair and its one cached cycle graph as above.
+ *   mgs_eig_info reports the same counters for this call; out[2] counts the SpMVs of A and B together, out[7] those of B alone.
+ *   B == NULL: the call is mgs_eig_lobpcg — the same code path, the same bits.
+ *   MGS_ERR_INVALID, with a message, nothing launched: everything mgs_eig_lobpcg refuses (rows < 3m), and: B not square, of another size or
+ *   of another context than A; B a row shard; a null space declared on A or on B — the complement would have to be B-orthogonal, which is
+ *   not served, and the message says so.
+ * mgs_eig_residual: r_i = fl(ax_i − fl(θ·bx_i)) for i < n and *nrm2 = Σ fl(r_i·r_i), one pass (three reads, one write; blas1.hip).  The sum
+ *   is taken with mgs_dot's launch decisions and folds — 16-byte lanes when ax, bx and r all start on 16 bytes and option "blas1_vec" is on
+ *   (an odd last element on one lane), 8-byte grid-stride lanes otherwise — so *nrm2 carries the bits of mgs_dot(r, r), and two identical
+ *   calls give identical bits (tests/eig_gen_ref.py restates them).  r may be ax or bx (the same start address).  nrm2 == NULL: the sum is
+ *   folded on the device and not fetched; the call does not wait.  MGS_ERR_INVALID, nothing launched: a NULL context or vector, a vector
+ *   of another context or shorter than n, n < 1, r overlapping ax or bx without being that vector. */
 #define MGS_EIG_MAX_BLOCK 8
 int mgs_eig_lobpcg(const mgs_csr *A, mgs_hier *h, int m, mgs_vec *const *X, double *theta, double *resid, int *max_iter, double *tol, int *status);
+int mgs_eig_lobpcg_gen(const mgs_csr *A, const mgs_csr *B, mgs_hier *h, int m, mgs_vec *const *X, double *theta, double *resid, int *max_iter, double *tol, int *status);
+int mgs_eig_residual(mgs_ctx *ctx, int64_t n, const mgs_vec *ax, const mgs_vec *bx, double theta, mgs_vec *r, double *nrm2);
 int mgs_eig_info(const mgs_ctx *ctx, int64_t out[8]);
 
 /* kernel-variant knobs for A/B measurements (initial values of every context: environment MGS_OPTIONS="key=value,...").  key: "spmv_variant", "xcd_remap", "nontemporal",

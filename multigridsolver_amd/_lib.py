@@ -191,6 +191,8 @@ PROTOTYPES = {
     "mgs_vecs_combine": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), c_dbl_p]),
     "mgs_vecs_info": (C.c_int, [C.c_void_p, c_i64_p]),
     "mgs_eig_lobpcg": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_dbl_p, c_dbl_p, c_int_p, c_dbl_p, c_int_p]),
+    "mgs_eig_lobpcg_gen": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_dbl_p, c_dbl_p, c_int_p, c_dbl_p, c_int_p]),
+    "mgs_eig_residual": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, c_dbl_p]),
     "mgs_eig_info": (C.c_int, [C.c_void_p, c_i64_p]),
     "mgs_guess_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "mgs_guess_destroy": (C.c_int, [C.c_void_p]),

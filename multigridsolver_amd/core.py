@@ -1186,20 +1186,32 @@ def vecs_info(ctx):
     out = (C.c_int64 * 8)(); check(lib().mgs_vecs_info(ctx.h, out), ctx.h); return [int(v) for v in out]
 
 
-def lobpcg(A, X, hier=None, max_iter=200, tol=1e-6):
+def lobpcg(A, X, hier=None, max_iter=200, tol=1e-6, B=None):
     """the len(X) smallest eigenpairs of the symmetric A by LOBPCG with hier's cycle as preconditioner (mgs_eig_lobpcg) →
     (status, iterations, theta, resid).  X: list of Vec, start vectors in, orthonormal Ritz vectors out (ascending theta);
     resid[j] = ‖A·x_j − θ_j·x_j‖₂/‖A‖∞ from a fresh A·X; status 0 all below tol / 1 max_iter / 2 start block rank deficient /
     3 trial basis rank deficient or not a number.  A declared null space (Csr.set_nullspace / set_nullspace_fields): the eigenpairs on its
-    complement"""
+    complement.
+    B: a symmetric positive definite Csr: the smallest eigenpairs of A·x = λ·B·x (mgs_eig_lobpcg_gen); X comes back B-orthonormal,
+    resid[j] = ‖A·x_j − θ_j·B·x_j‖₂/(‖A‖∞ + |θ_j|·‖B‖∞), status 2 also for a B that XᵀBX shows not to be positive definite; no declared null
+    space on A or B.  B=None is the call above, bit for bit"""
     m = len(X)
     th, rs = np.zeros(max(m, 1)), np.zeros(max(m, 1))
     mi, t, st = C.c_int(max_iter), C.c_double(tol), C.c_int(-1)
-    check(lib().mgs_eig_lobpcg(A.h, hier.h if hier else None, m, _handles(X), _dp(th), _dp(rs), C.byref(mi), C.byref(t), C.byref(st)), A.ctx.h)
+    check(lib().mgs_eig_lobpcg_gen(A.h, B.h if B is not None else None, hier.h if hier else None, m, _handles(X), _dp(th), _dp(rs), C.byref(mi), C.byref(t),
+                                   C.byref(st)), A.ctx.h)
     return st.value, mi.value, th[:m].copy(), rs[:m].copy()
 
 
+def eig_residual(ax, bx, theta, r):
+    """r = ax − θ·bx and → ‖r‖² in one pass (mgs_eig_residual): r_i = fl(ax_i − fl(θ·bx_i)), the sum with mgs_dot's folds, so the result carries
+    the bits of r.dot(r).  r may be ax or bx"""
+    s = C.c_double(0.0)
+    check(lib().mgs_eig_residual(ax.ctx.h, len(r), ax.h, bx.h, float(theta), r.h, C.byref(s)), ax.ctx.h)
+    return s.value
+
+
 def eig_info(ctx):
-    """counters of the last lobpcg on ctx: [0] iterations, [1] cycles, [2] SpMVs, [3] restarts without P, [4] columns locked at the end,
-    [5] work vectors, [6] hipGraph captures made during the call, [7] 0"""
+    """counters of the last lobpcg on ctx: [0] iterations, [1] cycles, [2] SpMVs (of A and, with B, of B), [3] restarts without P, [4] columns
+    locked at the end, [5] work vectors, [6] hipGraph captures made during the call, [7] SpMVs of B alone (0 without B)"""
     out = (C.c_int64 * 8)(); check(lib().mgs_eig_info(ctx.h, out), ctx.h); return [int(v) for v in out]

@@ -542,6 +542,24 @@ inline int LOBPCGiml(const DeviceMatrix &A, std::vector<Vector> &X, std::vector<
   std::vector<double> resid;
   return LOBPCGiml(A, X, theta, resid, &M, max_iter, tol);
 }
+// The generalised problem A·x = λ·B·x, B symmetric positive definite (mgs_eig_lobpcg_gen): X comes back B-orthonormal, tol is the largest
+// ‖A·x_j − θ_j·B·x_j‖₂/(‖A‖∞ + |θ_j|·‖B‖∞); status 2 also for a B that XᵀBX shows not to be positive definite.  No declared null space on A or B.
+inline int LOBPCGiml(const DeviceMatrix &A, const DeviceMatrix &B, std::vector<Vector> &X, std::vector<double> &theta, std::vector<double> &resid, const MultiGridPrecond *M,
+                     int &max_iter, double &tol) {
+  std::vector<mgs_vec *> x;
+  for (Vector &c : X) x.push_back(c.out());
+  theta.assign(X.size(), 0.0); resid.assign(X.size(), 0.0);
+  int status = -1;
+  check(mgs_eig_lobpcg_gen(A.handle(), B.handle(), M && M->use_preconditioner() ? M->handle() : nullptr, (int)x.size(), x.data(), theta.data(), resid.data(), &max_iter, &tol,
+                           &status), context());
+  return status;
+}
+// r = ax − θ·bx, → ‖r‖² with the bits of r.dot(r) (mgs_eig_residual: one pass); r may be ax or bx
+inline double eigResidual(const Vector &ax, const Vector &bx, double theta, Vector &r) {
+  double s = 0.0;
+  check(mgs_eig_residual(context(), r.size(), ax.handle(), bx.handle(), theta, r.out(), &s), context());
+  return s;
+}
 
 // ---------------------------------------------------------------- projected initial guesses (mgs.h: mgs_guess)
 // No reference counterpart: the reference solves one right-hand side (bicg.cpp:159-166).  For a caller who solves with the same operator

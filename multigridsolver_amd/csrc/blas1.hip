@@ -1,5 +1,5 @@
 // blas1.hip — vector updates and deterministic reductions: axpby / axpbypcz, dot, dot2, update + dot2, the PCG passes, sum / mean / shift for the
-// constant null space, the label-segmented sum / shift for the field-wise one, several inner products in one pass (mdot), the multi-axpy with two sums (maxpy), the K-cycle's orthogonalised pair, and
+// constant null space, the label-segmented sum / shift for the field-wise one, the eigenresidual r = ax − θ·bx with its norm, several inner products in one pass (mdot), the multi-axpy with two sums (maxpy), the K-cycle's orthogonalised pair, and
 // the host half of every reduction: partial buffers, the staged fold, results posted to the host.  gfx950 only.
 // Every reduction pass leaves one partial (pair) per workgroup in a fixed layout and ends in the folds of blas1.hpp; the 8- and 16-byte forms
 // of a pass are separate kernels, their summation orders differ on purpose (tests/blas1_ref.py restates both).
@@ -241,6 +241,39 @@ __global__ __launch_bounds__(TB) void dot_block_vec_kernel(int64_t n, const doub
     if (NP == 2) { const vd2 a = zv[i], b = wv[i]; s1 += a.x * b.x; s1 += a.y * b.y; }
   }
   if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) { s0 += x[n - 1] * y[n - 1]; if (NP == 2) s1 += z[n - 1] * w[n - 1]; }
+  BLAS1_FOLD2(s0, s1, sh, part);
+}
+
+// ------------------------------------------------------------------ eigenresidual (mgs_eig_residual): r = ax − θ·bx with ‖r‖², one pass
+// Per entry t = fl(θ·bx_i), r_i = fl(ax_i − t), and fl(r_i·r_i) is added (-ffp-contract=off keeps the three roundings apart).  32 B per row: three
+// reads and one write, where a 2 → 1 combine followed by k_dot moves 40 B in two launches.  The sums are k_dot's: the 8-byte form leaves one
+// partial per workgroup for dot_final_kernel, the 16-byte form a pair (second sum zero) for k_dot2_finish, lane t adding its pair x then y and the
+// odd last element going to lane 0 of workgroup 0 — ‖r‖² carries the bits of k_dot(r, r).  r may be ax or bx: a lane loads its entry (pair) of
+// both inputs before it stores, and no lane reads what another one stores (no __restrict__ on the three).
+__global__ __launch_bounds__(TB) void eig_residual_kernel(int64_t n, const double *ax, const double *bx, double theta, double *r, double *__restrict__ part) {
+  __shared__ double sh[TB / 64];
+  double s = 0.0;
+  int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * TB;
+  for (; i < n; i += stride) { const double t = theta * bx[i]; const double ri = ax[i] - t; r[i] = ri; s += ri * ri; }
+  BLAS1_FOLD1(s, sh, part, false);
+}
+__global__ __launch_bounds__(TB) void eig_residual_vec_kernel(int64_t n, const double *ax, const double *bx, double theta, double *r, double *__restrict__ part, int nts) {
+  __shared__ double sh[2][TB / 64];
+  const int64_t n2 = n >> 1;
+  const vd2 *av = reinterpret_cast<const vd2 *>(ax);
+  const vd2 *bv = reinterpret_cast<const vd2 *>(bx);
+  vd2 *rv = reinterpret_cast<vd2 *>(r);
+  double s0 = 0.0, s1 = 0.0;
+  const int64_t stride = (int64_t)gridDim.x * TB;
+  for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < n2; i += stride) {
+    const vd2 a = av[i], b = bv[i]; vd2 t, o;
+    t.x = theta * b.x; t.y = theta * b.y;
+    o.x = a.x - t.x; o.y = a.y - t.y;
+    st2(rv + i, o, nts != 0);
+    s0 += o.x * o.x; s0 += o.y * o.y;
+  }
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) { const double t = theta * bx[n - 1]; const double ri = ax[n - 1] - t; r[n - 1] = ri; s0 += ri * ri; }
   BLAS1_FOLD2(s0, s1, sh, part);
 }
 
@@ -736,6 +769,27 @@ int k_dot(mgs_ctx *ctx, int64_t n, const double *x, const double *y, double *out
   const Post pa = out_host ? begin_post(ctx) : NO_POST;
   hipLaunchKernelGGL(dot_final_kernel, dim3(1), dim3(TB), 0, ctx->stream, nb, ctx->red_dev, ctx->red_dev + DOT_BLOCKS, pa);
   if (ctx->ncomm) MGS_TRY(mgs_comm_allreduce_sum(ctx->ncomm, ctx->red_dev + DOT_BLOCKS, 1));   // sum over the row shards, on this stream
+  return fetch_or_leave(ctx, 1, out_host, pa);
+}
+// r = ax − θ·bx and ‖r‖² (mgs_eig_residual): k_dot's launch decisions with r among the pointers that must start on 16 bytes, k_dot's folds, so the
+// norm is k_dot(r, r) bit for bit.  out_host = NULL: enqueue and fold, do not fetch.
+int k_eig_residual(mgs_ctx *ctx, int64_t n, const double *ax, const double *bx, double theta, double *r, double *out_host) {
+  if (ctx->opt_blas1_vec && n >= 2 && al16(ax) && al16(bx) && al16(r)) {
+    RedLaunch L;
+    MGS_TRY(red_launch(ctx, n, true, n / 2, &L));
+    hipLaunchKernelGGL(eig_residual_vec_kernel, dim3(L.nb), dim3(TB), 0, ctx->stream, n, ax, bx, theta, r, L.part, L.nts);
+    MGS_HIP(ctx, hipGetLastError());
+    if (!out_host) return k_dot2_finish(ctx, L.nb, L.part, nullptr);
+    double two[2] = {0.0, 0.0};
+    MGS_TRY(k_dot2_finish(ctx, L.nb, L.part, two));
+    *out_host = two[0];
+    return MGS_OK;
+  }
+  const int nb = grid_cap(n, DOT_BLOCKS);
+  hipLaunchKernelGGL(eig_residual_kernel, dim3(nb), dim3(TB), 0, ctx->stream, n, ax, bx, theta, r, ctx->red_dev);
+  const Post pa = out_host ? begin_post(ctx) : NO_POST;
+  hipLaunchKernelGGL(dot_final_kernel, dim3(1), dim3(TB), 0, ctx->stream, nb, ctx->red_dev, ctx->red_dev + DOT_BLOCKS, pa);
+  if (ctx->ncomm) MGS_TRY(mgs_comm_allreduce_sum(ctx->ncomm, ctx->red_dev + DOT_BLOCKS, 1));
   return fetch_or_leave(ctx, 1, out_host, pa);
 }
 int k_dot_dev(mgs_ctx *ctx, int64_t n, const double *x, const double *y, double *out_dev) {

@@ -479,6 +479,8 @@ int k_rand(mgs_ctx *ctx, double *d, int64_t n, uint64_t seed, int64_t off);
 int k_axpby(mgs_ctx *ctx, int64_t n, double a, const double *x, double b, double *y);
 int k_axpbypcz(mgs_ctx *ctx, int64_t n, double a, const double *x, double b, const double *y, double c, double *z);
 int k_dot(mgs_ctx *ctx, int64_t n, const double *x, const double *y, double *out_host);
+// r = ax − θ·bx (t = fl(θ·bx_i), r_i = fl(ax_i − t)) with ‖r‖² = k_dot(r, r) bit for bit, one pass; r may be ax or bx; out_host = NULL: folded, not fetched
+int k_eig_residual(mgs_ctx *ctx, int64_t n, const double *ax, const double *bx, double theta, double *r, double *out_host);
 int k_dense_gemv(mgs_ctx *ctx, int n, const double *M, const double *b, double *x);
 int k_dot_dev(mgs_ctx *ctx, int64_t n, const double *x, const double *y, double *out_dev);
 int k_update_dot2(mgs_ctx *ctx, int64_t n, double a, const double *x, double b, const double *y, double *z, const double *w, double *out_host2);

@@ -54,6 +54,9 @@ def main(argv=None):
                     help="instead of a solve: the K smallest eigenpairs of the symmetric A by LOBPCG (K <= 8) with the hierarchy the other options describe "
                          "as preconditioner (V(nu, nu), no K-cycle), from random start vectors; --tol bounds |A x - theta x|/|A|_inf; no right-hand side; "
                          "single GPU only")
+    ap.add_argument("--mass", default=None, metavar="FILE.mtx",
+                    help="with --eigs: the symmetric positive definite B of the generalised problem A x = theta B x (MatrixMarket, the same reader as the operator); "
+                         "the vectors come back B-orthonormal, --tol bounds |A x - theta B x|/(|A|_inf + |theta| |B|_inf); not with --nullspace")
     ap.add_argument("--dump-x", default=None, help="write the solution (rank order, raw little-endian f64)")
     args = ap.parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1")); rank = int(os.environ.get("RANK", "0"))
@@ -71,6 +74,8 @@ def main(argv=None):
         raise SystemExit("--minres-ahead N (N >= 0) goes with --solver minres on a single GPU")
     if args.eigs and (world > 1 or args.eigs < 0 or args.solver is not None):
         raise SystemExit("--eigs K (K >= 1) runs on a single GPU and takes no --solver")
+    if args.mass is not None and (not args.eigs or args.nullspace != "none"):
+        raise SystemExit("--mass FILE.mtx goes with --eigs K and without --nullspace (a null space together with B is not served)")
     if args.solver is None:
         args.solver = "bicgstab"
     if world > 1:
@@ -97,8 +102,13 @@ def main(argv=None):
             h.set_operand_precision(args.operand_bits)
         if args.eigs:
             X = [ctx.vec(rows).rand(1, j * rows) for j in range(args.eigs)]
+            B = None
+            if args.mass is not None:
+                B = mg.Csr.from_mtx(ctx, args.mass)
+                if B.shape != (rows, rows):
+                    raise SystemExit("--mass: B is %d x %d, the operator %d x %d" % (B.shape + (rows, rows)))
             ctx.sync(); t0 = time.perf_counter()
-            st, it, theta, resid = mg.lobpcg(A, X, h, args.max_iter, args.tol)
+            st, it, theta, resid = mg.lobpcg(A, X, h, args.max_iter, args.tol, B)
             ctx.sync(); dt = time.perf_counter() - t0
             sys.stderr.write("    \033[1;34m[time] \033[0m%-42s : %f.\n" % ("LOBPCG_SolveTimer", dt))
             for j in range(args.eigs):
